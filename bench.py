@@ -28,6 +28,8 @@ library's own RCCL communicator (ncclCommInitRank, its id carried by torch's sto
 callbacks); every rank delivers its own blocks to its own host memory, from threads and pinned buffers bound to its GPU's NUMA node.
 --one-gpu: the N ranks as N contexts on GPU 0 with gloo collectives (the plumbing check of a single-GPU box).
 --no-torch: N = 1 without importing torch, on the system HIP runtime only: the configuration rocprofv3 traces unperturbed.
+--dump-outputs DIR: N = 1, what the last timed step delivered (every record's statistics, the head and tail of its text) as
+DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs (bench_dump.py).
 """
 import argparse
 import json
@@ -53,6 +55,25 @@ WORKLOADS = {
     "onthq60": ("errhmm", "ERRHMM-ONT-HQ.model", 60.0, 1, "BASELINE configs[4]: wgs errhmm ERRHMM-ONT-HQ depth 60"),
     "qshmm10": ("qshmm", "QSHMM-RSII.model", 20.0, 10, "BASELINE configs[2]: wgs qshmm QSHMM-RSII depth 20 pass-num 10 (BAM records)"),
 }
+
+_MODEL_DIR = None
+
+
+def model_path(name):
+    """a model file for the context loaders and the CPU baseline: the committed gzip-compressed copy under
+    tests/golden/models, unpacked into a temporary directory of this process (removed at exit) -- bench.py writes nothing
+    into the tree, which may be read-only to whoever runs it"""
+    import gzip
+    global _MODEL_DIR
+    if _MODEL_DIR is None:
+        _MODEL_DIR = tempfile.TemporaryDirectory(prefix="pbsim_bench_models_")
+    p = os.path.join(_MODEL_DIR.name, name)
+    if not os.path.exists(p):
+        with gzip.open(os.path.join(ROOT, "tests", "golden", "models", name + ".gz"), "rb") as f, open(p + ".tmp", "wb") as g:
+            g.write(f.read())
+        os.replace(p + ".tmp", p)
+    return p
+
 
 def physical_cores():
     """(physical cores, logical CPUs) this process may run on"""
@@ -110,7 +131,7 @@ def cpu_baseline(model="ERRHMM-ONT.model", depth=20, sample_bp=4_000_000):
             f.write(b">chr1\n")
             lines = seq.reshape(-1, 80)
             f.write(np.concatenate([lines, np.full((lines.shape[0], 1), 10, np.uint8)], axis=1).tobytes())
-        mpath = harness.model_path(model)
+        mpath = model_path(model)
 
         def command(exe, prefix, seed, dep, philox=False):
             args = ["--strategy", "wgs", "--method", "errhmm", "--errhmm", mpath, "--genome", fa,
@@ -181,44 +202,63 @@ def cpu_baseline(model="ERRHMM-ONT.model", depth=20, sample_bp=4_000_000):
 
 class CountingTextSink:
     """pbsim_sink of the per-unit drivers (pbsim_simulate_trans / _sample): receives the members in pinned host memory and only
-    counts them; with deflate bit 2 the two callbacks arrive from two threads (one counter each)"""
+    counts them; with deflate bit 2 the two callbacks arrive from two threads (one counter each).  `capture`
+    (bench_dump.OutputCapture): also keeps what --dump-outputs writes, the unit's streams as record 1"""
 
-    def __init__(self, P):
+    def __init__(self, P, capture=None):
         self.read_bytes = self.maf_bytes = 0
+        self.capture = capture
         self._cbs = (P.SINK_CB(self._read), P.SINK_CB(self._maf))
         self.sink = P.Sink(None, *self._cbs)
 
     def _read(self, user, text, n):
+        if self.capture is not None:
+            self.capture.put(0, 1, ctypes_addr(text), n, self.read_bytes)
         self.read_bytes += n
         return 1
 
     def _maf(self, user, text, n):
+        if self.capture is not None:
+            self.capture.put(1, 1, ctypes_addr(text), n, self.maf_bytes)
         self.maf_bytes += n
         return 1
+
+
+def ctypes_addr(text):
+    """the address a sink callback's `const char *` points at"""
+    import ctypes
+    return ctypes.cast(text, ctypes.c_void_p).value
 
 
 def timed_unit_job(a, torch, P, C, ctx, fn, workload, kernel, extra_cfg=None):
     """A per-unit driver (`fn`: pbsim_simulate_trans / pbsim_simulate_sample) under the headline metric: every
     step is the whole job INCLUDING the delivery of its output -- FASTQ + MAF compressed on the GPU (pbsim_set_deflate(7)) and
-    copied into pinned host memory where a sink counts them, as run_job(True) does for the wgs job.  At least --steps steps and
-    at least a second of them; the same job with its text left in HBM beside it (median of five)."""
-    def run(deliver):
+    copied into pinned host memory where a sink counts them, as run_job(True) does for the wgs job.  --steps timed steps; the
+    same job with its text left in HBM beside it (median of five)."""
+    if a.dump_outputs:
+        import bench_dump
+
+    def run(deliver, capture=None):
         ctx.set_deflate(7 if deliver else 0)
-        sink = CountingTextSink(P)
+        sink = CountingTextSink(P, capture)
         P._check(fn(ctx.h, C.byref(sink.sink) if deliver else None))
         return sink
     for _ in range(max(1, a.warmup)):
-        run(True)
+        sk = run(True)
     torch.cuda.synchronize()
     ctx.prof_reset()
-    steps, host_bytes = 0, 0
+    steps, host_bytes, dump = a.steps, 0, None
     t0 = time.perf_counter()
-    while steps < max(10, a.steps) or time.perf_counter() - t0 < 1.0:
-        sk = run(True)
+    for i in range(steps):
+        if a.dump_outputs and i == steps - 1:   # (the step before was the same job: where its streams ended)
+            dump = bench_dump.OutputCapture(1, expect={1: (sk.read_bytes, sk.maf_bytes)})
+        sk = run(True, dump)
         host_bytes += sk.read_bytes + sk.maf_bytes
-        steps += 1
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if dump is not None:
+        dump.done(1, ctx.stats(), sk.read_bytes, sk.maf_bytes)
+        write_dump(dump, a.dump_outputs)
     walk_ms, launches, _ = ctx.prof_get()
     st = ctx.stats()
     bases, reads = st.res_len_total, st.res_num
@@ -297,7 +337,7 @@ def bench_trans(a, torch, harness, P, local):
     p = P.default_params(strategy=P.STRATEGY_TRANS, method=P.METHOD_ERR, seed=1)
     ctx = P.Context(p, local)
     ctx.set_scratch_bytes(int(a.scratch_gib * (1 << 30)))
-    ctx.load_errhmm(harness.model_path("ERRHMM-SEQUEL.model"))
+    ctx.load_errhmm(model_path("ERRHMM-SEQUEL.model"))
     t0 = time.perf_counter()
     ctx.set_transcripts(["T%d" % i for i in range(n)], [int(x) for x in plus], [int(x) for x in minus], seqs)
     t_set = time.perf_counter() - t0
@@ -461,20 +501,26 @@ def make_records(torch, harness, dist, dev, cdev, rank, world, n_rec, G):
 
 
 class CountingSink:
-    """receives the members in pinned host memory and only counts them (one counter per sink: the two arrive from two threads)"""
+    """receives the members in pinned host memory and only counts them (one counter per sink: the two arrive from two threads).
+    `capture` (bench_dump.OutputCapture): also keeps what --dump-outputs writes"""
 
-    def __init__(self, P, C):
+    def __init__(self, P, C, capture=None):
         self.read_bytes = self.maf_bytes = 0
         self.stats = {}
+        self.capture = capture
         self._cbs = (P.REC_TEXT_CB(self._read), P.REC_TEXT_CB(self._maf), P.REC_DONE_CB(self._done))
         self.sink = P.RecordSink(None, *self._cbs)
         self.P, self.C = P, C
 
     def _read(self, user, rec, text, n, off):
+        if self.capture is not None:
+            self.capture.put(0, rec, ctypes_addr(text), n, off)
         self.read_bytes += n
         return 1
 
     def _maf(self, user, rec, text, n, off):
+        if self.capture is not None:
+            self.capture.put(1, rec, ctypes_addr(text), n, off)
         self.maf_bytes += n
         return 1
 
@@ -482,7 +528,15 @@ class CountingSink:
         s = self.P.Stats()
         self.C.memmove(self.C.byref(s), st, self.C.sizeof(self.P.Stats))
         self.stats[rec] = (s.res_num, s.res_len_total, rb, mb)
+        if self.capture is not None:
+            self.capture.done(rec, s, rb, mb)
         return 1
+
+
+def write_dump(capture, directory):
+    """--dump-outputs: the captured step's arrays under `directory` (after the timed region)"""
+    shapes = capture.write(directory)
+    sys.stderr.write("bench.py: outputs of the last timed step -> %s: %s\n" % (directory, shapes))
 
 
 def steady_state(a, torch, harness, P, local, model, genome_ptr, G, qs=False, pass_num=1):
@@ -490,7 +544,7 @@ def steady_state(a, torch, harness, P, local, model, genome_ptr, G, qs=False, pa
     p = P.default_params(strategy=P.STRATEGY_WGS, method=P.METHOD_QS if qs else P.METHOD_ERR, seed=1, depth=20.0, pass_num=pass_num)
     ctx = P.Context(p, local)
     ctx.set_scratch_bytes(int(a.scratch_gib * (1 << 30)))
-    (ctx.load_qshmm if qs else ctx.load_errhmm)(harness.model_path(model))
+    (ctx.load_qshmm if qs else ctx.load_errhmm)(model_path(model))
     ctx.set_reference_device(genome_ptr, G, 1)
     B, S = ctx.batch_capacity(), 2
 
@@ -529,7 +583,7 @@ def other_configs():
     """The BASELINE configurations the headline is not quoted on, under the same metric, so that every one of them is timed by
     whoever runs `python bench.py`: configs[4] (ERRHMM-ONT-HQ depth 60, the 3 Gbp genome; one timed step), configs[2] (QSHMM-RSII
     --pass-num 10 depth 20 as BAM records + MAF; the four-record job, one timed step of 18 s -- round 5 timed ONE record),
-    configs[3] (100 000 transcripts) and the sampling method (>= 10 steps and >= 1 s each: timed_unit_job).  Every one delivers
+    configs[3] (100 000 transcripts) and the sampling method (ten timed steps each: timed_unit_job).  Every one delivers
     its output like the headline (compressed on the GPU, into pinned host memory).  Each is this same script as a child
     process (started after this process has closed its context; never an exec); what is kept of its line is below.  A
     configuration that fails is reported as {"error": ..} -- it never takes the headline's line with it."""
@@ -539,7 +593,8 @@ def other_configs():
             ("configs[3] trans", ["--workload", "trans"]),
             ("sampling method", ["--workload", "sample"]))
     for name, flags in runs:
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--no-extras", "--no-cpu-baseline",
+        steps = "10" if flags[1] in ("trans", "sample") else "1"
+        cmd = [sys.executable, os.path.abspath(__file__), "--steps", steps, "--warmup", "1", "--no-extras", "--no-cpu-baseline",
                "--detail", ""] + flags
         t0 = time.perf_counter()
         try:
@@ -616,7 +671,7 @@ def critical_path(bd_all, K):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3, help="timed runs of the whole job")
+    ap.add_argument("--steps", type=int, default=3, help="timed runs of the whole job (ms_per_step = their wall time / steps)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--record-len", type=int, default=RECORD_LEN)
     ap.add_argument("--records", type=int, default=4)
@@ -661,7 +716,14 @@ def main():
                          "traces without perturbing it (class NoTorch)")
     ap.add_argument("--param", action="append", default=[],
                     help="experiment only: override a pbsim_params field, e.g. --param len_sd=0 (not the headline workload)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="--gpus 1: after the timed steps, write what the last one delivered as DIR/<name>.npy (bench_dump.py: "
+                         "every record's statistics and the head and tail of its FASTQ / MAF text; at most 64 MB)")
     a = ap.parse_args()
+    if a.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
+    if a.dump_outputs and a.gpus != 1:
+        sys.exit("bench.py: --dump-outputs is for --gpus 1 (a rank receives only its own pieces of the streams)")
     if a.no_torch:
         if a.gpus != 1 or a.workload in ("trans", "sample"):
             sys.exit("bench.py: --no-torch is for --gpus 1 and the wgs workloads")
@@ -687,6 +749,8 @@ def main():
 
     import ctypes as C
     import pbsim3_amd as P
+    if a.dump_outputs:
+        import bench_dump
     # host placement first: this thread, the threads the library starts and its pinned staging go to the GPU's NUMA node
     numa = P.bind_host_to_device(local)
     if a.no_torch:
@@ -731,7 +795,7 @@ def main():
     ctx = P.Context(p, local)
     if a.no_torch:
         torch.cuda.ctx = ctx
-    (ctx.load_qshmm if qs else ctx.load_errhmm)(harness.model_path(model))
+    (ctx.load_qshmm if qs else ctx.load_errhmm)(model_path(model))
     if pass_num > 1:
         ctx.set_bam_output(True)
     with P.Context(p, local) as warm:      # the library's first kernel launch loads its code object (0.15 s in a fresh process): not K0's
@@ -774,8 +838,8 @@ def main():
     else:
         cref = None
 
-    def run_job(deliver):
-        sink = CountingSink(P, C)
+    def run_job(deliver, capture=None):
+        sink = CountingSink(P, C, capture)
         ctx.set_deflate(7 if deliver else 0)    # bits 0/1: both sinks receive gzip members; bit 2: served from two host threads
         if not deliver:
             sink.sink = P.RecordSink(None, P.REC_TEXT_CB(), P.REC_TEXT_CB(), sink._cbs[2])
@@ -784,15 +848,17 @@ def main():
 
     deliver = not a.hbm_only
     for _ in range(max(1, a.warmup)):            # at least one untimed run: every slot allocates its pools
-        run_job(deliver)
+        sink = run_job(deliver)
     ctx.prof_reset()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    sinks, counters, bd_sum = [], [], {}
-    for _ in range(a.steps):
-        sinks.append(run_job(deliver))
+    sinks, counters, bd_sum, dump = [], [], {}, None
+    for i in range(a.steps):
+        if a.dump_outputs and i == a.steps - 1:  # (the step before was the same job: where its streams ended)
+            dump = bench_dump.OutputCapture(NR, expect={r: v[2:] for r, v in (sinks[-1] if sinks else sink).stats.items()})
+        sinks.append(run_job(deliver, dump))
         counters.append(ctx.job_counters())
         bd = ctx.job_breakdown()
         for k, v in bd.items():
@@ -801,6 +867,8 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if dump is not None:
+        write_dump(dump, a.dump_outputs)
     walk_ms, launches, _ = ctx.prof_get()
     walk_busy_ms = ctx.prof_walk_busy()
     tail_ms, tail_launches = ctx.prof_tail()
@@ -978,7 +1046,8 @@ def main():
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import replay_ranks as RR
             t_tab = time.perf_counter()
-            tables = RR.build_tables(P, harness, p, model, qs, recs, G, local)
+            # (build_tables takes its model file from `harness`: this script's unpacked copy)
+            tables = RR.build_tables(P, argparse.Namespace(model_path=model_path), p, model, qs, recs, G, local)
             t_tab = time.perf_counter() - t_tab
 
             def run_with(comm):

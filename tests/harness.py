@@ -5,33 +5,69 @@ import hashlib
 import json
 import os
 import subprocess
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 ORACLE = os.path.join(ROOT, "oracle", "pbsim_oracle")
 REF_GLIBC = os.path.join(ROOT, "oracle", "_ref", "pbsim_ref")
 REF_PHILOX = os.path.join(ROOT, "oracle", "_ref", "pbsim_ref_philox")
-# model files are inputs (format contract); tests look for them here first and
-# fall back to the read-only reference mount in this container
+# model files are inputs (format contract): committed gzip-compressed, unpacked on first use (cached_file)
 MODEL_GZ_DIR = os.path.join(ROOT, "tests", "golden", "models")
 MODEL_CACHE = os.path.join(MODEL_GZ_DIR, "_unpacked")
+
+
+def cached_file(cache, name, make, src=None):
+    """cache/<name>, written by make(path) on first use.  When the tree cannot be written to (a checkout owned by another
+    user, a read-only mount) the file goes to a directory of this user's under the system's temporary directory instead,
+    keyed by the content of `src` (the committed file it is made from; without one, of this file, which generates it) so that
+    a later checkout never reads a stale copy."""
+    p = os.path.join(cache, name)
+    if os.path.exists(p):
+        return p
+    try:
+        return _write_cached(cache, p, make)
+    except OSError:
+        if os.path.exists(p):
+            return p
+    top = os.path.join(tempfile.gettempdir(), "pbsim3_amd-%d" % os.getuid())
+    os.makedirs(top, mode=0o700, exist_ok=True)
+    if os.stat(top).st_uid != os.getuid():
+        raise PermissionError("%s belongs to another user" % top)
+    key = hashlib.sha1(open(src or os.path.abspath(__file__), "rb").read()).hexdigest()[:16]
+    d = os.path.join(top, os.path.relpath(cache, ROOT), key)
+    q = os.path.join(d, name)
+    return q if os.path.exists(q) else _write_cached(d, q, make)
+
+
+def _write_cached(d, p, make):
+    os.makedirs(d, exist_ok=True)
+    tmp = p + ".%d.tmp" % os.getpid()
+    try:
+        make(tmp)
+        os.replace(tmp, p)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return p
+
+
+def gunzip_to(src):
+    """make() of cached_file: the decompressed bytes of `src`"""
+    def make(dst):
+        import gzip
+        with gzip.open(src, "rb") as f, open(dst, "wb") as g:
+            g.write(f.read())
+    return make
 
 
 def model_path(name):
     """FIC-HMM model files are INPUT DATA (format contract); the six
     used by the tests are committed gzip-compressed and unpacked on first use."""
-    import gzip
-    p = os.path.join(MODEL_CACHE, name)
-    if not os.path.exists(p):
-        src = os.path.join(MODEL_GZ_DIR, name + ".gz")
-        if not os.path.exists(src):
-            raise FileNotFoundError(name)
-        os.makedirs(MODEL_CACHE, exist_ok=True)
-        tmp = p + ".%d.tmp" % os.getpid()
-        with gzip.open(src, "rb") as f, open(tmp, "wb") as g:
-            g.write(f.read())
-        os.replace(tmp, p)
-    return p
+    src = os.path.join(MODEL_GZ_DIR, name + ".gz")
+    if not os.path.exists(os.path.join(MODEL_CACHE, name)) and not os.path.exists(src):
+        raise FileNotFoundError(name)
+    return cached_file(MODEL_CACHE, name, gunzip_to(src), src)
 
 
 INPUT_CACHE = os.path.join(GOLDEN, "inputs", "_unpacked")
@@ -99,36 +135,29 @@ def load_fullsize():
 def input_path(name):
     """tests/golden/inputs/<name>: committed as is, committed gzip-compressed (the reference's own sample files: data),
     or generated on first use -- `synth_<bases>_<seed>.fa`: one FASTA record of that many synth_bases, 80 per line."""
-    import gzip
     import re
     p = os.path.join(GOLDEN, "inputs", name)
     if os.path.exists(p):
         return p
-    q = os.path.join(INPUT_CACHE, name)
-    if os.path.exists(q):
-        return q
-    os.makedirs(INPUT_CACHE, exist_ok=True)
-    tmp = q + ".%d.tmp" % os.getpid()
     m = re.fullmatch(r"synth_(\d+)_(\d+)\.fa", name)
     if os.path.exists(p + ".gz"):
-        with gzip.open(p + ".gz", "rb") as f, open(tmp, "wb") as g:
-            g.write(f.read())
-    elif m:
-        import numpy as np
-        n, seed = int(m.group(1)), int(m.group(2))
-        b = synth_bases(n, seed)
-        full = n // 80 * 80
-        lines = np.empty((full // 80, 81), dtype=np.uint8)
-        lines[:, :80] = b[:full].reshape(-1, 80)
-        lines[:, 80] = 10
-        with open(tmp, "wb") as g:
-            g.write(b">synth_%d_%d\n" % (n, seed))
-            g.write(lines.tobytes())
-            if full < n:
-                g.write(b[full:].tobytes() + b"\n")
-    else:
-        raise FileNotFoundError(name)
-    os.replace(tmp, q)
+        return cached_file(INPUT_CACHE, name, gunzip_to(p + ".gz"), p + ".gz")
+    if m:
+        def make(tmp):
+            import numpy as np
+            n, seed = int(m.group(1)), int(m.group(2))
+            b = synth_bases(n, seed)
+            full = n // 80 * 80
+            lines = np.empty((full // 80, 81), dtype=np.uint8)
+            lines[:, :80] = b[:full].reshape(-1, 80)
+            lines[:, 80] = 10
+            with open(tmp, "wb") as g:
+                g.write(b">synth_%d_%d\n" % (n, seed))
+                g.write(lines.tobytes())
+                if full < n:
+                    g.write(b[full:].tobytes() + b"\n")
+        return cached_file(INPUT_CACHE, name, make)
+    raise FileNotFoundError(name)
     return q
 
 

@@ -5,6 +5,7 @@ import ctypes as C
 import hashlib
 import os
 import re
+import shutil
 import subprocess
 
 import numpy as np
@@ -41,14 +42,13 @@ def test_library_exports_every_declared_symbol():
         assert n in bound, f"{n} is declared in the header but not bound in pbsim3_amd.API"
 
 
-def test_fat_binary_is_gfx950_only():
-    out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "--offloading", P.lib_path()],
-                         capture_output=True, text=True, cwd="/tmp").stdout
+def test_fat_binary_is_gfx950_only(tmp_path):
+    # llvm-objdump drops the extracted bundles next to its input: a copy, so that the build tree may be read-only
+    lib = str(tmp_path / os.path.basename(P.lib_path()))
+    shutil.copyfile(P.lib_path(), lib)
+    out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "--offloading", lib],
+                         capture_output=True, text=True, cwd=str(tmp_path)).stdout
     archs = set(re.findall(r"amdgcn-amd-amdhsa--(gfx[0-9a-z]+)", out))
-    d = os.path.dirname(P.lib_path())   # llvm-objdump drops the extracted bundles next to the input
-    for f in os.listdir(d):
-        if f.startswith(os.path.basename(P.lib_path()) + "."):
-            os.remove(os.path.join(d, f))
     assert archs == {"gfx950"}, archs
 
 
