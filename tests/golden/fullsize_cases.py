@@ -5,8 +5,13 @@ output stream plus the stderr report -- the streams themselves are 10-65 GB of t
 A record is `harness.synth_bases(length, seed)`: plain 64-bit integer arithmetic, the same bytes on the CPU (numpy, where the
 reference runs) and on the GPU box (numpy or torch, `harness.synth_bases_torch`), so nothing large is committed.
 
-  args      : the reference's command line without --genome / --prefix (MODEL:<name> = tests/golden/models/<name>)
-  record    : (length, seed) of the one FASTA record
+  args        : the reference's command line without --genome / --transcript / --sample / --prefix
+                (MODEL:<name> = tests/golden/models/<name>)
+  record      : (length, seed) of the one FASTA record (--genome)
+  transcripts : (n, seed) of harness.synth_transcripts: the --transcript file (trans cases have no record)
+  sample      : (n, seed) of harness.synth_sample_fastq: the --sample FASTQ
+
+A generated input's sha256 is kept with the digests (`input_sha256`), so that a generator that drifts fails as such.
 """
 
 FULLSIZE = {
@@ -41,5 +46,28 @@ FULLSIZE = {
         "record": (20_000_000, 102),
         "args": ["--strategy", "wgs", "--method", "qshmm", "--qshmm", "MODEL:QSHMM-RSII.model", "--depth", "20", "--pass-num", "10",
                  "--seed", "1"],
+    },
+    # the transcript and sampling machinery at small size: the CPU suite runs the oracle on them (tests/test_fullsize_digests.py)
+    "t1_trans_small": {
+        "transcripts": (200, 5),
+        "args": ["--strategy", "trans", "--method", "errhmm", "--errhmm", "MODEL:ERRHMM-SEQUEL.model", "--seed", "1"],
+    },
+    "t2_sample_small": {
+        "record": (2_000_000, 107),
+        "sample": (300, 6),
+        "args": ["--strategy", "wgs", "--method", "sample", "--depth", "5", "--seed", "1"],
+    },
+    # configs[3] at the benchmarked size: 100 000 transcripts of bench.py --workload trans's shape + the edge units of
+    # harness.transcript_edge_units (~2 M reads)
+    "c3_trans_errhmm_sequel_100k": {
+        "transcripts": (100_000, 3),
+        "args": ["--strategy", "trans", "--method", "errhmm", "--errhmm", "MODEL:ERRHMM-SEQUEL.model", "--seed", "1"],
+    },
+    # bench.py --workload sample's job: a 100 Mbp record at depth 20 (2 Gbases) sampled from 50 000 quality strings
+    # (430 M characters, 370 M of them kept by the filter: about 5.4 sweeps over the profile)
+    "s_sample_100m_d20": {
+        "record": (100_000_000, 108),
+        "sample": (50_000, 9),
+        "args": ["--strategy", "wgs", "--method", "sample", "--depth", "20", "--seed", "1"],
     },
 }

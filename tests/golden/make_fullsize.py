@@ -27,37 +27,27 @@ from fullsize_cases import FULLSIZE  # noqa: E402
 OUT = os.path.join(HERE, "fullsize.json")
 
 
-def write_fasta(path, length, seed):
-    import numpy as np
-    seq = harness.synth_bases(length, seed)
-    with open(path, "wb") as f:
-        f.write(b">synth_%d_%d\n" % (length, seed))
-        width = 80
-        full = length // width * width
-        step = width * (1 << 16)
-        for a in range(0, full, step):
-            rows = seq[a:min(full, a + step)].reshape(-1, width)
-            f.write(np.concatenate([rows, np.full((rows.shape[0], 1), 10, np.uint8)], axis=1).tobytes())
-        if full < length:
-            f.write(seq[full:].tobytes() + b"\n")
-
-
 def run_case(name, stubs):
     case = FULLSIZE[name]
-    length, seed = case["record"]
     args = harness.resolve(case["args"])
     t0 = time.time()
     with tempfile.TemporaryDirectory(dir="/dev/shm") as td:
-        fa = os.path.join(td, "g.fa")
-        write_fasta(fa, length, seed)
+        inputs, digests = harness.write_case_inputs(case, td)
         env = dict(os.environ, PATH=stubs + ":" + os.environ["PATH"], PBSHIM_SEED=args[args.index("--seed") + 1], PBSHIM_MODE="philox")
-        p = subprocess.run([harness.REF_PHILOX] + args + ["--genome", fa, "--prefix", os.path.join(td, "out")], env=env,
+        p = subprocess.run([harness.REF_PHILOX] + args + inputs + ["--prefix", os.path.join(td, "out")], env=env,
                            capture_output=True, text=True, check=True, cwd=td)
-        entry = {"record": [length, seed], "args": case["args"], "stderr": harness.strip_report(p.stderr)}
+        entry = {"args": case["args"], "stderr": harness.strip_report(p.stderr)}
+        for k in ("record", "transcripts", "sample"):
+            if k in case:
+                entry[k] = list(case[k])
+        if "transcripts" in case or "sample" in case:
+            entry["input_sha256"] = digests
+        # wgs writes out_0001.* per record (pbsim.cpp:708, 725), trans writes out.* (pbsim.cpp:771, 788)
+        stem = "out" if "transcripts" in case else "out_0001"
         for fn in sorted(os.listdir(td)):
-            if not fn.startswith("out_0001") or fn.endswith(".ref"):
+            if not fn.startswith(stem + ".") or fn.endswith(".ref"):
                 continue
-            key = fn[len("out_0001"):].replace(".fq.gz", ".fq").replace(".maf.gz", ".maf").replace(".bam", ".sam")
+            key = fn[len(stem):].replace(".fq.gz", ".fq").replace(".maf.gz", ".maf").replace(".bam", ".sam")
             with open(os.path.join(td, fn)) as f:
                 crc, n = f.read().split()
             entry[key] = {"crc32": crc, "bytes": int(n)}

@@ -125,6 +125,193 @@ def synth_bases_torch(n, seed, device="cuda"):
     return out
 
 
+def _words(n, seed, stream):
+    """n splitmix64 words of (index, seed, stream) as Python ints: the same integer arithmetic as synth_bases_at"""
+    import numpy as np
+    with np.errstate(over="ignore"):
+        x = (np.arange(n, dtype=np.uint64) + np.uint64((seed * 0x632BE59BD9B4E019 + stream * 0xD1B54A32D192ED03) & (2**64 - 1))) * \
+            np.uint64(0x9E3779B97F4A7C15)
+        x ^= x >> np.uint64(30)
+        x *= np.uint64(0xBF58476D1CE4E5B9)
+        x ^= x >> np.uint64(27)
+        x *= np.uint64(0x94D049BB133111EB)
+        x ^= x >> np.uint64(31)
+    return x
+
+
+BUF_SIZE = 10240         # the reference's fgets buffer: a line of more than BUF_SIZE - 1 bytes is read in several pieces
+TRANS_ID_LEN_MAX = 128
+
+
+def transcript_edge_units(seed):
+    """The listed edge units synth_transcripts appends after its bulk: [(name, id, plus, minus, seq)].  `name` says what each
+    one is there for; the sequences are synth_bases_at of a stream of their own."""
+    units, at = [], [0]
+
+    def bases(n, s=None):
+        b = synth_bases_at(at[0], n, seed + 7_000_001).tobytes() if s is None else s
+        at[0] += n
+        return b
+
+    def add(name, plus, minus, seq, tid=None):
+        units.append((name, tid or "E%d_%s" % (len(units), name), plus, minus, seq))
+
+    # read lengths around the start-position ranks ceil(len / 1000) (pbsim.cpp:4516-4522).  Not 1 or 2: there the start-position
+    # draw often leaves an empty read, and the reference then indexes its accuracy histogram with (int)NaN and crashes
+    # (pbsim.cpp:4691-4695).  A 5-base transcript does so only rarely; the committed cases are ones the reference completed.
+    for n in (5, 99, 100, 101, 999, 1000, 1001, 2000, 2001):
+        add("len%d" % n, 3, 1, bases(n))
+    # LINES (id, three tabs, sequence, newline) of these many bytes: around the 10 239-byte pieces of fgets(BUF_SIZE)
+    for line in (10238, 10239, 10240, 10241, 10242, 20479, 20480):
+        tid = "E%d_line%d" % (len(units), line)
+        head = "%s\t2\t1\t" % tid
+        seq = bytearray(bases(line - len(head) - 1))
+        if line == 20479:          # a homopolymer of 17 across the end of the first piece (bytes 10 230 .. 10 246 of the line)
+            a = 10230 - len(head)
+            seq[a:a + 17] = b"G" * 17
+        add("line%d" % line, 2, 1, bytes(seq), tid)
+    # long transcripts: start-position ranks far beyond the bulk's 12 (TR_RANK_MAX 1000; TRANS_LEN_MAX 1 000 000)
+    for n, p, m in ((15_000, 1, 1), (50_000, 2, 1), (200_000, 1, 2), (500_000, 1, 1), (999_000, 2, 1)):
+        add("long%d" % n, p, m, bases(n))
+    # expression values: none, one strand only, and one unit of 5 000 reads
+    add("exp0_0", 0, 0, bases(3000))
+    add("exp4_0", 4, 0, bases(3000))
+    add("exp0_4", 0, 4, bases(3000))
+    add("exp4000_1000", 4000, 1000, bases(2500))
+    # lower case (the reference upper-cases from the SECOND base on, pbsim.cpp:4457-4459) and runs of N
+    add("lower_all", 3, 2, bases(4000).lower())
+    s = bytearray(bases(4000))
+    s[0:1] = s[0:1].lower()
+    s[1000:1100] = s[1000:1100].lower()
+    add("lower_first", 3, 2, bytes(s))
+    s = bytearray(bases(5000))
+    s[0:20] = b"N" * 20
+    s[2000:2300] = b"N" * 300
+    s[4990:5000] = b"n" * 10
+    add("n_runs", 3, 2, bytes(s))
+    # ids: exactly TRANS_ID_LEN_MAX characters, and a longer one (cut at TRANS_ID_LEN_MAX, pbsim.cpp:4432-4433)
+    add("id128", 2, 1, bases(3000), ("I128_" + "x" * 200)[:TRANS_ID_LEN_MAX])
+    add("id200", 2, 1, bases(3000), ("I200_" + "y" * 200)[:200])
+    return units
+
+
+def synth_transcripts(n, seed, bases=None):
+    """The bytes of a --transcript file (`id\\tplus\\tminus\\tseq\\n` per line): n transcripts of the benchmark's shape, then
+    transcript_edge_units(seed).  Bulk: lengths 300 .. 12 000 with a long tail (300 + 11 700 u^3, mean ~3 200), plus
+    expression 0 .. 40 (mean 20), minus 1 for one transcript in ten (mean 0.1), sequences consecutive slices of
+    synth_bases(total, seed).  Integer arithmetic only: the same bytes on every box.  `bases(n, seed)` may stand in for
+    synth_bases (harness.synth_bases_torch on a GPU box: the same bytes, faster)."""
+    import numpy as np
+    w = [x.tolist() for x in (_words(n, seed, s) for s in (1, 2, 3, 4))]
+    lens = [300 + 11700 * ((u >> 44) ** 3) // (1 << 60) for u in w[0]]
+    plus = [(a >> 40) % 21 + (b >> 40) % 21 for a, b in zip(w[1], w[2])]
+    minus = [1 if (u >> 40) % 10 == 0 else 0 for u in w[3]]
+    allseq = np.asarray((bases or synth_bases)(sum(lens), seed)).tobytes()
+    out, at = [], 0
+    for i in range(n):
+        out.append(b"T%d\t%d\t%d\t" % (i, plus[i], minus[i]) + allseq[at:at + lens[i]] + b"\n")
+        at += lens[i]
+    for name, tid, p, m, seq in transcript_edge_units(seed):
+        out.append(b"%s\t%d\t%d\t" % (tid.encode(), p, m) + seq + b"\n")
+    return b"".join(out)
+
+
+def synth_sample_fastq(n, seed):
+    """The bytes of a 4-line FASTQ for --method sample: n strings of lengths 100 .. 60 000 (100 + 59 900 u^6, mean ~8 700),
+    each with its own quality level and a +-5 jitter per character, clipped to '!' .. '~' (one string in twenty at a level
+    of 40 .. 93); then a cluster of 400 strings whose accuracy straddles the default --accuracy-min 0.75 (characters
+    Q5 or Q7, about 43 % Q5), and strings of 99, 100 and 101 characters around --length-min 100.  The bases are not read
+    by the sampling method: a fixed pattern.  Integer arithmetic only."""
+    import numpy as np
+    w = [x.tolist() for x in (_words(n, seed, s) for s in (11, 12))]
+    lens = [100 + 59900 * ((u >> 54) ** 6) // (1 << 60) for u in w[0]]
+    level = [40 + (u >> 40) % 54 if (u >> 20) % 20 == 0 else 3 + (u >> 40) % 35 for u in w[1]]
+    cl = _words(400, seed, 13).tolist()
+    cl_lens = [300 + (u >> 40) % 1700 for u in cl]
+    cl_thr = [104 + (u >> 20) % 16 for u in cl]        # byte < thr: Q5 (p 0.316), else Q7 (p 0.200): accuracy ~0.745 .. 0.756
+    edge_lens = [99, 100, 101, 99, 100, 101]
+    total = sum(lens) + sum(cl_lens) + sum(edge_lens)
+    jb = _words((total + 7) // 8, seed, 14).view(np.uint8)[:total].astype(np.int16)
+    pat = np.frombuffer(b"ACGT" * 15001, dtype=np.uint8)
+    out, at = [], 0
+
+    def rec(k, q):
+        out.append(b"@s%d\n%s\n+\n%s\n" % (k, pat[:len(q)].tobytes(), q.tobytes()))
+
+    for i in range(n):
+        j = jb[at:at + lens[i]]
+        rec(i, (np.clip(level[i] + j % 11 - 5, 0, 93) + 33).astype(np.uint8))
+        at += lens[i]
+    for i in range(len(cl)):
+        j = jb[at:at + cl_lens[i]]
+        rec(n + i, np.where(j < cl_thr[i], 38, 40).astype(np.uint8))
+        at += cl_lens[i]
+    for i, ln in enumerate(edge_lens):
+        j = jb[at:at + ln]
+        rec(n + len(cl) + i, (np.clip((25 if i < 3 else 4) + j % 11 - 5, 0, 93) + 33).astype(np.uint8))
+        at += ln
+    return b"".join(out)
+
+
+def sample_profile(fq, len_min=100, len_max=1_000_000, acc_min=0.75, acc_max=1.0):
+    """The filtered quality strings of get_sample_inf (pbsim.cpp:1216-1283) for a well-formed 4-line FASTQ, as
+    pbsim3_amd.args.read_sample_fastq, with numpy: per-character values of the reference's table qc[q].prob = pow(10, q / -10)
+    (libm pow, as the reference's), summed in file order from 0.0 by a sequential cumsum (np.sum adds pairwise)."""
+    import numpy as np
+    table = np.array([10 ** (q / -10) for q in range(94)], dtype=np.float64)
+    lines = fq.split(b"\n")
+    out = []
+    for q in lines[3::4]:
+        n = len(q)
+        if not (len_min <= n <= len_max):
+            continue
+        prob = np.cumsum(table[np.frombuffer(q, dtype=np.uint8) - 33])[-1]
+        acc = 1.0 - float(prob) / n
+        if acc_min <= acc <= acc_max:
+            out.append(q)
+    return out
+
+
+def write_fasta(path, length, seed, bases=None):
+    """one FASTA record `>synth_<length>_<seed>` of synth_bases(length, seed) (or of `bases`, the same bytes), 80 per line"""
+    import numpy as np
+    seq = np.asarray(synth_bases(length, seed) if bases is None else bases)
+    with open(path, "wb") as f:
+        f.write(b">synth_%d_%d\n" % (length, seed))
+        width = 80
+        full = length // width * width
+        step = width * (1 << 16)
+        for a in range(0, full, step):
+            rows = seq[a:min(full, a + step)].reshape(-1, width)
+            f.write(np.concatenate([rows, np.full((rows.shape[0], 1), 10, np.uint8)], axis=1).tobytes())
+        if full < length:
+            f.write(seq[full:].tobytes() + b"\n")
+
+
+def write_case_inputs(case, d, bases=None):
+    """The generated inputs of a fullsize_cases.py case, written into directory d: (the reference's command line
+    for them, {input: sha256 of the file}).  `bases(n, seed)` may stand in for synth_bases (the same bytes)."""
+    argv, digests = [], {}
+    todo = []
+    if "record" in case:
+        length, seed = case["record"]
+        todo.append(("genome", "g.fa", lambda p: write_fasta(p, length, seed, None if bases is None else bases(length, seed))))
+    if "transcripts" in case:
+        todo.append(("transcript", "tr.txt", lambda p: open(p, "wb").write(synth_transcripts(*case["transcripts"], bases=bases))))
+    if "sample" in case:
+        todo.append(("sample", "s.fq", lambda p: open(p, "wb").write(synth_sample_fastq(*case["sample"]))))
+    for opt, fn, make in todo:
+        p = os.path.join(d, fn)
+        make(p)
+        h = hashlib.sha256()
+        with open(p, "rb") as f:
+            for blk in iter(lambda: f.read(1 << 24), b""):
+                h.update(blk)
+        argv += ["--" + opt, p]
+        digests[opt] = h.hexdigest()
+    return argv, digests
+
+
 def load_fullsize():
     """tests/golden/fullsize.json: CRC-32 + length of the streams the REFERENCE wrote for the BASELINE-size cases
     (tests/golden/make_fullsize.py), plus its stderr report"""
