@@ -143,6 +143,33 @@ CASES["wgs_qshmm_rsii_ultralong_pass2"] = dict(
     args=["--strategy", "wgs", "--method", "qshmm", "--qshmm", "MODEL:QSHMM-RSII.model", "--depth", "4", "--seed", "32",
           "--pass-num", "2"] + ULTRA)
 
+# the wave walkers' state-count limits (tests/golden/make_models.py): classes whose highest state sits on each edge of the
+# chain counts -- ERRHMM two / three / four chains at reach 15|16 and 23|24, states 30 and 31, and a model one state past
+# kCoopMaxStates (32: the lane walker only); QSHMM n_chains 1 .. 7 at reach 7|8 .. 47|48 and 50.  Reads of a few thousand
+# bases (dozens of 64-column steps each), enough of them that every designed class expects 20 or more
+# (tests/test_state_limit_tables.py); the legs: the defaults, the initial-state columns of multi-pass (kInit, qz), the
+# hp_bits instance of the ERRHMM wave walker, the QSHMM repair path under many deletions, and short reads
+LONG = ["--length-mean", "3000", "--length-sd", "2000"]
+for m, seed in (("S31", 41), ("S32", 51)):
+    base = ["--strategy", "wgs", "--method", "errhmm", "--errhmm", f"MODEL:SYNTH-ERRHMM-{m}.model"]
+    big = ["--genome", "INPUT:synth_1000000_44.fa", "--depth", "3"] + LONG
+    CASES[f"wgs_errhmm_{m.lower()}_long"] = dict(args=base + big + ["--seed", str(seed)])
+    CASES[f"wgs_errhmm_{m.lower()}_long_pass3"] = dict(args=base + big + ["--seed", str(seed + 1), "--pass-num", "3"])
+    CASES[f"wgs_errhmm_{m.lower()}_long_hpbias3"] = dict(args=base + big + ["--seed", str(seed + 2), "--hp-del-bias", "3"])
+    CASES[f"wgs_errhmm_{m.lower()}_short"] = dict(
+        args=base + ["--genome", "INPUT:synth_200000_46.fa", "--depth", "2", "--seed", str(seed + 3),
+                     "--length-mean", "300", "--length-sd", "200"])
+QS50 = ["--strategy", "wgs", "--method", "qshmm", "--qshmm", "MODEL:SYNTH-QSHMM-S50.model"]
+QS50_BIG = ["--genome", "INPUT:synth_1000000_45.fa", "--depth", "6"] + LONG
+CASES["wgs_qshmm_s50_long"] = dict(args=QS50 + QS50_BIG + ["--seed", "61"])
+CASES["wgs_qshmm_s50_long_pass3"] = dict(args=QS50 + QS50_BIG + ["--seed", "62", "--pass-num", "3"])
+CASES["wgs_qshmm_s50_long_delheavy"] = dict(args=QS50 + QS50_BIG + ["--seed", "63", "--difference-ratio", "5:10:85"])
+CASES["wgs_qshmm_s50_short"] = dict(
+    args=QS50 + ["--genome", "INPUT:synth_300000_47.fa", "--depth", "2", "--seed", "64", "--length-mean", "300",
+                 "--length-sd", "200"])
+# (for the tests: these cases and their models)
+STATE_LIMIT = {c: next(a[6:] for a in CASES[c]["args"] if a.startswith("MODEL:")) for c in CASES if "_s31_" in c or "_s32_" in c or "_s50_" in c}
+
 # cases whose complete outputs are committed (gzip) in addition to the hashes
 FULL = ["wgs_errhmm-ont_quirk", "wgs_qshmm_rsii_pass3", "trans_errhmm_sequel"]
 

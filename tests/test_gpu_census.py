@@ -38,7 +38,7 @@ def product_stats(case):
     args = harness.resolve(CASES[case]["args"])
     p, a = product.params_from_args(args)
     if p.strategy == P.STRATEGY_WGS:
-        _, stats = product.run_wgs_job(args, scratch_mb=64)
+        _, stats, _ = product.run_wgs_job(args, scratch_mb=64)
         return p, stats
     with P.Context(p, 0) as ctx:
         (ctx.load_errhmm if p.method == P.METHOD_ERR else ctx.load_qshmm)(a["--errhmm" if p.method == P.METHOD_ERR else "--qshmm"])

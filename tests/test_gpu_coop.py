@@ -64,14 +64,27 @@ def test_wave_walker_matches_lane_walker(name, monkeypatch):
             assert got[0][k] == want[0][k], (name, coop, k)
 
 
+def assert_walkers(case, args, coop, waves):
+    """the wave walker took tasks exactly when it should: never with PBSIM_COOP_LEN=-1, else whenever the model and settings
+    qualify (every golden case has reads of 512 bases and more); a model that does not qualify is named with its reason in
+    product.NO_WAVE_MODELS and must leave every task to the lane walker"""
+    reason = product.wave_walker_reason(args)
+    if coop == -1 or reason is not None:
+        assert waves == 0, (case, coop, waves, reason)
+    else:
+        assert waves > 0, (case, coop, "the wave walker took no task")
+
+
 @pytest.mark.parametrize("case", WGS_ERR + ["wgs_errhmm_sequel_pass3"])
-@pytest.mark.parametrize("coop", [-1, 512])
+@pytest.mark.parametrize("coop", [0, -1, 512])
 def test_goldens_with_another_share(case, coop, monkeypatch):
     monkeypatch.setenv("PBSIM_COOP_LEN", str(coop))
-    outs, _ = product.run_wgs_job(harness.resolve(CASES[case]["args"]), scratch_mb=product.scratch_mb_for(case))
+    args = harness.resolve(CASES[case]["args"])
+    outs, _, waves = product.run_wgs_job(args, scratch_mb=product.scratch_mb_for(case))
     gold = MANIFEST[f"{case}/philox"]
     for k, v in outs.items():
         assert harness.sha(v) == gold[k]["sha256"], (case, coop, k)
+    assert_walkers(case, args, coop, waves)
 
 
 def test_split_on_several_ranks(tmp_path, monkeypatch):
@@ -146,10 +159,12 @@ def test_qshmm_goldens_on_either_walker(case, coop, monkeypatch):
     """the reference's own QSHMM goldens (all three models, ratios, multi-pass, the Q15 hp-del-bias cases, which keep their
     byte-form hp array and therefore the lane walker) with every task / no task / the long tasks on the wave walker"""
     monkeypatch.setenv("PBSIM_COOP_LEN", str(coop))
-    outs, _ = product.run_wgs_job(harness.resolve(CASES[case]["args"]), scratch_mb=product.scratch_mb_for(case))
+    args = harness.resolve(CASES[case]["args"])
+    outs, _, waves = product.run_wgs_job(args, scratch_mb=product.scratch_mb_for(case))
     gold = MANIFEST[f"{case}/philox"]
     for k, v in outs.items():
         assert harness.sha(v) == gold[k]["sha256"], (case, coop, k)
+    assert_walkers(case, args, coop, waves)
 
 
 # ---- units drawn from a counter (PBSIM_COOP_DYNAMIC; the default for batches of 16 k - 250 k tasks) ------------------------

@@ -51,9 +51,12 @@ def test_wgs_qshmm_and_multipass_match_oracle_and_golden(case, tmp_path):
 
 @pytest.mark.parametrize("case", WGS_ERR + WGS_OTHER + ["wgs_qshmm_onthq_acc95", "wgs_qshmm_onthq_pass2_hpbias2"])
 def test_job_pipeline_matches_golden(case):
-    """the same commands through pbsim_job_* (all records resident, one pipeline of rounds; a 4 MB scratch pool forces many rounds)"""
+    """the same commands through pbsim_job_* (all records resident, one pipeline of rounds; a 4 MB scratch pool forces many rounds).
+    Their batches are small: by default every task of a model the wave walkers take goes to them, and they must have run."""
     args = harness.resolve(CASES[case]["args"])
-    outs, _ = product.run_wgs_job(args, scratch_mb=product.scratch_mb_for(case))
+    outs, _, waves = product.run_wgs_job(args, scratch_mb=product.scratch_mb_for(case))
     gold = MANIFEST[f"{case}/philox"]
     for k, v in outs.items():
         assert harness.sha(v) == gold[k]["sha256"], (case, k)
+    reason = product.wave_walker_reason(args)
+    assert (waves > 0) == (reason is None), (case, waves, reason)
