@@ -8,14 +8,15 @@ pbsim_job_run: header draws, (class, length) bucketing, ERRHMM walks, the quota 
 MAF text emitted on the GPU, per-record statistics -- AND the delivery of the output: FASTQ + MAF are compressed on the GPU
 (BGZF-framed gzip members, deflate.hip) and copied into pinned host memory, where a sink receives them ("incl.
 batch D2H"; what the CLI does for .fq.gz / .maf.gz except the file writes).  `value` = bases of the job / wall time of a
-step.  Sub-fields give the same job with the text left in HBM (whole_job_hbm) and the steady-state batch pipeline on one
-record (steady_state_hbm).  The default run (N = 1, no flags beyond --steps / --warmup) also measures, outside the timed
-region: `other_configs` -- BASELINE configs[4], [2] (the four-record job), [3] and the sampling job, every one delivered like the
+step.  A plain run (no flags beyond --gpus / --steps / --warmup / --dump-outputs) does only that: it sets up, warms up, times
+the steps, writes --dump-outputs and prints its line.  --full measures everything else too, outside the timed region: the
+same job with the text left in HBM (whole_job_hbm) and the steady-state batch pipeline on one record (steady_state_hbm);
+`other_configs` -- BASELINE configs[4], [2] (the four-record job), [3] and the sampling job, every one delivered like the
 headline, as child processes; `comm_latency` -- what a collective costs through the library's RCCL communicator and through the
 torch.distributed callbacks (groups of one); `replay` -- every rank of the EIGHT-rank job alone on this GPU against virtual
-ranks, twice the measured latency injected per collective (tools/replay_ranks.py); and `setup.value_from_fresh_records` -- the
-job started on announced records that a feeder thread hands over while it runs.  It prints ONE compact line (bench_line.py,
-under 6 KB) and writes the full record to bench_detail.json.
+ranks, twice the measured latency injected per collective (tools/replay_ranks.py); `setup.value_from_fresh_records` -- the
+job started on announced records that a feeder thread hands over while it runs; and `cpu_baseline` -- the reference on the
+host's cores.  It prints ONE compact line (bench_line.py, under 6 KB) and writes the full record to bench_detail.json.
 The records are harness.synth_bases: integer arithmetic, so the reference itself can be run on the bench genome (and has been on
 record 2: tests/golden/fullsize.json).
 
@@ -233,8 +234,8 @@ def ctypes_addr(text):
 def timed_unit_job(a, torch, P, C, ctx, fn, workload, kernel, extra_cfg=None):
     """A per-unit driver (`fn`: pbsim_simulate_trans / pbsim_simulate_sample) under the headline metric: every
     step is the whole job INCLUDING the delivery of its output -- FASTQ + MAF compressed on the GPU (pbsim_set_deflate(7)) and
-    copied into pinned host memory where a sink counts them, as run_job(True) does for the wgs job.  --steps timed steps; the
-    same job with its text left in HBM beside it (median of five)."""
+    copied into pinned host memory where a sink counts them, as run_job(True) does for the wgs job.  --steps timed steps; with
+    --full, the same job with its text left in HBM beside it (median of five)."""
     if a.dump_outputs:
         import bench_dump
 
@@ -266,15 +267,6 @@ def timed_unit_job(a, torch, P, C, ctx, fn, workload, kernel, extra_cfg=None):
     ref_bases = bases - st.res_ins_num + st.res_del_num
     alg = steps * (ref_bases + 2 * bases + 2 * maf_columns)
     ach = alg / (walk_ms / 1e3) / 1e9 if walk_ms > 0 else None
-    ctx.release_pools()
-    run(False)
-    torch.cuda.synchronize()
-    hbm = []
-    for _ in range(5):
-        t1 = time.perf_counter()
-        run(False)
-        torch.cuda.synchronize()
-        hbm.append(time.perf_counter() - t1)
     out = {"metric": "simulated bases/sec", "value": bases * steps / dt, "unit": "bases/s", "n_gpus": 1, "steps": steps,
            "warmup": max(1, a.warmup), "ms_per_step": dt * 1e3 / steps, "higher_is_better": True, "scaling": "strong",
            "vs_baseline": None, "dtype": "u8", "data": "synthetic", "reads_per_sec": reads * steps / dt,
@@ -284,9 +276,19 @@ def timed_unit_job(a, torch, P, C, ctx, fn, workload, kernel, extra_cfg=None):
                         "frac": ach / HBM_PEAK_GBS if ach else None, "traffic": None,
                         "alg_bytes_per_launch": alg / max(1, launches), "avg_launch_ms": walk_ms / max(1, launches), "launches": launches,
                         "kernel_limiter": "valu-issue", "job_limiter": "pcie",
-                        "pcie_frac": host_bytes / dt / (PCIE_PEAK_GBS * 1e9)},
-           "whole_job_hbm": {"value": bases / sorted(hbm)[len(hbm) // 2], "unit": "bases/s", "runs_ms": [x * 1e3 for x in hbm],
-                             "note": "the same job, text left in HBM (no compression, no copy); median of five runs"}}
+                        "pcie_frac": host_bytes / dt / (PCIE_PEAK_GBS * 1e9)}}
+    if a.full:
+        ctx.release_pools()
+        run(False)
+        torch.cuda.synchronize()
+        hbm = []
+        for _ in range(5):
+            t1 = time.perf_counter()
+            run(False)
+            torch.cuda.synchronize()
+            hbm.append(time.perf_counter() - t1)
+        out["whole_job_hbm"] = {"value": bases / sorted(hbm)[len(hbm) // 2], "unit": "bases/s", "runs_ms": [x * 1e3 for x in hbm],
+                                "note": "the same job, text left in HBM (no compression, no copy); median of five runs"}
     import bench_line
     bench_line.emit(out, a.detail, sys.stdout)
 
@@ -581,12 +583,13 @@ def steady_state(a, torch, harness, P, local, model, genome_ptr, G, qs=False, pa
 
 def other_configs():
     """The BASELINE configurations the headline is not quoted on, under the same metric, so that every one of them is timed by
-    whoever runs `python bench.py`: configs[4] (ERRHMM-ONT-HQ depth 60, the 3 Gbp genome; one timed step), configs[2] (QSHMM-RSII
-    --pass-num 10 depth 20 as BAM records + MAF; the four-record job, one timed step of 18 s -- round 5 timed ONE record),
-    configs[3] (100 000 transcripts) and the sampling method (ten timed steps each: timed_unit_job).  Every one delivers
-    its output like the headline (compressed on the GPU, into pinned host memory).  Each is this same script as a child
-    process (started after this process has closed its context; never an exec); what is kept of its line is below.  A
-    configuration that fails is reported as {"error": ..} -- it never takes the headline's line with it."""
+    whoever runs `python bench.py --full`: configs[4] (ERRHMM-ONT-HQ depth 60, the 3 Gbp genome; one timed step), configs[2]
+    (QSHMM-RSII --pass-num 10 depth 20 as BAM records + MAF; the four-record job, one timed step of 18 s -- round 5 timed ONE
+    record), configs[3] (100 000 transcripts) and the sampling method (ten timed steps each: timed_unit_job).  Every one
+    delivers its output like the headline (compressed on the GPU, into pinned host memory).  Each is this same script as a
+    child process (started after this process has closed its context; never an exec), with --full so that the per-unit jobs
+    measure their whole_job_hbm too; what is kept of its line is below.  A configuration that fails is reported as
+    {"error": ..} -- it never takes the headline's line with it."""
     res = {}
     runs = (("configs[4] onthq60", ["--workload", "onthq60"]),
             ("configs[2] qshmm10", ["--workload", "qshmm10"]),
@@ -594,8 +597,8 @@ def other_configs():
             ("sampling method", ["--workload", "sample"]))
     for name, flags in runs:
         steps = "10" if flags[1] in ("trans", "sample") else "1"
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", steps, "--warmup", "1", "--no-extras", "--no-cpu-baseline",
-               "--detail", ""] + flags
+        cmd = [sys.executable, os.path.abspath(__file__), "--steps", steps, "--warmup", "1", "--full", "--no-extras",
+               "--no-cpu-baseline", "--detail", ""] + flags
         t0 = time.perf_counter()
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
@@ -679,19 +682,23 @@ def main():
     ap.add_argument("--workload", default="errhmm", choices=sorted(WORKLOADS) + ["trans", "sample"],
                     help="errhmm = BASELINE configs[1] (headline); onthq60 = configs[4]; qshmm10 = configs[2]; "
                          "trans = configs[3] (whole job, wall time); sample = the sampling method")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the whole_job_hbm / steady_state_hbm sub-measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: cpu_baseline, "
+                         "comm_latency, whole_job_hbm, steady_state_hbm, setup.value_from_fresh_records, replay and "
+                         "other_configs (the --no-* options below leave some of them out again)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the whole_job_hbm / steady_state_hbm sub-measurements")
     ap.add_argument("--hbm-only", action="store_true", help="experiment: leave the text in HBM in the timed runs too")
     ap.add_argument("--one-gpu", action="store_true",
                     help="plumbing check: the --gpus N ranks as N contexts on GPU 0, gloo collectives (not a scaling measurement)")
     ap.add_argument("--replay-ranks", default=None,
-                    help="N=1 only: e.g. 2,4,8 -- additionally measure the per-rank critical path of the N-rank job on this one GPU, "
+                    help="--full, N=1 only: e.g. 2,4,8 -- additionally measure the per-rank critical path of the N-rank job on this one GPU, "
                          "every rank alone against virtual ranks (tools/replay_ranks.py).  Default: 8 for the headline workload "
                          "(with the other sub-measurements; --no-extras or --replay-ranks '' turn it off)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="N=1, headline workload: skip the one timed step each of BASELINE configs[4], [2] and [3] (`other_configs`)")
+                    help="--full, N=1, headline workload: skip the one timed step each of BASELINE configs[4], [2] and [3] (`other_configs`)")
     ap.add_argument("--fresh-records", action="store_true",
-                    help="--gpus N > 1: additionally time the job from FRESH records -- every record broadcast again (C1, on a process "
+                    help="--full, --gpus N > 1: additionally time the job from FRESH records -- every record broadcast again (C1, on a process "
                          "group of its own, from a feeder thread) and handed over while the job runs (pbsim_job_expect) -- and print "
                          "setup.value_from_fresh_records.  Opt-in: two communicators driven from two threads have only run over gloo here")
     ap.add_argument("--comm", default="rccl", choices=["rccl", "torch"],
@@ -724,6 +731,10 @@ def main():
         sys.exit("bench.py: --steps must be >= 1")
     if a.dump_outputs and a.gpus != 1:
         sys.exit("bench.py: --dump-outputs is for --gpus 1 (a rank receives only its own pieces of the streams)")
+    if not a.full:
+        if a.replay_ranks or a.fresh_records:
+            sys.exit("bench.py: --replay-ranks and --fresh-records are sub-measurements of --full")
+        a.no_extras = a.no_cpu_baseline = a.no_other_configs = True     # a plain run measures the headline figure only
     if a.no_torch:
         if a.gpus != 1 or a.workload in ("trans", "sample"):
             sys.exit("bench.py: --no-torch is for --gpus 1 and the wgs workloads")
@@ -906,9 +917,9 @@ def main():
     # torch path tensor construction and Python under the GIL.
     comm_lat = None
     try:
-        if world > 1:
+        if world > 1 and a.full:
             comm_lat = {"job_comm": dict(P.comm_latency(cref, 8, 300, 20), kind=comm_kind)}
-        elif not a.no_extras:
+        elif world == 1 and not a.no_extras:
             comm_lat = {}
             nat1 = P.RcclComm.create(0, 1, local, lambda ident: ident)
             comm_lat["rccl_native"] = dict(P.comm_latency(nat1.ref, 8, 1000, 50), ranks_seen=nat1.info()["ranks_seen"])

@@ -122,7 +122,8 @@ def test_window_keeps_the_dump_under_the_limit():
     assert bench_dump.window_for(4) == bench_dump.MAX_WINDOW
 
 
-@pytest.mark.parametrize("args", [["--steps", "0"], ["--gpus", "2", "--dump-outputs", "x"]])
+@pytest.mark.parametrize("args", [["--steps", "0"], ["--gpus", "2", "--dump-outputs", "x"], ["--replay-ranks", "8"],
+                                  ["--gpus", "2", "--fresh-records"]])
 def test_bench_refuses_before_touching_a_gpu(args):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(harness.ROOT, "bench.py")] + args, capture_output=True, text=True,

@@ -1,11 +1,13 @@
 """bench.py on the GPU box as the driver runs it: the LAST stdout line must parse, stay under the size limit and carry
-`roofline` + `cpu_baseline`; and the exact command shape of the scaling run -- `bench.py --gpus 2` starting
-its ranks itself -- must give one parseable line with n_gpus == 2 (item 8; --one-gpu: the two ranks are two contexts on this
-box's one GPU over gloo, RCCL takes one rank per GPU)."""
+`roofline` (+ `cpu_baseline` with --full); a plain run of the headline job measures nothing but its
+figure; and the exact command shape of the scaling run -- `bench.py --gpus 2` starting its ranks itself -- must give one
+parseable line with n_gpus == 2 (item 8; --one-gpu: the two ranks are two contexts on this box's one GPU over gloo, RCCL takes
+one rank per GPU)."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -32,7 +34,8 @@ def run_bench(args, tmp_path):
 
 
 def test_default_shape_small_records(tmp_path):
-    line, detail, _ = run_bench(["--gpus", "1", "--steps", "1", "--warmup", "1", "--record-len", "4000000", "--records", "2"], tmp_path)
+    line, detail, _ = run_bench(["--gpus", "1", "--steps", "1", "--warmup", "1", "--record-len", "4000000", "--records", "2",
+                                 "--full"], tmp_path)
     assert line["n_gpus"] == 1 and line["steps"] == 1 and line["warmup"] == 1 and line["unit"] == "bases/s"
     assert line["value"] > 0 and line["ms_per_step"] > 0
     assert abs(line["value"] - line["config"]["bases_per_step"] / (line["ms_per_step"] / 1e3)) / line["value"] < 1e-3
@@ -51,9 +54,24 @@ def test_default_shape_small_records(tmp_path):
     assert "secondary" in detail["roofline"] and "per_rank" in detail["critical_path"]
 
 
+def test_plain_headline_run_is_lean(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: the headline job's line and nothing measured beside it, and at
+    most 30 s of the process's wall time outside its N + W runs of the job (set-up, first launches and exit included)"""
+    t0 = time.perf_counter()
+    line, detail, _ = run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1"], tmp_path)
+    wall = time.perf_counter() - t0
+    assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0
+    assert line["config"]["bases_per_step"] > 50e9 and line["roofline"]["launches"] > 0
+    for k in ("cpu_baseline", "comm_latency", "whole_job_hbm", "steady_state_hbm", "replay", "other_configs", "sub_errors"):
+        assert k not in line and detail.get(k) is None, k
+    assert detail["setup"]["value_from_fresh_records"] is None
+    outside = wall - 3 * line["ms_per_step"] / 1e3
+    assert outside < 30, "%.1f s outside the steps" % outside
+
+
 def test_scale_command_dry_run_two_ranks_one_gpu(tmp_path):
     line, detail, p = run_bench(["--gpus", "2", "--one-gpu", "--steps", "1", "--warmup", "1", "--record-len", "4000000",
-                                 "--records", "2", "--no-cpu-baseline"], tmp_path)
+                                 "--records", "2", "--full", "--no-cpu-baseline"], tmp_path)
     assert "launching 2 ranks" in p.stderr
     assert line["n_gpus"] == 2 and line["steps"] == 1 and line["value"] > 0
     assert len(line["per_rank"]["reads_delivered"]) == 2 and all(x > 0 for x in line["per_rank"]["reads_delivered"])

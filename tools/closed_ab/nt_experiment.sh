@@ -4,7 +4,7 @@
 out=gpurun_out/$1; mkdir -p $out
 for nt in 0 1 3; do
   PBSIM_EXTRA_CFLAGS="-DPBSIM_NT=$nt" python -c "import pbsim3_amd.build as b; b.build(force=True)" > $out/build_$nt.log 2>&1
-  python bench.py --no-cpu-baseline > $out/bench_$nt.json 2> $out/bench_$nt.err
+  python bench.py --full --no-cpu-baseline > $out/bench_$nt.json 2> $out/bench_$nt.err
   echo "NT=$nt $(cut -c1-120 $out/bench_$nt.json)"
   bash tools/stats_slots1.sh $1/s1_$nt > $out/slots1_$nt.log 2>&1; sed -n 1,4p $out/slots1_$nt.log
   bash tools/pmc_traffic.sh $out/traffic_$nt > $out/traffic_$nt.log 2>&1; tail -5 $out/traffic_$nt.log

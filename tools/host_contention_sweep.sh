@@ -19,7 +19,7 @@ job() { python3 bench.py --no-extras --no-cpu-baseline --steps 2 2>/dev/null | p
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%.1f ms per step, %.1f Gbases/s, pcie_frac %.3f' % (d['ms_per_step'], d['value']/1e9, d['delivery']['pcie_frac']))"; }
-ranks() { PBSIM_REPLAY_ONLY=0,7 python3 bench.py --replay-ranks 8 --c1-gbs 0 --no-extras --no-cpu-baseline --steps 1 2>/dev/null | python3 -c "
+ranks() { PBSIM_REPLAY_ONLY=0,7 python3 bench.py --full --replay-ranks 8 --c1-gbs 0 --no-extras --no-cpu-baseline --steps 1 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(', '.join('rank %d of 8: %.1f ms (delivery thread busy %.1f)' % (x['rank'], x['wall_ms'], x['breakdown_ms']['worker_busy']) for x in d['replay']['by_world']['8']['per_rank']))"; }

@@ -13,7 +13,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 R=$GRAFT_REPO_ROOT
 T="timeout 900"
-$T python3 bench.py --detail $out/bench_n1_detail.json > $out/bench_n1.json 2> $out/bench_n1.err
+$T python3 bench.py --full --detail $out/bench_n1_detail.json > $out/bench_n1.json 2> $out/bench_n1.err
 $T python3 bench.py --no-torch --no-cpu-baseline --detail $out/bench_notorch_detail.json > $out/bench_notorch.json 2> $out/bench_notorch.err
 cd /tmp && export TMPDIR=/tmp
 $T rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/prof -- python3 $R/bench.py --no-torch --no-cpu-baseline --detail $R/$out/bench_prof_detail.json > $R/$out/bench_prof.json 2> $R/$out/bench_prof.err
@@ -22,10 +22,10 @@ cd $R
 cp $(find $out/prof -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv
 cp $(find $out/prof_hbm -name "*kernel_stats.csv" | head -1) $out/kernel_stats_hbm.csv
 $T python3 bench.py --hbm-only --no-cpu-baseline --no-extras --detail "" > $out/bench_hbm_only.json 2>/dev/null
-$T python3 bench.py --workload onthq60 --no-cpu-baseline --steps 1 --detail "" > $out/bench_onthq60.json 2>/dev/null
-$T python3 bench.py --workload qshmm10 --no-cpu-baseline --steps 1 --detail "" > $out/bench_qshmm10.json 2>/dev/null
-$T python3 bench.py --workload trans --detail "" > $out/bench_trans.json 2>/dev/null
-$T python3 bench.py --workload sample --detail "" > $out/bench_sample.json 2>/dev/null
+$T python3 bench.py --full --workload onthq60 --no-cpu-baseline --steps 1 --detail "" > $out/bench_onthq60.json 2>/dev/null
+$T python3 bench.py --full --workload qshmm10 --no-cpu-baseline --steps 1 --detail "" > $out/bench_qshmm10.json 2>/dev/null
+$T python3 bench.py --full --workload trans --detail "" > $out/bench_trans.json 2>/dev/null
+$T python3 bench.py --full --workload sample --detail "" > $out/bench_sample.json 2>/dev/null
 for k in errhmm onthq qshmm10; do $T python3 tools/walk_solo.py $k 3 2>/dev/null | tail -1; done > $out/walk_solo.txt
 rm -rf $out/prof $out/prof_hbm
 for f in $out/bench_*.json; do case $f in *_detail.json) continue;; esac; grep '^{' $f | tail -1 > $f.tmp && mv $f.tmp $f; done

@@ -1,4 +1,4 @@
-"""An N-rank job's per-rank critical path, measured on ONE GPU (bench.py --replay-ranks 2,4,8).
+"""An N-rank job's per-rank critical path, measured on ONE GPU (bench.py --full --replay-ranks 2,4,8).
 
 A rank of an N-rank job exchanges only integers with the others: per round the pass-0 bases and the largest raw
 length of every rank's block (A), the cut inside every block (B; only in rounds that can touch the quota) and the byte counts

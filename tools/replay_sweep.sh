@@ -6,7 +6,7 @@ out=$1; shift
 for wl in errhmm onthq60; do
   for kv in "$@"; do
     echo "== $wl $kv" >> $out
-    env PBSIM_REPLAY_ONLY=0,3,7 $kv python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras --workload $wl --replay-ranks 8 2>> $out.err | python -c '
+    env PBSIM_REPLAY_ONLY=0,3,7 $kv python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras --workload $wl --replay-ranks 8 2>> $out.err | python -c '
 import json,sys
 d=json.loads(sys.stdin.readline())
 r=d["replay"]["by_world"]["8"]
