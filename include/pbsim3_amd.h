@@ -164,6 +164,50 @@ int pbsim_simulate_templ(pbsim_ctx *ctx, const pbsim_sink *sink); /* simulate_by
  * pbsim_unit_reads: reads of the whole set (sum of the expression values, or the number of templates). */
 int pbsim_simulate_units_range(pbsim_ctx *ctx, int64_t first_read, int64_t n_reads, const pbsim_sink *sink);
 int64_t pbsim_unit_reads(pbsim_ctx *ctx);
+
+/* ---- reads as device arrays -------------------------------------------------
+ * The same reads as the text drivers, handed over as arrays in HBM instead of FASTQ/SAM + MAF text.  A task is one read
+ * of one pass; task t = r * pass_num + h holds read r (in read order) and pass h, the order in which the text drivers write
+ * their records (pbsim.cpp:3986-4078 wgs errhmm; the MAF emit of wgs qshmm :2352-2383, trans :4736-4767 / :2984-3015,
+ * templ :5306-5337 / :3502-3533).  Per base:
+ *   seq       the bytes of the FASTQ sequence line (pass_num 1, pbsim.cpp:4014) or of the SAM SEQ field (:4017)
+ *   qual      the quality bytes of the same record minus 33 (ERRHMM: all 0, its quality line is all '!', :4007-4010)
+ *   ref_pos   0-based forward-strand coordinate of the reference base in the same MAF column, -1 where the MAF reference
+ *             line holds '-' (an inserted base); in the record (wgs) or in the transcript / template (trans, templ).
+ *             Read base i of a '+' task sits in the MAF column that holds its (i+1)-th read byte; of a '-' task in the
+ *             column that holds its (q-i)-th (the MAF lines are in reference orientation, :3981-3984)
+ * Per task:
+ *   offsets      [tasks + 1] exclusive scan of the tasks' base counts (task t's bases are [offsets[t], offsets[t+1]))
+ *   read_number  the number in the read's id, sim.res_num (:4013)
+ *   pass_index   h (the /h of a SAM id, :4016)
+ *   unit         wgs: the record_index given to pbsim_set_reference*; trans/templ: the unit's 0-based load order
+ *   strand       0 '+', 1 '-': the strand of the MAF read line (:4074)
+ *   ref_start, ref_span   start and size of the MAF reference line (:4047-4063)
+ *   n_sub, n_ins, n_del   the walk's error counters of the task (sim.res_sub_num etc. are their sums, :3986-4005) */
+typedef struct pbsim_read_arrays {
+  uint8_t *seq, *qual;   /* [bases] */
+  int32_t *ref_pos;      /* [bases]; NULL: not written */
+  int64_t *offsets;      /* [tasks + 1] */
+  int64_t *read_number;  /* [tasks] ... */
+  int32_t *pass_index, *unit;
+  uint8_t *strand;
+  int64_t *ref_start;
+  int32_t *ref_span, *n_sub, *n_ins, *n_del;
+} pbsim_read_arrays;
+/* alloc: the caller fills `out` with device pointers (on the context's device, 16-byte aligned) for exactly `tasks`
+ * tasks and `bases` bases of the next batch; on_batch: the batch's arrays are complete (the context's stream has been
+ * synchronised).  Both are called once per batch in read order; a batch without final tasks is skipped.  Return 0 from
+ * either to abort the run: pbsim_simulate_arrays then returns 0 and the context stays usable. */
+typedef struct pbsim_array_sink {
+  void *user;
+  int (*alloc)(void *user, int64_t tasks, int64_t bases, pbsim_read_arrays *out);
+  int (*on_batch)(void *user, const pbsim_batch_info *info);
+} pbsim_array_sink;
+/* Runs the context's current unit like pbsim_simulate_wgs (wgs: the record set by pbsim_set_reference*) or
+ * pbsim_simulate_trans (trans/templ: all loaded units), same reads, same statistics (pbsim_get_stats), but no text: each
+ * batch's rows go into the sink's arrays.  pbsim_set_deflate and pbsim_set_bam_output do not apply.  The sampling
+ * method is refused. */
+int pbsim_simulate_arrays(pbsim_ctx *ctx, const pbsim_array_sink *sink);
 /* Host-side readers of the reference's unit files for callers above the ABI that are not C++: parse `path` like
  * simulate_by_*_trans does its --transcript file (pbsim.cpp:4428-4485; get_transcript_inf :1075) resp. get_templ_inf its
  * --template FASTA (:1366) and hand the units over (pbsim_set_transcripts / pbsim_set_templates).

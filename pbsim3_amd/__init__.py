@@ -8,6 +8,7 @@ gfx950 device is usable, the calls raise.
 """
 import ctypes as C
 import os
+from typing import NamedTuple
 
 from . import build as _build
 
@@ -51,6 +52,51 @@ SINK_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_char), C.c_int64)
 
 class Sink(C.Structure):
     _fields_ = [("user", C.c_void_p), ("on_read_text", SINK_CB), ("on_maf_text", SINK_CB)]
+
+
+class ReadArrays(C.Structure):
+    """pbsim_read_arrays: device pointers, one per array (ref_pos may be NULL)"""
+    _fields_ = [("seq", C.c_void_p), ("qual", C.c_void_p), ("ref_pos", C.c_void_p), ("offsets", C.c_void_p),
+                ("read_number", C.c_void_p), ("pass_index", C.c_void_p), ("unit", C.c_void_p), ("strand", C.c_void_p),
+                ("ref_start", C.c_void_p), ("ref_span", C.c_void_p), ("n_sub", C.c_void_p), ("n_ins", C.c_void_p),
+                ("n_del", C.c_void_p)]
+
+
+ARRAY_ALLOC_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(ReadArrays))
+ARRAY_BATCH_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(BatchInfo))
+
+
+class ArraySink(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("alloc", ARRAY_ALLOC_CB), ("on_batch", ARRAY_BATCH_CB)]
+
+
+# (name, dtype, per task / per base) of the arrays of a ReadBatch, in pbsim_read_arrays order
+ARRAY_FIELDS = [("seq", "uint8", "base"), ("qual", "uint8", "base"), ("ref_pos", "int32", "base"),
+                ("offsets", "int64", "offset"), ("read_number", "int64", "task"), ("pass_index", "int32", "task"),
+                ("unit", "int32", "task"), ("strand", "uint8", "task"), ("ref_start", "int64", "task"),
+                ("ref_span", "int32", "task"), ("n_sub", "int32", "task"), ("n_ins", "int32", "task"),
+                ("n_del", "int32", "task")]
+
+
+class ReadBatch(NamedTuple):
+    """Reads of one batch (or of a whole run) as torch tensors on the context's device; include/pbsim3_amd.h
+    pbsim_read_arrays has the contract.  Task t = read r, pass h at t = r * pass_num + h; its bases are
+    seq[offsets[t]:offsets[t + 1]].  ref_pos is None when simulated with labels=False.  first_read: the number of the
+    batch's first read."""
+    seq: object
+    qual: object
+    ref_pos: object
+    offsets: object
+    read_number: object
+    pass_index: object
+    unit: object
+    strand: object
+    ref_start: object
+    ref_span: object
+    n_sub: object
+    n_ins: object
+    n_del: object
+    first_read: int
 
 
 OP_SUM, OP_MIN, OP_MAX = 0, 1, 2
@@ -132,6 +178,7 @@ API = [
     ("pbsim_load_template_file", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]),
     ("pbsim_simulate_wgs", C.c_int, [C.c_void_p, C.POINTER(Sink)]),
     ("pbsim_simulate_trans", C.c_int, [C.c_void_p, C.POINTER(Sink)]),
+    ("pbsim_simulate_arrays", C.c_int, [C.c_void_p, C.POINTER(ArraySink)]),
     ("pbsim_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     ("pbsim_sam_header", C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64]),
     ("pbsim_set_bam_output", C.c_int, [C.c_void_p, C.c_int]),
@@ -445,6 +492,7 @@ class Context:
     def __init__(self, params, device=0):
         self.lib = load()
         self.params = params
+        self.device = device
         self.h = self.lib.pbsim_create(C.byref(params), device)
         if not self.h:
             raise PbsimError(self.lib.pbsim_last_error().decode(errors="replace"))
@@ -499,6 +547,75 @@ class Context:
         sink = Sink(None, SINK_CB(on_read), SINK_CB(on_maf))
         _check(self.lib.pbsim_simulate_wgs(self.h, C.byref(sink) if collect else None))
         return b"".join(reads), b"".join(mafs)
+
+    def simulate_arrays(self, on_batch=None, labels=True):
+        """Simulates the current unit (wgs: the record set by set_reference*; trans/templ: all loaded units) into torch
+        tensors on this context's device instead of text.  With on_batch, calls on_batch(ReadBatch) once per batch in
+        read order (returning False aborts: PbsimError) and returns None; without, returns one ReadBatch of all batches.
+        labels=False leaves ref_pos out (None): 2 instead of 6 bytes per base."""
+        import collections
+
+        import torch
+        dev = torch.device("cuda", self.device)
+        pending, batches, error = collections.deque(), [], []
+
+        def alloc(user, tasks, bases, out):
+            try:
+                # the caching allocator may hand out memory that torch's own stream still uses: let that finish before
+                # this context's stream writes into it
+                torch.cuda.current_stream(dev).synchronize()
+                t = {}
+                for name, dtype, per in ARRAY_FIELDS:
+                    if name == "ref_pos" and not labels:
+                        t[name] = None
+                        continue
+                    n = bases if per == "base" else tasks + 1 if per == "offset" else tasks
+                    t[name] = torch.empty(n, dtype=getattr(torch, dtype), device=dev)
+                    setattr(out.contents, name, t[name].data_ptr() or None)
+                pending.append(t)
+                return 1
+            except BaseException as e:     # (an exception must not cross the C frames)
+                error.append(e)
+                return 0
+
+        def done(user, info):
+            try:
+                b = ReadBatch(first_read=info.contents.first_read, **pending.popleft())
+                if on_batch is None:
+                    batches.append(b)
+                    return 1
+                return 0 if on_batch(b) is False else 1
+            except BaseException as e:
+                error.append(e)
+                return 0
+
+        sink = ArraySink(None, ARRAY_ALLOC_CB(alloc), ARRAY_BATCH_CB(done))
+        ok = self.lib.pbsim_simulate_arrays(self.h, C.byref(sink))
+        if error:
+            raise error[0]
+        _check(ok)
+        if on_batch is not None:
+            return None
+        if not batches:
+            empty = {name: torch.zeros(1 if per == "offset" else 0, dtype=getattr(torch, dtype), device=dev)
+                     for name, dtype, per in ARRAY_FIELDS}
+            if not labels:
+                empty["ref_pos"] = None
+            return ReadBatch(first_read=1, **empty)
+        cat = {}
+        for name, _, per in ARRAY_FIELDS:
+            if name == "ref_pos" and not labels:
+                cat[name] = None
+            elif per == "offset":
+                base, parts = 0, []
+                for b in batches:
+                    parts.append(b.offsets[:-1] + base)
+                    base += int(b.offsets[-1])
+                parts.append(torch.tensor([base], dtype=torch.int64, device=dev))
+                cat[name] = torch.cat(parts)
+            else:
+                cat[name] = torch.cat([getattr(b, name) for b in batches])
+        return ReadBatch(first_read=batches[0].first_read, **cat)
 
     def sam_header(self):
         n = self.lib.pbsim_sam_header(self.h, None, 0)

@@ -287,6 +287,7 @@ struct Slot {
   int64_t b_first = 0, b_n = 0, b_slots_max = 0;
   bool b_truncated = false, b_enqueued = false, b_walked = false, b_finalized = false;
   bool b_chain = false;                // the batch is a chain of truncated reads (walk_begin(.., chain))
+  bool b_exported = false;             // the batch's arrays are being written (export_batch; deliver_arrays waits for them)
   int64_t b_trunc = -1;                // truncate_remaining of the batch (a re-walk begins it again)
   double b_factor = 2.0;               // scratch factor of the batch's layout
   int64_t b_pass0 = 0;

@@ -1169,6 +1169,13 @@ extern "C++" int pbsim::finalize_text(pbsim_ctx *c, pbsim_batch_info *info) {
   return PBSIM_SUCCEEDED;
 }
 
+extern "C++" int pbsim::emit_batch(pbsim_ctx *c, const BatchOutput &o, pbsim_batch_info *info) {
+  return o.arrays ? export_batch(c, o.arrays, info) : finalize_text(c, info);
+}
+extern "C++" int pbsim::deliver_batch(pbsim_ctx *c, const BatchOutput &o) {
+  return o.arrays ? deliver_arrays(c, o.arrays) : deliver(c, o.sink);
+}
+
 int pbsim_batch_finalize(pbsim_ctx *c, int64_t len_total_before, pbsim_batch_info *info) {
   pbsim_batch_info bi;
   if (!finalize_cut(c, len_total_before, &bi)) return PBSIM_FAILED;
@@ -1305,9 +1312,12 @@ extern "C++" int pbsim::ensure_tables(pbsim_ctx *c, bool hp11) {
 // are pipelined over the slots: batch k+1 is enqueued (assuming batch k will not
 // be cut) before batch k is finalised, so the GPU never idles on a batch's
 // longest read or on the host round trips; a batch enqueued past the cut is
-// simply dropped.
+// simply dropped.  The batches leave as text (pbsim_simulate_wgs) or as arrays (pbsim_simulate_arrays): `out`.
 int pbsim_simulate_wgs(pbsim_ctx *c, const pbsim_sink *sink) {
   if (!c) return fail("bad argument");
+  return simulate_wgs(c, BatchOutput{sink, nullptr});
+}
+extern "C++" int pbsim::simulate_wgs(pbsim_ctx *c, const BatchOutput &out) {
   NEED_DEVICE(c);
   if (c->p.strategy != PBSIM_STRATEGY_WGS) return fail("pbsim_simulate_wgs: strategy is not wgs");
   if (!c->d_seq) return fail("no reference set (pbsim_set_reference)");
@@ -1326,7 +1336,7 @@ int pbsim_simulate_wgs(pbsim_ctx *c, const pbsim_sink *sink) {
     // With a sink the text leaves the GPU batch by batch (PCIe, host writes: ~0.15 s per Gbase), which hides any tail of
     // the walks, while the first hipMalloc of a 25-GB text buffer costs 0.8 s: batches of ~2.5 Gbases there.
     double batch_bases = (double)quota * c->p.pass_num / n_slots;
-    if (sink && (sink->on_read_text || sink->on_maf_text)) batch_bases = std::min(batch_bases, kSinkBatchBases);
+    if (out.sink && (out.sink->on_read_text || out.sink->on_maf_text)) batch_bases = std::min(batch_bases, kSinkBatchBases);
     const double want = batch_bases * 1.07 * regions_of(c) * 1.3 + (64 << 20);
     const double share = std::min(48.0 * (1LL << 30), 0.15 * (double)(free_b + c->s().d_scratch.bytes * n_slots));
     const int64_t auto_b = (int64_t)std::max(256.0 * (1 << 20), std::min(want, share));
@@ -1374,8 +1384,8 @@ int pbsim_simulate_wgs(pbsim_ctx *c, const pbsim_sink *sink) {
         c->cur = 0;
         if (!pbsim_batch_walk(c, next_read, 1, quota - len_total, nullptr)) return PBSIM_FAILED;
       }
-      if (!pbsim_batch_finalize(c, len_total, &bi)) return PBSIM_FAILED;
-      if (!deliver(c, sink)) return PBSIM_FAILED;
+      if (!finalize_cut(c, len_total, &bi) || !emit_batch(c, out, &bi)) return PBSIM_FAILED;
+      if (!deliver_batch(c, out)) return PBSIM_FAILED;
       if (trace) fprintf(stderr, "[pbsim trace] t=%.1f ms tail read %lld: %.1f ms\n", t0 - t_start, (long long)next_read, now() - t0);
       next_read += bi.n_final;
       len_total = bi.len_total_after;
@@ -1437,12 +1447,12 @@ int pbsim_simulate_wgs(pbsim_ctx *c, const pbsim_sink *sink) {
       if (!pbsim_batch_walk_begin(c, next_read + bi.n_final, 1, quota - bi.len_total_after)) tail_slot = -1;
       c->cur = pd.slot;
     }
-    if (!finalize_text(c, &bi)) {
+    if (!emit_batch(c, out, &bi)) {
       drop_pending();
       return PBSIM_FAILED;
     }
     const double t2 = now();
-    if (!deliver(c, sink)) {
+    if (!deliver_batch(c, out)) {
       drop_pending();
       return PBSIM_FAILED;
     }

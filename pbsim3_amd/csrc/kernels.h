@@ -201,6 +201,37 @@ struct TextArgs {
   const uint8_t *read_minus;    // [n_reads] strand for trans (NULL for wgs)
 };
 
+// pbsim_read_arrays (include/pbsim3_amd.h): device arrays of the final tasks, task t = read r, pass h at t = r * pass_num + h
+struct ReadArrays {
+  uint8_t *seq, *qual;        // [bases]
+  int32_t *ref_pos;           // [bases] or null
+  int64_t *offsets;           // [tasks + 1]
+  int64_t *read_number;       // [tasks]
+  int32_t *pass_index, *unit;
+  uint8_t *strand;
+  int64_t *ref_start;
+  int32_t *ref_span, *n_sub, *n_ins, *n_del;
+};
+
+struct ExportArgs {
+  int64_t first_read;
+  int64_t n_reads;            // final reads of the batch
+  int64_t bases;              // sum of out_len over their tasks
+  int32_t pass_num;
+  int32_t is_qs;              // quality row present
+  uint32_t unit;              // wgs: record index
+  const int32_t *len, *off;
+  const int32_t *out_len, *maf_len, *nsub, *nins, *ndel;
+  const int32_t *task_of_slot;
+  const int32_t *wave_cap;
+  const int64_t *wave_off;
+  const uint8_t *scratch;
+  const int32_t *read_unit;   // trans/templ: [n_reads] unit of each read (NULL for wgs)
+  const uint8_t *read_minus;  // trans/templ: [n_reads] strand (NULL for wgs: the parity rule)
+  int64_t *task_off;          // [tasks + 1] launch_export_sizes: out_len, scanned in place (total behind it)
+  ReadArrays out;
+};
+
 // ---- launches (all asynchronous on `s`) ------------------------------------
 void launch_prepare_reference(uint8_t *seq, uint8_t *hp, int flag_hp11, int64_t len, int64_t *tile_first, int64_t *tile_last,
                               int64_t *carry_start, int64_t *carry_next, int keep_first_case, DeviceFlags *flags,
@@ -252,6 +283,12 @@ void launch_quota_cut(const int64_t *cum, const int32_t *rawlen, int64_t n_reads
                       int64_t quota, int force_all, DeviceFlags *flags, hipStream_t s);
 void launch_text_sizes(const TextArgs &a, DeviceFlags *flags, hipStream_t s);
 void launch_text_emit(const TextArgs &a, int64_t n_slots_max, const DeviceFlags *flags, hipStream_t s);
+// the arrays of a batch: first the sizes (task_off = exclusive scan of out_len, total -> task_off[tasks]; flags->sums[3..5] +=
+// bases, reference bases, MAF columns as launch_text_sizes; scan_tmp as launch_exclusive_scan_i64's tmp), then, into
+// a.out, the metadata and offsets (k_export_meta), the ERRHMM quality memset and the rows (k_export_rows); out.ref_pos ==
+// null: no reference coordinates
+void launch_export_sizes(const ExportArgs &a, DeviceFlags *flags, int64_t *scan_tmp, hipStream_t s);
+void launch_export(const ExportArgs &a, int64_t n_slots_max, const DeviceFlags *flags, hipStream_t s);
 
 // ---- deflate.hip: text -> BGZF-framed gzip members, one per DF_CHUNK input bytes
 #define DF_CHUNK 32768

@@ -3076,6 +3076,119 @@ __device__ __forceinline__ void write_maf_tile(char *text, long long D, int m, i
   }
 }
 
+// ---- the pieces of a row kernel that k_text_rows and k_export_rows share: the tile loader (one lane per task x quarter
+// of a 256-column window) and the squeeze of a task's window (the columns whose byte is not 0) into a destination row.
+// Lane (lt, lc) loads dword c + 16 lc of task lt (LDS banks 5 lt + c + 16 lc: all different); the loads of the NEXT
+// tile are issued before this tile is served, so their latency hides behind the four serving steps
+// (no bounds checks: columns past a row's end are never used, and the pool ends with kScratchSlack bytes of slack)
+struct RowLane {
+  const uint32_t *src;  // dword 0 of the lane's quarter of its task's row
+  size_t step;          // dword d of the lane's task: interleaved 64 dwords apart, transposed (kWaveTransposed) adjacent
+};
+__device__ __forceinline__ RowLane row_lane(const uint32_t *region, bool transposed, int cap_dw, int wv, int lt, int lc) {
+  RowLane r;
+  r.src = transposed ? region + (size_t)(wv * 16 + lt) * cap_dw + 16 * lc : region + wv * 16 + lt + (size_t)(16 * lc) * 64;
+  r.step = transposed ? 1 : 64;
+  return r;
+}
+// the lane's 16 dwords of the window that starts at dword c1 of its task's row
+__device__ __forceinline__ void tile_fetch(uint32_t pre[16], const RowLane &r, int c1) {
+#pragma unroll
+  for (int c = 0; c < 16; ++c) pre[c] = scratch_load(r.src + (size_t)(c1 + c) * r.step);
+}
+// ... parked in the wave's tile: row lt, behind the 16 carry bytes
+__device__ __forceinline__ void tile_park(uint32_t *tile, const uint32_t pre[16], int lt, int lc) {
+#pragma unroll
+  for (int c = 0; c < 16; ++c) tile[lt * kTileStride + 4 + c + 16 * lc] = pre[c];
+}
+
+// Squeeze of one task's window (`trow` = its tile row, ncol valid columns) by the 16 lanes `sub` of a group: the
+// non-zero bytes leave, in column order, for dst_base + D + *done (16-byte aligned chunks; the task's first and last
+// bytes as bytes).  `pend` (4 dwords) holds the task's squeezed bytes that do not fill a destination chunk yet, *done
+// the bytes squeezed so far.  kPhred: every kept byte leaves minus 33 (a quality row: ASCII -> phred).
+struct SqueezeStep {
+  uint32_t keep;  // bit b: column 16 sub + b of the window is kept
+  int excl;       // kept columns of the group's lower lanes
+  int total;      // kept columns of the window
+};
+template <bool kPhred>
+__device__ __forceinline__ SqueezeStep squeeze_window(char *dst_base, long long D, const uint32_t *trow, int ncol, bool act,
+                                                      bool last, int sub, int lane, uint32_t *outb, const uint32_t *s_sel,
+                                                      uint32_t *pend, int *done) {
+  // lane `sub` holds columns 16 sub .. 16 sub + 15 of the window; its output offset is the count of kept bytes in the lower
+  // lanes of its row of 16 (DPP scan).  The out row starts with the task's pending bytes, so that it is destination-chunk
+  // aligned.
+  const uint8_t *orow = reinterpret_cast<const uint8_t *>(outb);
+  const int dn = *done;
+  const int p = (int)((D + dn) & 15);  // bytes of the destination chunk in front of this window's first byte
+  uint32_t w[4];
+  uint32_t keep = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    w[k] = trow[4 + 4 * sub + k];
+    const uint32_t nz = ~eq_bytes(w[k], 0u) & 0x80808080u;          // 0x80 per non-zero byte
+    keep |= ((((nz >> 7) * 0x00204081u) >> 21) & 15u) << (4 * k);    // -> 4 bits
+  }
+  const int nv = ncol - 16 * sub;  // valid columns of this lane
+  keep &= (nv >= 16) ? 0xffffu : (nv > 0 ? (1u << nv) - 1u : 0u);
+  const int cnt = __popc(keep);
+  const int incl = row16_scan(cnt);
+  const int total = __shfl(incl, (lane & 48) | 15, 64);
+  // the out row: pending bytes in front, zeros behind; every lane ORs its kept bytes in, one dword of <= 4 at a time
+  // (compacted by a v_perm_b32, shifted to its byte offset: two ds_or_b32, the second one usually of zero)
+  reinterpret_cast<uint4 *>(outb)[1 + sub] = make_uint4(0u, 0u, 0u, 0u);
+  if (sub < 2) reinterpret_cast<uint4 *>(outb)[17 + sub] = make_uint4(0u, 0u, 0u, 0u);
+  if (sub < 4) outb[sub] = pend[sub];
+  wave_lds_sync();
+  {
+    const int o = p + incl - cnt;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint32_t nib = (keep >> (4 * k)) & 15u;
+      uint32_t v = __builtin_amdgcn_perm(0u, w[k], s_sel[nib]);
+      if (kPhred) v -= 0x21212121u & (uint32_t)((1ull << (8 * __popc(nib))) - 1u);  // kept bytes are >= 33: no borrow
+      const int off = o + __popc(keep & ((1u << (4 * k)) - 1u));
+      const unsigned long long sv = (unsigned long long)v << (8 * (off & 3));
+      atomicOr(&outb[off >> 2], (uint32_t)sv);
+      atomicOr(&outb[(off >> 2) + 1], (uint32_t)(sv >> 32));
+    }
+  }
+  wave_lds_sync();
+  const int have = p + total;              // row bytes: [0, p) belong to earlier windows (or to the text in front)
+  const int n_ch = have >> 4;
+  char *dst = dst_base + (D + dn - p);     // 16-byte aligned
+  const int foreign = (p > dn) ? p - dn : 0;  // leading bytes of chunk 0 that belong to the text in front of the row
+  if (act && sub < n_ch) {
+    const uint32_t *src = outb + 4 * sub;
+    if (sub == 0 && foreign) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        if (4 * k >= foreign) {
+          reinterpret_cast<uint32_t *>(dst)[k] = src[k];
+        } else if (4 * k + 4 > foreign) {
+          for (int b = foreign; b < 4 * k + 4; b++) dst[b] = (char)orow[b];
+        }
+      }
+    } else {
+      reinterpret_cast<uint4 *>(dst)[sub] = reinterpret_cast<const uint4 *>(outb)[sub];
+    }
+  }
+  const int rem = have & 15;
+  if (act && last) {
+    const int lo = (n_ch == 0) ? foreign : 0;  // a row that ends inside its first chunk
+    if (sub >= lo && sub < rem) dst[16 * n_ch + sub] = (char)orow[16 * n_ch + sub];
+  }
+  wave_lds_sync();
+  if (act && sub < 4) pend[sub] = outb[4 * n_ch + sub];
+  if (act && sub == 0) *done = dn + total;
+  wave_lds_sync();
+  SqueezeStep st;
+  st.keep = keep;
+  st.excl = incl - cnt;
+  st.total = total;
+  return st;
+}
+
 __global__ __launch_bounds__(256) void k_text_rows(TextArgs a, const DeviceFlags *flags) {
   __shared__ uint32_t s_tile[64 * kTileStride + 4];  // + the dwords an aligned alignbyte of the last row reads past it
   __shared__ __attribute__((aligned(16))) uint32_t s_out[16 * kOutStride];  // one squeezed row per (wave, group)
@@ -3148,28 +3261,17 @@ __global__ __launch_bounds__(256) void k_text_rows(TextArgs a, const DeviceFlags
   const int lt = lane & 15, lc = lane >> 4;  // load role: task-in-wave, which quarter of the tile's dwords
   const int g = lane >> 4, sub = lane & 15;  // serve role: task group, 16-byte chunk
   uint32_t *outb = s_out + (wv * 4 + g) * kOutStride;
-  uint8_t *orow = reinterpret_cast<uint8_t *>(outb);
 
-  // lane (lt, lc) loads dword c + 16 lc of task lt (LDS banks 5 lt + c + 16 lc: all different); the loads of the NEXT
-  // tile are issued before this tile is served, so their latency hides behind the four serving steps
-  // (no bounds checks: columns past a row's end are never used, and the pool ends with kScratchSlack bytes of slack)
   uint32_t pre[16];
-  const uint32_t *lane_src = transposed ? region + (size_t)(wv * 16 + lt) * cap_dw + 16 * lc : region + wv * 16 + lt + (size_t)(16 * lc) * 64;
-  const size_t dw_step = transposed ? 1 : 64;  // dword d of the lane's task: interleaved 64 dwords apart, transposed adjacent
-#pragma unroll
-  for (int c = 0; c < 16; ++c) pre[c] = scratch_load(lane_src + (size_t)c * dw_step);
+  const RowLane rl = row_lane(region, transposed, cap_dw, wv, lt, lc);
+  tile_fetch(pre, rl, 0);
   for (int s0 = 0, t = 0; s0 < mmax; s0 += 256, ++t) {
     // carry: the previous tile's last 16 bytes move in front (lane = task row x dword)
     if (t > 0) tile[lt * kTileStride + lc] = tile[lt * kTileStride + 64 + lc];
     wave_lds_sync();
-#pragma unroll
-    for (int c = 0; c < 16; ++c) tile[lt * kTileStride + 4 + c + 16 * lc] = pre[c];
+    tile_park(tile, pre, lt, lc);
     wave_lds_sync();
-    if (s0 + 256 < mmax) {
-      const int c1 = (s0 + 256) >> 2;
-#pragma unroll
-      for (int c = 0; c < 16; ++c) pre[c] = scratch_load(lane_src + (size_t)(c1 + c) * dw_step);
-    }
+    if (s0 + 256 < mmax) tile_fetch(pre, rl, (s0 + 256) >> 2);
 #pragma unroll 1
     for (int it = 0; it < 4; ++it) {
       const int i = it * 4 + g, j = wv * 16 + i;
@@ -3182,73 +3284,9 @@ __global__ __launch_bounds__(256) void k_text_rows(TextArgs a, const DeviceFlags
         continue;
       }
       if (pass == 0 && act) write_maf_tile(a.maf_text, s_dmaf[j], m, t, trow, minus, true, sub);
-      // ---- squeeze the columns that carry a read base (non-zero byte): lane `sub` holds columns 16 sub .. 16 sub + 15
-      // of the window; its output offset is the count of kept bytes in the lower lanes of its row of 16 (DPP scan).
-      // The out row starts with the task's pending bytes, so that it is destination-chunk aligned.
+      // the read bases (pass 0) / the qualities (pass 2): the columns whose byte is not 0
       const int ncol = act ? ((m - s0 < 256) ? m - s0 : 256) : 0;
-      const int dn = s_done[j];
-      const long long D = s_dsq[j];
-      const int p = (int)((D + dn) & 15);  // bytes of the destination chunk in front of this window's first byte
-      uint32_t w[4];
-      uint32_t keep = 0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        w[k] = trow[4 + 4 * sub + k];
-        const uint32_t nz = ~eq_bytes(w[k], 0u) & 0x80808080u;          // 0x80 per non-zero byte
-        keep |= ((((nz >> 7) * 0x00204081u) >> 21) & 15u) << (4 * k);    // -> 4 bits
-      }
-      const int nv = ncol - 16 * sub;  // valid columns of this lane
-      keep &= (nv >= 16) ? 0xffffu : (nv > 0 ? (1u << nv) - 1u : 0u);
-      const int cnt = __popc(keep);
-      const int incl = row16_scan(cnt);
-      const int total = __shfl(incl, (lane & 48) | 15, 64);
-      // the out row: pending bytes in front, zeros behind; every lane ORs its kept bytes in, one dword of <= 4 at a time
-      // (compacted by a v_perm_b32, shifted to its byte offset: two ds_or_b32, the second one usually of zero)
-      reinterpret_cast<uint4 *>(outb)[1 + sub] = make_uint4(0u, 0u, 0u, 0u);
-      if (sub < 2) reinterpret_cast<uint4 *>(outb)[17 + sub] = make_uint4(0u, 0u, 0u, 0u);
-      if (sub < 4) outb[sub] = s_pend[j * 4 + sub];
-      wave_lds_sync();
-      {
-        const int o = p + incl - cnt;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const uint32_t v = __builtin_amdgcn_perm(0u, w[k], s_sel[(keep >> (4 * k)) & 15u]);
-          const int off = o + __popc(keep & ((1u << (4 * k)) - 1u));
-          const unsigned long long sv = (unsigned long long)v << (8 * (off & 3));
-          atomicOr(&outb[off >> 2], (uint32_t)sv);
-          atomicOr(&outb[(off >> 2) + 1], (uint32_t)(sv >> 32));
-        }
-      }
-      wave_lds_sync();
-      const int have = p + total;              // row bytes: [0, p) belong to earlier windows (or to the text in front)
-      const bool last = s0 + 256 >= m;
-      const int n_ch = have >> 4;
-      char *dst = a.read_text + (D + dn - p);  // 16-byte aligned
-      const int foreign = (p > dn) ? p - dn : 0;  // leading bytes of chunk 0 that belong to the text in front of the row
-      if (act && sub < n_ch) {
-        const uint32_t *src = outb + 4 * sub;
-        if (sub == 0 && foreign) {
-#pragma unroll
-          for (int k = 0; k < 4; k++) {
-            if (4 * k >= foreign) {
-              reinterpret_cast<uint32_t *>(dst)[k] = src[k];
-            } else if (4 * k + 4 > foreign) {
-              for (int b = foreign; b < 4 * k + 4; b++) dst[b] = (char)orow[b];
-            }
-          }
-        } else {
-          reinterpret_cast<uint4 *>(dst)[sub] = reinterpret_cast<const uint4 *>(outb)[sub];
-        }
-      }
-      const int rem = have & 15;
-      if (act && last) {
-        const int lo = (n_ch == 0) ? foreign : 0;  // a row that ends inside its first chunk
-        if (sub >= lo && sub < rem) dst[16 * n_ch + sub] = (char)orow[16 * n_ch + sub];
-      }
-      wave_lds_sync();
-      if (act && sub < 4) s_pend[j * 4 + sub] = outb[4 * n_ch + sub];
-      if (act && sub == 0) s_done[j] = dn + total;
-      wave_lds_sync();
+      squeeze_window<false>(a.read_text, s_dsq[j], trow, ncol, act, s0 + 256 >= m, sub, lane, outb, s_sel, s_pend + j * 4, s_done + j);
     }
   }
 }
@@ -3378,6 +3416,214 @@ __global__ __launch_bounds__(256) void k_bam_finish(TextArgs a) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   fill_run(reinterpret_cast<char *>(pw), q, 9, 9, lane);  // every lane has read its bases: the pw array takes its values
+}
+
+// ---------------------------------------------------------------------------
+// Arrays (pbsim_simulate_arrays): the final tasks' rows as device arrays instead of text.  Task t = read r, pass h
+// (t = r * pass_num + h, the order of the text, pbsim.cpp:3986-4078).
+// ---------------------------------------------------------------------------
+// one thread per task: task_off[t] = out_len[t] (scanned in place behind it) and the sums k_text_sizes keeps
+__global__ __launch_bounds__(256) void k_export_sizes(ExportArgs a, DeviceFlags *flags) {
+  short_kernel_priority();
+  __shared__ unsigned long long s_sum[3];
+  if (threadIdx.x < 3) s_sum[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t < a.n_reads * a.pass_num) {
+    const int64_t r = t / a.pass_num;
+    const int q = a.out_len[t];
+    a.task_off[t] = q;
+    atomicAdd(&s_sum[0], (unsigned long long)q);
+    atomicAdd(&s_sum[1], (unsigned long long)a.len[r]);
+    atomicAdd(&s_sum[2], (unsigned long long)a.maf_len[t]);
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) atomicAdd((unsigned long long *)&flags->sums[3 + threadIdx.x], s_sum[threadIdx.x]);
+}
+
+// one thread per task: the metadata and the offsets
+__global__ __launch_bounds__(256) void k_export_meta(ExportArgs a) {
+  short_kernel_priority();
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= a.n_reads * a.pass_num) return;
+  const int64_t r = t / a.pass_num;
+  const int h = (int)(t - r * a.pass_num);
+  const int64_t readnum = a.first_read + r;
+  a.out.offsets[t] = a.task_off[t];
+  if (t == 0) a.out.offsets[a.n_reads * a.pass_num] = a.task_off[a.n_reads * a.pass_num];
+  a.out.read_number[t] = readnum;
+  a.out.pass_index[t] = h;
+  a.out.unit[t] = a.read_unit ? a.read_unit[r] : (int32_t)a.unit;
+  a.out.strand[t] = (uint8_t)(a.read_minus ? (a.read_minus[r] != 0) : ((readnum & 1) == 0));  // MAF read line, :4066
+  a.out.ref_start[t] = a.off[r];                                                                // MAF reference line, :4046-4052
+  a.out.ref_span[t] = a.len[r];
+  a.out.n_sub[t] = a.nsub[t];
+  a.out.n_ins[t] = a.nins[t];
+  a.out.n_del[t] = a.ndel[t];
+}
+
+// One workgroup per (scratch wave, part), the walk of k_text_rows: the same tile loader, the same squeeze.
+//   part 0  read row -> seq; with ref_pos, the reference row of the same tasks is loaded beside it, and every kept column
+//           takes its reference coordinate: the count r of the task's columns so far whose reference byte is not '-' (a
+//           wave prefix scan of 16-column masks, carried from window to window), start + r on '+', start + span - 1 - r
+//           on '-' (the rows are in read orientation, the MAF lines in reference orientation), -1 under a '-'
+//   part 1  quality row (QSHMM) -> qual, minus 33
+// ref_pos leaves through an LDS row per (wave, group) as aligned 16-byte stores, its first and last <= 3 values as dwords.
+// kLabels = false (ref_pos not asked for) is an instance of its own: without the reference row's registers and LDS it keeps
+// twice as many workgroups per CU.
+constexpr int kPosStride = 260;  // int32 per LDS position row: <= 3 in front of the window's first value + 256 values + 1
+
+template <bool kLabels>
+__global__ __launch_bounds__(256) void k_export_rows(ExportArgs a, const DeviceFlags *flags) {
+  __shared__ uint32_t s_tile[64 * kTileStride + 4];
+  __shared__ __attribute__((aligned(16))) uint32_t s_out[16 * kOutStride];
+  __shared__ __attribute__((aligned(16))) int32_t s_pos[16 * kPosStride];
+  __shared__ uint32_t s_rmask[64 * 8];  // per task: non-'-' reference columns of the window, 64 columns per loader lane
+  __shared__ uint32_t s_sel[16];
+  __shared__ uint32_t s_pend[64 * 4];
+  __shared__ int s_m[64], s_task[64], s_done[64], s_rdone[64], s_sign[64];
+  __shared__ long long s_dst[64], s_rbase[64];
+  const int64_t wave = blockIdx.x;
+  const int part = blockIdx.y;
+  short_kernel_priority();
+  if (wave * 64 >= flags->total_slots) return;
+  const bool labels = kLabels && part == 0;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (tid < 64) {
+    const int task = a.task_of_slot[wave * 64 + tid];
+    int m = 0, tk = -1, sign = 1;
+    long long dst = 0, rbase = 0;
+    if (task >= 0) {
+      const int64_t r = task / a.pass_num;
+      if (r < a.n_reads) {
+        const int64_t readnum = a.first_read + r;
+        const bool minus = a.read_minus ? (a.read_minus[r] != 0) : ((readnum & 1) == 0);
+        m = a.maf_len[task];
+        tk = task;
+        dst = a.task_off[task];
+        rbase = minus ? (long long)a.off[r] + a.len[r] - 1 : (long long)a.off[r];
+        sign = minus ? -1 : 1;
+      }
+    }
+    s_m[tid] = m;
+    s_task[tid] = tk;
+    s_done[tid] = 0;
+    s_rdone[tid] = 0;
+    s_sign[tid] = sign;
+    s_dst[tid] = dst;
+    s_rbase[tid] = rbase;
+  }
+  s_pend[tid] = 0;
+  if (tid < 16) {
+    uint32_t sel = 0x0c0c0c0cu, n = 0;  // 0x0c selects a zero byte
+    for (uint32_t b = 0; b < 4; b++)
+      if ((tid >> b) & 1) {
+        sel = (sel & ~(0xffu << (8 * n))) | (b << (8 * n));
+        n++;
+      }
+    s_sel[tid] = sel;
+  }
+  __syncthreads();
+  int mmax = 0;
+  {
+    const int j = wv * 16 + (lane & 15);
+    int v = (s_task[j] >= 0) ? s_m[j] : 0;
+#pragma unroll
+    for (int d = 8; d > 0; d >>= 1) {
+      const int t = __shfl_xor(v, d, 64);
+      v = (t > v) ? t : v;
+    }
+    mmax = __shfl(v, 0, 64);
+  }
+  if (mmax == 0) return;
+  const int cap_raw = __builtin_amdgcn_readfirstlane(a.wave_cap[wave]);
+  const int cap_dw = cap_raw & ~kWaveTransposed;
+  const bool transposed = (cap_raw & kWaveTransposed) != 0;
+  const uint8_t *wave_rows = a.scratch + a.wave_off[wave];
+  const int row = part == 0 ? 0 : 2;
+  const uint32_t *region = reinterpret_cast<const uint32_t *>(wave_rows + (size_t)row * cap_dw * 256);
+  const uint32_t *ref_region = reinterpret_cast<const uint32_t *>(wave_rows + (size_t)cap_dw * 256);
+  uint32_t *tile = s_tile + wv * 16 * kTileStride;
+  const int lt = lane & 15, lc = lane >> 4;
+  const int g = lane >> 4, sub = lane & 15;
+  uint32_t *outb = s_out + (wv * 4 + g) * kOutStride;
+  int32_t *posb = s_pos + (wv * 4 + g) * kPosStride;
+  char *dst_base = reinterpret_cast<char *>(part == 0 ? a.out.seq : a.out.qual);
+
+  uint32_t pre[16], pre_ref[16];
+  const RowLane rl = row_lane(region, transposed, cap_dw, wv, lt, lc);
+  const RowLane rr = row_lane(ref_region, transposed, cap_dw, wv, lt, lc);
+  tile_fetch(pre, rl, 0);
+  if (labels) tile_fetch(pre_ref, rr, 0);
+  for (int s0 = 0; s0 < mmax; s0 += 256) {
+    wave_lds_sync();
+    tile_park(tile, pre, lt, lc);
+    if (labels) {  // the loader lane's 64 reference columns -> 64 bits, 1 = not '-'
+      uint32_t mk[2] = {0u, 0u};
+#pragma unroll
+      for (int c = 0; c < 16; ++c) {
+        const uint32_t nd = ~eq_bytes(pre_ref[c], 0x2Du) & 0x80808080u;
+        mk[c >> 3] |= ((((nd >> 7) * 0x00204081u) >> 21) & 15u) << (4 * (c & 7));
+      }
+      s_rmask[(wv * 16 + lt) * 8 + 2 * lc] = mk[0];
+      s_rmask[(wv * 16 + lt) * 8 + 2 * lc + 1] = mk[1];
+    }
+    wave_lds_sync();
+    if (s0 + 256 < mmax) {
+      tile_fetch(pre, rl, (s0 + 256) >> 2);
+      if (labels) tile_fetch(pre_ref, rr, (s0 + 256) >> 2);
+    }
+#pragma unroll 1
+    for (int it = 0; it < 4; ++it) {
+      const int i = it * 4 + g, j = wv * 16 + i;
+      const int m = s_m[j];
+      const bool act = s_task[j] >= 0 && s0 < m;
+      const int ncol = act ? ((m - s0 < 256) ? m - s0 : 256) : 0;
+      const long long D = s_dst[j];
+      const int dn = s_done[j];
+      const SqueezeStep st = (part == 0)
+          ? squeeze_window<false>(dst_base, D, tile + i * kTileStride, ncol, act, s0 + 256 >= m, sub, lane, outb, s_sel,
+                                  s_pend + j * 4, s_done + j)
+          : squeeze_window<true>(dst_base, D, tile + i * kTileStride, ncol, act, s0 + 256 >= m, sub, lane, outb, s_sel,
+                                 s_pend + j * 4, s_done + j);
+      if (!labels) continue;
+      // ---- reference coordinates of the kept columns
+      const int nv = ncol - 16 * sub;
+      const uint32_t valid = (nv >= 16) ? 0xffffu : (nv > 0 ? (1u << nv) - 1u : 0u);
+      const uint32_t rm = (s_rmask[j * 8 + (sub >> 1)] >> (16 * (sub & 1))) & valid;
+      const int rc = __popc(rm);
+      const int rincl = row16_scan(rc);
+      const int rtot = __shfl(rincl, (lane & 48) | 15, 64);
+      const int rdn = s_rdone[j];
+      const long long P0 = D + dn;             // element index of the window's first value in ref_pos
+      const int p4 = (int)(P0 & 3);            // values of its 16-byte chunk in front of it
+      const long long rb = s_rbase[j];
+      const int sign = s_sign[j];
+      const int rlo = rdn + rincl - rc;        // reference bases of the task in front of this lane's columns
+      for (uint32_t k = st.keep; k; k &= k - 1) {
+        const int b = __builtin_ctz(k);
+        const uint32_t below = (1u << b) - 1u;
+        const int idx = st.excl + __popc(st.keep & below);
+        posb[p4 + idx] = ((rm >> b) & 1u) ? (int32_t)(rb + (long long)sign * (rlo + __popc(rm & below))) : -1;
+      }
+      wave_lds_sync();
+      if (act) {
+        int32_t *gdst = a.out.ref_pos + (P0 - p4);  // 16-byte aligned
+        const int have = p4 + st.total;
+        for (int c = sub; 4 * c < have; c += 16) {
+          if (4 * c >= p4 && 4 * c + 4 <= have) {
+            reinterpret_cast<int4 *>(gdst)[c] = reinterpret_cast<const int4 *>(posb)[c];
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+              if (4 * c + e >= p4 && 4 * c + e < have) gdst[4 * c + e] = posb[4 * c + e];
+          }
+        }
+      }
+      wave_lds_sync();
+      if (act && sub == 0) s_rdone[j] = rdn + rtot;
+    }
+  }
 }
 
 }  // namespace
@@ -3561,6 +3807,25 @@ void launch_text_emit(const TextArgs &a, int64_t n_slots_max, const DeviceFlags 
   if (!a.is_qs || a.pass_num > 1) hipLaunchKernelGGL(k_text_fill, dim3(blocks_for(n_tasks, 4)), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_text_rows, dim3((unsigned)(n_slots_max / 64), a.is_qs ? 3 : 2), dim3(256), 0, s, a, flags);
   if (a.bam) hipLaunchKernelGGL(k_bam_finish, dim3(blocks_for(n_tasks, 4)), dim3(256), 0, s, a);
+}
+
+void launch_export_sizes(const ExportArgs &a, DeviceFlags *flags, int64_t *scan_tmp, hipStream_t s) {
+  const int64_t n_tasks = a.n_reads * a.pass_num;
+  if (n_tasks <= 0) return;
+  hipLaunchKernelGGL(k_export_sizes, dim3(blocks_for(n_tasks, 256)), dim3(256), 0, s, a, flags);
+  launch_exclusive_scan_i64(a.task_off, a.task_off, n_tasks, scan_tmp, a.task_off + n_tasks, s);
+}
+
+void launch_export(const ExportArgs &a, int64_t n_slots_max, const DeviceFlags *flags, hipStream_t s) {
+  const int64_t n_tasks = a.n_reads * a.pass_num;
+  if (n_tasks <= 0) return;
+  hipLaunchKernelGGL(k_export_meta, dim3(blocks_for(n_tasks, 256)), dim3(256), 0, s, a);
+  if (!a.is_qs && a.bases > 0) (void)hipMemsetAsync(a.out.qual, 0, (size_t)a.bases, s);  // ERRHMM: a line of '!' (pbsim.cpp:4007-4010)
+  const dim3 grid((unsigned)(n_slots_max / 64), a.is_qs ? 2 : 1);
+  if (a.out.ref_pos)
+    hipLaunchKernelGGL(k_export_rows<true>, grid, dim3(256), 0, s, a, flags);
+  else
+    hipLaunchKernelGGL(k_export_rows<false>, grid, dim3(256), 0, s, a, flags);
 }
 
 }  // namespace pbsim

@@ -200,6 +200,12 @@ int pbsim_load_template_file(pbsim_ctx *c, const char *path, int64_t stats[2]) {
 
 int pbsim_simulate_units_range(pbsim_ctx *c, int64_t first_read, int64_t n_reads, const pbsim_sink *sink) {
   if (!c) return fail("bad argument");
+  return simulate_units_range(c, first_read, n_reads, BatchOutput{sink, nullptr});
+}
+
+// The batches leave as text (pbsim_simulate_units_range) or as arrays (pbsim_simulate_arrays): `out`.
+extern "C++" int pbsim::simulate_units_range(pbsim_ctx *c, int64_t first_read, int64_t n_reads, const BatchOutput &out) {
+  const pbsim_sink *sink = out.sink;
   NEED_DEVICE(c);
   if (c->p.strategy == PBSIM_STRATEGY_WGS) return fail("pbsim_simulate_trans: strategy is wgs");
   if (!c->d_seq || c->n_units < 1) return fail("no transcripts/templates set");
@@ -265,7 +271,7 @@ int pbsim_simulate_units_range(pbsim_ctx *c, int64_t first_read, int64_t n_reads
     if (!have_prev) return PBSIM_SUCCEEDED;
     have_prev = false;
     c->cur = prev_slot;
-    return deliver(c, sink);
+    return deliver_batch(c, out);
   };
   auto give_up = [&]() {
     if (acct.valid()) (void)acct.get();
@@ -315,7 +321,7 @@ int pbsim_simulate_units_range(pbsim_ctx *c, int64_t first_read, int64_t n_reads
       continue;
     }
     pbsim_batch_info bi;
-    if (!pbsim_batch_finalize(c, 0, &bi)) {
+    if (!finalize_cut(c, 0, &bi) || !emit_batch(c, out, &bi)) {
       give_up();
       return PBSIM_FAILED;
     }
