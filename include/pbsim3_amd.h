@@ -247,6 +247,15 @@ int64_t pbsim_deflate_bound(int64_t text_bytes);
 int pbsim_batch_fetch_deflated(pbsim_ctx *ctx, char *read_gz, int64_t read_cap, char *maf_gz, int64_t maf_cap,
                                int64_t *read_gz_bytes, int64_t *maf_gz_bytes);
 int pbsim_deflate_buffer(pbsim_ctx *ctx, const void *src, int64_t n, void *dst, int64_t cap, int64_t *out_bytes);
+/* Decompression on the GPU, for BGZF input (SAMv1 4.1: gzip members of at most 64 KiB of output, each with a 'BC' extra
+ * field giving its size -- what bgzip writes, and what pbsim_deflate_buffer and the CLI's .fq.gz / .maf.gz / .bam are).
+ * pbsim_inflate_bound needs no context and no device: the inflated size of the BGZF buffer src[0..n) from its member
+ * headers and trailers, or -1 when the buffer is not BGZF (other gzip, a missing 'BC' field, an ISIZE over 65536, a member
+ * that runs past the end).  pbsim_inflate_buffer inflates every member at once into dst (cap bytes at least the bound) and
+ * checks each member's CRC-32 and ISIZE; other gzip, a corrupt member ("gzip member at byte offset N: <reason>") and a
+ * tables-only context give PBSIM_FAILED, and the context stays usable. */
+int64_t pbsim_inflate_bound(const void *src, int64_t n);
+int pbsim_inflate_buffer(pbsim_ctx *ctx, const void *src, int64_t n, void *dst, int64_t cap, int64_t *out_bytes);
 
 /* ---- batch primitives (used by the drivers above, bench.py, multi-GPU) ------
  * pbsim_batch_walk     header draw + bucketing + HMM walk of reads

@@ -191,6 +191,8 @@ API = [
     ("pbsim_batch_fetch_deflated", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("pbsim_deflate_buffer", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("pbsim_inflate_bound", C.c_int64, [C.c_void_p, C.c_int64]),
+    ("pbsim_inflate_buffer", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_batch_walk", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_slot_count", C.c_int, []),
     ("pbsim_select_slot", C.c_int, [C.c_void_p, C.c_int]),
@@ -262,6 +264,11 @@ def load(build_if_missing=True):
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def inflate_bound(data: bytes) -> int:
+    """Inflated size of BGZF `data` from its member headers (no device needed), or -1 when it is not BGZF."""
+    return load().pbsim_inflate_bound(data, len(data))
 
 
 class PbsimError(RuntimeError):
@@ -660,6 +667,16 @@ class Context:
         n = C.c_int64(0)
         src = C.create_string_buffer(data, len(data)) if data else None
         _check(self.lib.pbsim_deflate_buffer(self.h, src, len(data), dst, cap, C.byref(n)))
+        return dst.raw[:n.value]
+
+    def inflate_buffer(self, data: bytes) -> bytes:
+        """The bytes of BGZF `data` (gzip members with the 'BC' field), inflated by the GPU kernels."""
+        cap = inflate_bound(data)
+        if cap < 0:
+            _check(self.lib.pbsim_inflate_buffer(self.h, data, len(data), None, 0, C.byref(C.c_int64(0))))
+        dst = C.create_string_buffer(max(cap, 1))
+        n = C.c_int64(0)
+        _check(self.lib.pbsim_inflate_buffer(self.h, data, len(data), dst, cap, C.byref(n)))
         return dst.raw[:n.value]
 
     def set_transcripts(self, ids, plus, minus, seqs):

@@ -19,6 +19,7 @@
 #include <sched.h>
 #include <sys/mman.h>
 #include <sys/resource.h>
+#include <sys/stat.h>
 #include <sys/syscall.h>
 #include <sys/time.h>
 #include <time.h>
@@ -36,6 +37,7 @@
 
 #include "../../include/pbsim3_amd.h"
 #include "gzout.h"
+#include "input_file.h"
 #include "knobs.h"
 #include "unit_io.h"
 
@@ -123,6 +125,18 @@ void open_sink(const Cli &c, Out *o, const std::string &plain_name, const std::s
 }
 
 bool native_bam(const Cli &c) { return c.p.pass_num > 1 && !c.no_gzip && !c.use_samtools; }
+
+// a regular file that starts with the gzip magic (what input_file.h inflates)
+bool is_gzip_file(const char *file) {
+  struct stat sb;
+  if (stat(file, &sb) != 0 || !S_ISREG(sb.st_mode)) return false;  // (a FIFO is never opened here)
+  const int fd = open(file, O_RDONLY);
+  if (fd < 0) return false;
+  unsigned char m[2];
+  const bool gz = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && pread(fd, m, 2, 0) == 2 && m[0] == 0x1f && m[1] == 0x8b;
+  close(fd);
+  return gz;
+}
 
 // what main() writes when it opens the samtools pipe (pbsim.cpp:721-722), as SAM text or as the BAM header
 // (`record`: genome.num for wgs -- the PU tag carries it; 0 for trans / templ)
@@ -223,7 +237,9 @@ void print_help() {
           "  --method errhmm  --errhmm MODEL   |   --method qshmm --qshmm MODEL --difference-ratio (6:55:39)\n"
           "  --length-mean (9000.0) --length-sd (7000.0) --accuracy-mean (0.85) --pass-num (1) --hp-del-bias (1)\n"
           "  --device N (0)   --devices a,b,.. (one rank per GPU)   --no-gzip (plain .fq/.maf/.sam instead of gzip/samtools pipes)\n"
-          "  --gzip gpu|host (gpu)   --gzip-threads N (host)   --samtools (pipe SAM into samtools view -b)\n\n");
+          "  --gzip gpu|host (gpu)   --gzip-threads N (host)   --samtools (pipe SAM into samtools view -b)\n"
+          "  --genome, --transcript, --template and --sample may be gzip-compressed (recognised by content): BGZF is\n"
+          "  inflated on the GPU, other gzip by zlib on the host; the whole inflated file is held in host memory\n\n");
 }
 
 void check(int ok) {
@@ -808,6 +824,14 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
   }
   if (rank0) print_sim_param(c);
 
+  // A gzip --sample is inflated (BGZF: on the GPU) while the profile is parsed, before the context would otherwise exist:
+  // the context comes first then.  A plain sample keeps the reference's order and output.
+  pbsim_ctx *ctx = nullptr;
+  if (sampling && !c.sam_reuse && is_gzip_file(c.sample.c_str())) {
+    ctx = pbsim_create(&c.p, c.device);
+    if (!ctx) check(0);
+    pbsim::set_input_context(ctx);
+  }
   pbsim::SampleProfile prof;
   if (sampling) {  // pbsim.cpp:580-617: read (or re-read) the profile, print its statistics
     std::string e;
@@ -843,8 +867,9 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
   }
 
   phase("parameters printed, sample profile parsed");
-  pbsim_ctx *ctx = pbsim_create(&c.p, c.device);
+  if (!ctx) ctx = pbsim_create(&c.p, c.device);
   if (!ctx) check(0);
+  pbsim::set_input_context(ctx);  // gzip inputs of this rank: inflated on its own device
   phase("context created (HIP initialised)");
   if (sampling) {
     std::vector<const uint8_t *> qp;
@@ -989,7 +1014,16 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
       if (!(getenv("PBSIM_CLI_LEAVE_CONTEXT") && *getenv("PBSIM_CLI_LEAVE_CONTEXT") == '1' && world == 1)) check(pbsim_job_begin(ctx, 1));
       else fm.map = nullptr;  // (3 GB of mapped file: unmapped with the process)
     } else {
-    if (rank0 && !pbsim::split_genome(c.genome.c_str(), c.prefix.c_str(), &gi, &err)) die(": %s", err.c_str());
+    if (!fm.inflate_error.empty()) {  // a gzip genome that does not inflate: its message, without a second attempt
+      if (rank0) {
+        fprintf(stderr, ":::: Reference stats ::::\n\n");
+        fprintf(stderr, "file name : %s\n", c.genome.c_str());
+        fprintf(stderr, "\n");
+      }
+      die(": %s", fm.inflate_error.c_str());
+    }
+    if (rank0 && !pbsim::split_genome(c.genome.c_str(), c.prefix.c_str(), &gi, &err, fm.inflated ? fm.map : nullptr, fm.size))
+      die(": %s", err.c_str());
     phase("genome split into .ref files");
     if (world > 1) {
       int64_t nrec = rank0 ? gi.num_seq : 0;
@@ -1239,6 +1273,7 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
   // handing 150 GB of HBM pools and the pinned staging back piece by piece takes 0.8 s that the process exit does at once.
   // A caller that lives on (pbsim3_amd.cli_main, a rank thread of --devices) gets its memory back here.
   const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
+  pbsim::set_input_context(nullptr);
   if (!(leave && *leave == '1' && world == 1)) pbsim_destroy(ctx);
   phase("context destroyed");
   barrier(comm);

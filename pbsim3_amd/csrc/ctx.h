@@ -449,6 +449,7 @@ int deflate_pieces(pbsim_ctx *c, DfLane &lane, const uint8_t *d_text, int64_t n,
                    const std::function<int(const char *, int64_t)> &consume,
                    const std::function<char *(int64_t)> *place = nullptr);
 int ensure_deflate_ready(pbsim_ctx *c);  // CRC / shift tables of deflate.hip resident (call before using lanes from threads)
+int ensure_crc_tables(pbsim_ctx *c);  // deflate.hip's slice-by-4 CRC-32 and pow128 tables resident (d_df_tables; inflate uses them too)
 // upper-case + homopolymer pass of a record (k_hp_*) enqueued on `stream`; flags receives the census (DeviceFlags)
 int prepare_enqueue(pbsim_ctx *c, uint8_t *d_seq, DevBuf &hp, DevBuf &tiles, DevBuf &flags, int64_t len, hipStream_t stream);
 int ensure_tables(pbsim_ctx *c, bool hp11);  // header + class tables (+ the set_mut variant) resident

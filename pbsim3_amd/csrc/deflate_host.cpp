@@ -322,6 +322,7 @@ extern "C++" int pbsim::ensure_deflate_ready(pbsim_ctx *c) {
       if (!st) HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
   return ensure_deflate_tables(c);
 }
+extern "C++" int pbsim::ensure_crc_tables(pbsim_ctx *c) { return ensure_deflate_tables(c); }
 extern "C++" int pbsim::deflate_prelaunch(pbsim_ctx *c, Slot &sl, bool want_read, bool want_maf, bool staged) {
   const pbsim_batch_info &bi = sl.b_info;
   if (want_read && bi.read_text_bytes > 0 && !df_begin(c, sl.df[0], sl.d_read_text.as<uint8_t>(), bi.read_text_bytes, staged, sl.stream))

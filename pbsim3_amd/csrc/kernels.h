@@ -312,4 +312,38 @@ void launch_deflate(const uint8_t *text, int64_t n_bytes, uint64_t *status, void
                     unsigned long long *d_prof = nullptr /* PBSIM_DEFLATE_PROF: per-phase tick sums */,
                     hipEvent_t ev_begin = nullptr, hipEvent_t ev_chunks_done = nullptr /* recorded around k_deflate_chunks */);
 
+// ---- inflate.hip: BGZF members -> their bytes, one workgroup (one wave) per member
+// One member of a piece: its deflate data in[in_off, in_off + in_len) of the piece's compressed bytes, its ISIZE bytes to
+// out[out_off, out_off + out_len) of the piece's output, `crc` the trailer's CRC-32 they must match.
+struct InflateMember {
+  int64_t in_off, out_off;
+  int32_t in_len, out_len;
+  uint32_t crc, pad;
+};
+// per-member status words of launch_inflate (0 = the member is good); inflate_reason() gives the text
+enum InflateStatus : int32_t {
+  kInfOk = 0,
+  kInfBlockType,       // invalid block type
+  kInfStoredLen,       // invalid stored block lengths
+  kInfTooMany,         // too many length or distance symbols
+  kInfClSet,           // invalid code lengths set
+  kInfRepeat,          // invalid bit length repeat
+  kInfNoEob,           // missing end-of-block code
+  kInfLitSet,          // invalid literal/lengths set
+  kInfDistSet,         // invalid distances set
+  kInfLitCode,         // invalid literal/length code
+  kInfDistCode,        // invalid distance code
+  kInfTooFar,          // invalid distance too far back
+  kInfTruncated,       // unexpected end of the deflate data
+  kInfTrailing,        // the deflate data ends before the member's trailer
+  kInfCrc,             // incorrect data check
+  kInfLength,          // incorrect length check
+  kInfCount
+};
+const char *inflate_reason(int32_t status);
+// members[0..n_members) of one piece: `in` (4-byte aligned; readable up to the dword that holds each member's last byte),
+// `out` (every member's out_len bytes at out_off), status[n_members]; CRC tables as deflate_host_tables() makes them
+void launch_inflate(const uint8_t *in, const InflateMember *members, int64_t n_members, uint8_t *out, int32_t *status,
+                    const uint32_t *d_crc_table, const uint32_t *d_pow128, hipStream_t s);
+
 }  // namespace pbsim

@@ -1,5 +1,7 @@
 #include "unit_io.h"
 
+#include "input_file.h"
+
 #include <fcntl.h>
 #include <limits.h>
 #include <math.h>
@@ -33,15 +35,29 @@ bool chomp(char *s) {
   }
   return false;
 }
+
+// a stdio stream over bytes in memory (the inflated bytes of a gzip input)
+FILE *mem_stream(const void *p, size_t n) { return n ? fmemopen(const_cast<void *>(p), n, "r") : fopen("/dev/null", "r"); }
+
+// fopen(file, "r") -- or, for a gzip file (input_file.h), a stream over its inflated bytes, which *gz keeps.  nullptr: the
+// file cannot be opened ("Cannot open file: <file>", as before) or does not inflate (that message)
+FILE *open_text(const char *file, InputBytes *gz, std::string *err) {
+  const int g = open_input ? open_input(file, gz, err) : 0;
+  if (g < 0) return nullptr;
+  FILE *fp = g ? mem_stream(gz->map, gz->size) : fopen(file, "r");
+  if (!fp) *err = std::string("Cannot open file: ") + file;
+  return fp;
+}
 }  // namespace
 
-bool split_genome(const char *file, const char *prefix, GenomeInfo *info, std::string *err) {
+bool split_genome(const char *file, const char *prefix, GenomeInfo *info, std::string *err, const void *bytes, size_t n_bytes) {
   fprintf(stderr, ":::: Reference stats ::::\n\n");
   fprintf(stderr, "file name : %s\n", file);
   fprintf(stderr, "\n");
-  FILE *fp = fopen(file, "r");
+  InputBytes gz;
+  FILE *fp = bytes ? mem_stream(bytes, n_bytes) : open_text(file, &gz, err);
   if (!fp) {
-    *err = std::string("Cannot open file: ") + file;
+    if (bytes) *err = std::string("Cannot open file: ") + file;
     return false;
   }
   std::unique_ptr<char[]> line(new char[kBuf]);
@@ -149,6 +165,30 @@ void parallel_blocks(size_t n_blocks, F &&f) {
 
 bool map_genome(const char *file, FastaMap *m, GenomeInfo *info, bool print_stats, bool *fallback, std::string *err) {
   *fallback = false;
+  {  // a gzip FASTA: its inflated bytes take the place of the mapped file (and are what a fallback pass reads, FastaMap::inflated)
+    InputBytes gz;
+    const int g = open_input ? open_input(file, &gz, err) : 0;
+    if (g < 0) {
+      m->inflate_error = *err;
+      if (print_stats) {
+        fprintf(stderr, ":::: Reference stats ::::\n\n");
+        fprintf(stderr, "file name : %s\n", file);
+        fprintf(stderr, "\n");
+      }
+      return false;
+    }
+    if (g > 0) {
+      m->map = gz.map;
+      m->size = gz.size;
+      m->inflated = true;
+      gz.map = nullptr;
+      if (m->size == 0) {
+        *fallback = true;
+        return false;
+      }
+    }
+  }
+  if (!m->inflated) {
   const int fd = open(file, O_RDONLY);
   if (fd < 0) {
     if (print_stats) {
@@ -174,6 +214,9 @@ bool map_genome(const char *file, FastaMap *m, GenomeInfo *info, bool print_stat
   }
   m->map = map;
   m->size = size;
+  }
+  const size_t size = m->size;
+  void *const map = m->map;
   const uint8_t *data = (const uint8_t *)map;
   if (data[0] != '>') {  // sequence in front of the first header: the reference writes through an unopened stream
     *fallback = true;
@@ -405,11 +448,9 @@ bool load_ref_record(const char *prefix, long num, std::string *seq, std::string
 }
 
 bool read_transcripts(const char *file, std::vector<Transcript> *out, long *total_exp, std::string *err) {
-  FILE *fp = fopen(file, "r");
-  if (!fp) {
-    *err = std::string("Cannot open file: ") + file;
-    return false;
-  }
+  InputBytes gz;
+  FILE *fp = open_text(file, &gz, err);
+  if (!fp) return false;
   std::unique_ptr<char[]> line(new char[kBuf]);
   bool first_chunk = true;
   *total_exp = 0;
@@ -444,11 +485,9 @@ bool read_transcripts(const char *file, std::vector<Transcript> *out, long *tota
 }
 
 bool read_templates(const char *file, std::vector<Transcript> *out, long *num, long long *len_total, std::string *err) {
-  FILE *fp = fopen(file, "r");
-  if (!fp) {
-    *err = std::string("Cannot open file: ") + file;
-    return false;
-  }
+  InputBytes gz;
+  FILE *fp = open_text(file, &gz, err);
+  if (!fp) return false;
   std::unique_ptr<char[]> line(new char[kBuf]);
   *num = 0;
   *len_total = 0;
@@ -511,13 +550,20 @@ bool finish_sample_stats(SampleProfile &s, double acc_total, const std::vector<l
 
 }  // namespace
 
+namespace {
+bool sample_stdio(FILE *fp, long len_min, long len_max, double acc_min, double acc_max, SampleProfile *out, std::string *err);
+}
+
 bool read_sample_fastq_stdio(const char *file, long len_min, long len_max, double acc_min, double acc_max, SampleProfile *out,
                        std::string *err) {
-  FILE *fp = fopen(file, "r");
-  if (!fp) {
-    *err = std::string("Cannot open file: ") + file;
-    return false;
-  }
+  InputBytes gz;
+  FILE *fp = open_text(file, &gz, err);
+  if (!fp) return false;
+  return sample_stdio(fp, len_min, len_max, acc_min, acc_max, out, err);
+}
+
+namespace {
+bool sample_stdio(FILE *fp, long len_min, long len_max, double acc_min, double acc_max, SampleProfile *out, std::string *err) {
   double qprob[94];
   for (int q = 0; q < 94; q++) qprob[q] = pow(10, (double)q / -10);  // pbsim.cpp:546-549
   std::vector<long> freq_len((size_t)len_max + 1, 0), freq_acc(100001, 0);
@@ -585,6 +631,7 @@ bool read_sample_fastq_stdio(const char *file, long len_min, long len_max, doubl
   fclose(fp);
   return finish_sample_stats(s, acc_total, freq_len, freq_acc, len_max, err);
 }
+}  // namespace
 
 // The same parse over the mapped file: line boundaries by memchr, the per-string sums of error probabilities (each an ordered
 // f64 sum of its own, pbsim.cpp:1263-1268) on several threads, the statistics and the filter in file order afterwards.  fgets'
@@ -593,6 +640,21 @@ bool read_sample_fastq_stdio(const char *file, long len_min, long len_max, doubl
 // anything that cannot be mapped.  The reference spends its sample FASTQ's parse on one core (361 MB: 0.75 s here with stdio).
 bool read_sample_fastq(const char *file, long len_min, long len_max, double acc_min, double acc_max, SampleProfile *out,
                        std::string *err) {
+  InputBytes gz;  // a gzip FASTQ: its inflated bytes stand for the mapped file, here and in the stdio pass
+  const int g = open_input ? open_input(file, &gz, err) : 0;
+  if (g < 0) return false;
+  if (g > 0 && (gz.size == 0 || memchr(gz.map, 0, gz.size)))
+    return sample_stdio(mem_stream(gz.map, gz.size), len_min, len_max, acc_min, acc_max, out, err);
+  struct Unmap {
+    void *p;
+    size_t n;
+    ~Unmap() {
+      if (p) munmap(p, n);
+    }
+  } unmap{nullptr, 0};
+  const char *data = (const char *)gz.map;
+  size_t size = gz.size;
+  if (g == 0) {
   const int fd = open(file, O_RDONLY);
   if (fd < 0) {
     *err = std::string("Cannot open file: ") + file;
@@ -603,18 +665,16 @@ bool read_sample_fastq(const char *file, long len_min, long len_max, double acc_
     close(fd);
     return read_sample_fastq_stdio(file, len_min, len_max, acc_min, acc_max, out, err);
   }
-  const size_t size = (size_t)sb.st_size;
+  size = (size_t)sb.st_size;
   void *map = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
   close(fd);
   if (map == MAP_FAILED) return read_sample_fastq_stdio(file, len_min, len_max, acc_min, acc_max, out, err);
   (void)madvise(map, size, MADV_SEQUENTIAL);
-  const char *data = (const char *)map;
-  struct Unmap {
-    void *p;
-    size_t n;
-    ~Unmap() { munmap(p, n); }
-  } unmap{map, size};
+  data = (const char *)map;
+  unmap.p = map;
+  unmap.n = size;
   if (memchr(data, 0, size)) return read_sample_fastq_stdio(file, len_min, len_max, acc_min, acc_max, out, err);
+  }
 
   SampleProfile &s = *out;
   s = SampleProfile();

@@ -3,6 +3,7 @@
 // transcript TSV reader (get_transcript_inf :1075-1136, the in-loop reader
 // :4428-4455).  Plain host C++; the per-base work (toupper, hp) is on the GPU.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include <string>
@@ -18,7 +19,11 @@ struct GenomeInfo {
 };
 
 // Splits <file> into <prefix>_NNNN.ref, printing the reference's ":::: Reference stats ::::" block.
-bool split_genome(const char *file, const char *prefix, GenomeInfo *info, std::string *err);
+// `bytes` (optional): the file's content already in memory -- the inflated bytes of a gzip FASTA that map_genome handed over
+// (FastaMap::inflated) -- read instead of the file; `file` is then only the name reported.  Without it, a gzip file is
+// inflated here (input_file.h).
+bool split_genome(const char *file, const char *prefix, GenomeInfo *info, std::string *err, const void *bytes = nullptr,
+                  size_t n_bytes = 0);
 // The same pass over the FASTA without stdio (round 4): the file mapped, header lines found by memchr on threads, the line
 // feeds of every record counted on threads -- a record is then its lines as they lie in the file plus its length, and the
 // line feeds are squeezed out on the GPU (pbsim_job_add_record_lines).  Prints the same ":::: Reference stats ::::" block and
@@ -35,6 +40,8 @@ struct FastaRecord {
 struct FastaMap {
   void *map = nullptr;
   size_t size = 0;
+  bool inflated = false;  // `map` holds the inflated bytes of a gzip file (an anonymous mapping), not the file
+  std::string inflate_error;  // map_genome: a gzip file that did not inflate (the message; nothing mapped)
   std::vector<FastaRecord> recs;
   FastaMap() = default;
   FastaMap(const FastaMap &) = delete;

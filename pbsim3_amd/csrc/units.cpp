@@ -19,6 +19,7 @@
 
 #include "ctx.h"
 #include "engine_internal.h"
+#include "input_file.h"
 #include "unit_io.h"
 #include "philox.h"
 
@@ -177,7 +178,10 @@ static int load_unit_file(pbsim_ctx *c, const char *path, int64_t stats[2], bool
   std::string err;
   long a = 0;
   long long b = 0;
-  if (templ ? !read_templates(path, &tr, &a, &b, &err) : !read_transcripts(path, &tr, &a, &err)) return fail(err);
+  pbsim_ctx *const was = set_input_context(c);  // a gzip file: BGZF inflated on this context's device, other gzip by zlib
+  const bool ok = templ ? read_templates(path, &tr, &a, &b, &err) : read_transcripts(path, &tr, &a, &err);
+  set_input_context(was);
+  if (!ok) return fail(err);
   std::vector<const char *> ids;
   std::vector<int64_t> plus, minus, lens;
   std::vector<const uint8_t *> seqs;
