@@ -38,7 +38,6 @@
 #include "../../include/pbsim3_amd.h"
 #include "gzout.h"
 #include "input_file.h"
-#include "knobs.h"
 #include "unit_io.h"
 
 namespace {
@@ -423,11 +422,12 @@ void parse_args(int argc, char **argv, Cli &c) {
 // pwrite from 16 threads into ONE file 3.6 GB/s, into 16 files 66 GB/s).  So a sink callback only copies its piece into a
 // buffer of the pool below -- on helper threads, a piece of 80 MB is gone in ~2 ms -- and returns; one writer thread per file
 // pwrite()s the buffers in the order they came, and the job keeps k records going side by side (pbsim_job_set_interleave), so
-// that 2k files are being written at any time.  The pool bounds the memory (PBSIM_CLI_WRITE_BUFFER_MB, default 8192): a
-// callback waits for a buffer when the files fall that far behind.
+// that 2k files are being written at any time.  The pool bounds the memory (kPoolBytes): a callback waits for a buffer when
+// the files fall that far behind.
 struct WritePool {
-  static constexpr size_t kChunk = 32u << 20, kSlice = 4u << 20;
-  size_t max_chunks = 256, made = 0;
+  static constexpr size_t kChunk = 32u << 20, kSlice = 4u << 20, kPoolBytes = (size_t)8192 << 20;
+  static constexpr size_t kMaxChunks = kPoolBytes / kChunk;
+  size_t made = 0;
   double waited_s = 0, copy_s = 0;   // callbacks waiting for a buffer (the files are behind) | copying (PBSIM_TRACE)
   int64_t copied = 0;
   std::vector<char *> idle;
@@ -446,9 +446,6 @@ struct WritePool {
   std::condition_variable tcv, dcv;
   bool stop = false;
   WritePool() {
-    const char *mb = pbsim::exp_env("PBSIM_CLI_WRITE_BUFFER_MB");
-    const size_t bytes = (size_t)(mb && atoll(mb) > 0 ? atoll(mb) : 8192) << 20;
-    max_chunks = std::max<size_t>(4, bytes / kChunk);
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
     for (unsigned i = 0; i < std::min(8u, std::max(1u, hw / 4)); i++) helpers.emplace_back([this]() { run(); });
   }
@@ -501,7 +498,7 @@ struct WritePool {
         idle.pop_back();
         return p;
       }
-      if (made < max_chunks) {
+      if (made < kMaxChunks) {
         made++;
         lk.unlock();
         // (huge pages where the kernel grants them: 8 GB of buffers are two million first-touch faults in 4 KB pages)
@@ -546,17 +543,13 @@ struct PosFile {
     // The rank's threads are bound to its GPU's NUMA node (pbsim_bind_host_to_device): right for the delivery threads and their
     // pinned staging, wrong for the threads that fill the page cache -- with every file's pages coming out of one node's
     // allocator eight writers moved 18 GB/s together; unbound they take pages (and memory bandwidth) from both sockets.
-    // PBSIM_CLI_WRITERS_BOUND=1 keeps them bound (A/B).
-    static const bool keep_bound = pbsim::exp_env("PBSIM_CLI_WRITERS_BOUND") && atoi(pbsim::exp_env("PBSIM_CLI_WRITERS_BOUND")) == 1;
-    if (!keep_bound) {
-      cpu_set_t all;
-      CPU_ZERO(&all);
-      for (int i = 0; i < CPU_SETSIZE; i++) CPU_SET(i, &all);
-      (void)sched_setaffinity(0, sizeof all, &all);
+    cpu_set_t all;
+    CPU_ZERO(&all);
+    for (int i = 0; i < CPU_SETSIZE; i++) CPU_SET(i, &all);
+    (void)sched_setaffinity(0, sizeof all, &all);
 #ifdef SYS_set_mempolicy
-      (void)syscall(SYS_set_mempolicy, 0 /* MPOL_DEFAULT */, nullptr, 0);
+    (void)syscall(SYS_set_mempolicy, 0 /* MPOL_DEFAULT */, nullptr, 0);
 #endif
-    }
     std::unique_lock<std::mutex> lk(mu);
     for (;;) {
       cv.wait(lk, [&] { return finishing || !q.empty(); });
@@ -673,11 +666,8 @@ struct JobFiles {
   int64_t first = 1;
   std::vector<std::unique_ptr<RecFiles>> recs;
   RecFiles &of(int64_t record) { return *recs[(size_t)(record - first)]; }
-  std::unique_ptr<WritePool> pool;  // positional files are written behind the job (WritePool above) unless PBSIM_CLI_SYNC_WRITES=1
-  void use_async_writes() {
-    const char *sw = pbsim::exp_env("PBSIM_CLI_SYNC_WRITES");
-    if (!(sw && *sw == '1')) pool.reset(new WritePool);
-  }
+  std::unique_ptr<WritePool> pool;  // positional files are written behind the job (WritePool above) once use_async_writes() was called
+  void use_async_writes() { pool.reset(new WritePool); }
   // after pbsim_job_run: every file's queue written, every file closed (write errors end the process here)
   void close_all() {
     for (auto &r : recs)

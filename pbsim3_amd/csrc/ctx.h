@@ -17,7 +17,6 @@
 
 #include "../../include/pbsim3_amd.h"
 #include "host_tables.h"
-#include "knobs.h"
 #include "kernels.h"
 
 namespace pbsim {
@@ -93,6 +92,8 @@ struct HostBuf {  // pinned staging
 using namespace pbsim;
 
 constexpr int kMaxSlots = 6;
+constexpr int kPipelineDepth = 2;  // slots pbsim_simulate_* keeps in flight
+static_assert(kPipelineDepth >= 1 && kPipelineDepth <= kMaxSlots, "the pipeline's slots are the first of kMaxSlots");
 
 // Everything one in-flight batch owns.  Several slots (each with its own stream)
 // let the walk of batch k+1 fill the GPU while the longest reads of batch k
@@ -186,10 +187,7 @@ struct DfLane {
   // compresses a few MB more than the one before it), and a 256 MB block costs tens of milliseconds to give back and as much to
   // page-lock again: a context that runs job after job (bench.py, the replay of one rank after the other) paid that again and
   // again -- stalls of 25-95 ms in a job's first rounds and behind its last collective (profiles/r05z_replay_host_noise.txt).
-#ifndef PBSIM_ARENA_IDLE_JOBS
-#define PBSIM_ARENA_IDLE_JOBS 16   // (-DPBSIM_ARENA_IDLE_JOBS=1: the behaviour of rounds 2-5, for an A/B)
-#endif
-  static constexpr int kArenaIdleJobs = PBSIM_ARENA_IDLE_JOBS;
+  static constexpr int kArenaIdleJobs = 16;
   void arena_release() {
     arena_blocks.clear();
     arena_fill.clear();
@@ -366,7 +364,6 @@ struct pbsim_ctx {
   bool scratch_factor_fixed = false;
   int64_t rewalked_batches = 0;  // batches walked again at the full factor (pbsim_prof: how often the estimate was too low)
   bool scratch_auto = true;    // sized per record by pbsim_simulate_wgs unless PBSIM_SCRATCH_MB / pbsim_set_scratch_bytes said otherwise
-  int pipeline_depth = 2;      // slots pbsim_simulate_* keeps in flight
   hipStream_t df_streams[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [lane][kernels | copies]
   bool defer_text_sync = false;  // finalize_text returns once the sizes are known; the text emission is still in flight (job pipeline)
   bool defer_account = false;    // deliver() leaves the batch's statistics to its caller (units.cpp accounts batch k + 1 on a thread beside the delivery of batch k)
@@ -442,9 +439,9 @@ int stats_merge(StatsAcc *st, const pbsim_params &p, const pbsim_comm *comm, int
 // d_text[0..n) (device) -> BGZF-framed gzip members, handed to `consume` piece by piece from pinned staging (deflate.hip)
 // `place` (optional): pinned host memory for a piece of the given size instead of the lane's staging (a batch-wide arena)
 // the first pieces of the selected... of slot `sl`'s two deflate calls (read text, MAF text) launched NOW, behind the slot's text
-// emission: the delivery that follows (deflate_pieces on the same buffers) finds them under way.  `staged`: the pieces will go
-// through the lanes' own staging (one rank) rather than a caller's arena.  Harmless when the delivery never comes.
-int deflate_prelaunch(pbsim_ctx *c, Slot &sl, bool want_read, bool want_maf, bool staged);
+// emission: the delivery that follows (deflate_pieces on the same buffers) finds them under way.  The pieces go through the
+// lanes' own staging, not a caller's arena.  Harmless when the delivery never comes.
+int deflate_prelaunch(pbsim_ctx *c, Slot &sl, bool want_read, bool want_maf);
 int deflate_pieces(pbsim_ctx *c, DfLane &lane, const uint8_t *d_text, int64_t n,
                    const std::function<int(const char *, int64_t)> &consume,
                    const std::function<char *(int64_t)> *place = nullptr);

@@ -41,8 +41,9 @@ int ensure_deflate_tables(pbsim_ctx *c) {
 // `place` (optional): where a piece of `total` compressed bytes shall be copied to (pinned host memory of the caller's, e.g.
 // an arena that keeps a whole batch) instead of the lane's double-buffered staging.
 // What a call needs before its first copy: buffers, streams, the code table and the kernels of its first pieces (df_begin).
-// This part can run AHEAD of the call (deflate_prelaunch, from another thread, on another stream): an experiment of round 5 that
-// was measured and not taken (job.cpp prelaunch(), profiles/r05_prelaunch_ab.txt); a product build never prelaunches.
+// This part can run AHEAD of the call (deflate_prelaunch, on the slot's own stream): the unit driver does that for a batch whose
+// bytes it delivers (units.cpp).  For the job pipeline's rounds it was measured and not taken (round 5,
+// profiles/r05_prelaunch_ab.txt): the kernels take the GPU from the round that is being delivered.
 struct DfGeom {
   int64_t piece, max_ch, n_pieces;
   int ahead, nbuf;
@@ -53,22 +54,19 @@ struct DfGeom {
   int64_t len(int64_t j, int64_t n) const { return std::min(piece, n - off(j)); }
 };
 DfGeom df_geom(int64_t n) {
-  // chunks per piece = per launch and per copy (experiment knob PBSIM_DEFLATE_PIECE_CHUNKS; a piece's members stay below 4 GiB)
-  static const int64_t piece_chunks = [] {
-    const char *e = exp_env("PBSIM_DEFLATE_PIECE_CHUNKS");
-    const int64_t v = e ? atoll(e) : DF_PIECE_CHUNKS;
-    return std::max<int64_t>(256, std::min<int64_t>(65536, v));
-  }();
+  // chunks per piece = per launch and per copy (a piece's members stay below 4 GiB)
+  constexpr int64_t piece_chunks = DF_PIECE_CHUNKS;
   // pieces the lane's kernels run ahead of the piece whose copy is being enqueued (ahead + 1 dense buffers in use).  Four
   // since the end of round 4 (two before): the kernels of a piece share the GPU with the next round's walk and arrive late
   // now and then; two more pieces in hand cover that -- configs[1] 1116-1120 -> 1089-1102 ms, configs[4] 3200 -> 3100-3140
   // (same box, profiles/r04_replay_late_ab.txt; six or eight with more buffers: no better) for 0.5 GB of HBM per lane.
-  static const int ahead_env = exp_env("PBSIM_DEFLATE_AHEAD") ? atoi(exp_env("PBSIM_DEFLATE_AHEAD")) : 4;
+  constexpr int kDfAhead = 4;
+  static_assert(kDfAhead >= 1 && kDfAhead <= kDfBuffers - 1, "ahead + 1 dense buffers are in use");
   DfGeom g;
   g.piece = piece_chunks * DF_CHUNK;
   g.max_ch = std::min<int64_t>(piece_chunks, (n + DF_CHUNK - 1) / DF_CHUNK);
   g.n_pieces = (n + g.piece - 1) / g.piece;
-  g.ahead = std::max(1, std::min(kDfBuffers - 1, ahead_env));
+  g.ahead = kDfAhead;
   g.nbuf = g.ahead + 1;
   return g;
 }
@@ -156,8 +154,7 @@ int df_begin(pbsim_ctx *c, DfLane &sl, const uint8_t *d_text, int64_t n, bool ow
   // A prelaunch takes the table fit and ONE piece: enough for the call's first copy to start at once; the rest of the head
   // start follows when the call begins (more pieces launched ahead took the GPU from the round being delivered:
   // profiles/r05_prelaunch_ab.txt).
-  static const int pre_pieces = exp_env("PBSIM_DEFLATE_PRE_PIECES") ? atoi(exp_env("PBSIM_DEFLATE_PRE_PIECES")) : 1;
-  const int64_t first = std::min<int64_t>(launch_stream ? std::max(1, std::min(pre_pieces, g.ahead)) : g.ahead, g.n_pieces);
+  const int64_t first = std::min<int64_t>(launch_stream ? 1 : g.ahead, g.n_pieces);
   for (int64_t j = 0; j < first; j++)
     if (!df_launch_piece(c, sl, g, d_text, n, j, false, own_staging, d_prof)) return PBSIM_FAILED;
   sl.pre_count = (int)first;
@@ -315,19 +312,19 @@ extern "C++" int pbsim::deflate_pieces(pbsim_ctx *c, DfLane &lane, const uint8_t
   return deflate_stream(c, lane, d_text, n, consume, place);
 }
 extern "C++" int pbsim::ensure_deflate_ready(pbsim_ctx *c) {
-  // (called by a job before its delivery threads start: the lanes' shared streams exist from here on -- the round loop's
-  // prelaunch and the delivery thread's calls would otherwise both find them missing and both create them)
+  // (called by a job before its delivery threads start: the lanes' shared streams exist from here on -- the
+  // delivery threads' calls would otherwise each find them missing and each create them)
   for (auto &lane : c->df_streams)
     for (hipStream_t &st : lane)
       if (!st) HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
   return ensure_deflate_tables(c);
 }
 extern "C++" int pbsim::ensure_crc_tables(pbsim_ctx *c) { return ensure_deflate_tables(c); }
-extern "C++" int pbsim::deflate_prelaunch(pbsim_ctx *c, Slot &sl, bool want_read, bool want_maf, bool staged) {
+extern "C++" int pbsim::deflate_prelaunch(pbsim_ctx *c, Slot &sl, bool want_read, bool want_maf) {
   const pbsim_batch_info &bi = sl.b_info;
-  if (want_read && bi.read_text_bytes > 0 && !df_begin(c, sl.df[0], sl.d_read_text.as<uint8_t>(), bi.read_text_bytes, staged, sl.stream))
+  if (want_read && bi.read_text_bytes > 0 && !df_begin(c, sl.df[0], sl.d_read_text.as<uint8_t>(), bi.read_text_bytes, true, sl.stream))
     return PBSIM_FAILED;
-  if (want_maf && bi.maf_text_bytes > 0 && !df_begin(c, sl.df[1], sl.d_maf_text.as<uint8_t>(), bi.maf_text_bytes, staged, sl.stream))
+  if (want_maf && bi.maf_text_bytes > 0 && !df_begin(c, sl.df[1], sl.d_maf_text.as<uint8_t>(), bi.maf_text_bytes, true, sl.stream))
     return PBSIM_FAILED;
   return PBSIM_SUCCEEDED;
 }

@@ -292,8 +292,6 @@ pbsim_ctx *pbsim_create(const pbsim_params *p, int device) {
   const char *mb = getenv("PBSIM_SCRATCH_MB");
   c->scratch_budget = (mb && atoll(mb) > 0) ? atoll(mb) * (1LL << 20) : (8LL << 30);
   c->scratch_auto = !(mb && atoll(mb) > 0);
-  const char *pd = exp_env("PBSIM_PIPELINE_DEPTH");
-  if (pd && atoi(pd) >= 1) c->pipeline_depth = std::min(kMaxSlots, atoi(pd));
   return c.release();
 }
 
@@ -1326,7 +1324,7 @@ extern "C++" int pbsim::simulate_wgs(pbsim_ctx *c, const BatchOutput &out) {
   // expected pass-0 output bases per read: E[L] of the length table, a little less than that while nothing has
   // been measured (deletions outweigh insertions in most models), the measured ratio afterwards
   double mean = 0.97 * std::min<double>(c->hdr.mean_len, (double)c->ref_len);
-  const int n_slots = std::max(1, std::min(kMaxSlots, c->pipeline_depth));
+  constexpr int n_slots = kPipelineDepth;
   if (c->scratch_auto) {
     // Nobody chose a pool size: a record wants to run as two batches (one per slot) -- a batch's walk lasts at least
     // as long as its longest read, so many small batches waste the GPU on their tails -- up to a share of the free HBM
@@ -1439,7 +1437,7 @@ extern "C++" int pbsim::simulate_wgs(pbsim_ctx *c, const BatchOutput &out) {
       drop_pending();
       return PBSIM_FAILED;
     }
-    if (fifo.empty() && n_slots > 1 && bi.n_final < pd.n && bi.need_truncated_read) {
+    if (fifo.empty() && bi.n_final < pd.n && bi.need_truncated_read) {
       // The quota falls inside this batch and the next read will be a truncated one (pbsim.cpp:3795-3800).  A lone
       // read walks for up to ~20 ms: start it on the free slot now, beside this batch's text emission.
       tail_slot = (pd.slot + 1) % n_slots;

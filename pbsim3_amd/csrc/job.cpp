@@ -867,9 +867,8 @@ struct Job {
     // Ramp-up: nothing moves over the link until the job's first round has been walked and its text emitted, and a full round
     // walks for 12-30 ms.  The first two rounds of a job are a fifth and a half of a full one: bytes flow after ~4 ms, and each
     // round's walk still hides behind the delivery of the round in front of it (a round's bytes take ~3x its walk).  The same
-    // on every rank (`rounds` counts the rounds begun).  PBSIM_JOB_RAMP=0 turns it off (A/B).
-    static const bool ramp_on = !(exp_env("PBSIM_JOB_RAMP") && atoi(exp_env("PBSIM_JOB_RAMP")) == 0);
-    if (ramp_on && rounds < 2) n_per = std::min<int64_t>(n_per, std::max<int64_t>(64, (int64_t)((double)R.cap * (rounds == 0 ? 0.2 : 0.5))));
+    // on every rank (`rounds` counts the rounds begun).
+    if (rounds < 2) n_per = std::min<int64_t>(n_per, std::max<int64_t>(64, (int64_t)((double)R.cap * (rounds == 0 ? 0.2 : 0.5))));
     n_per = std::max<int64_t>(n_per, 1);
     if (!collect(rec)) return PBSIM_FAILED;  // (an announced record: resident and prepared by now, or waited for here)
     const int s = acquire_slot();
@@ -892,19 +891,6 @@ struct Job {
     reads_walked += n_per;
     rounds++;
     return PBSIM_SUCCEEDED;
-  }
-
-  // Measured and NOT taken (round 5, profiles/r05_prelaunch_ab.txt): the table fit and the first piece(s) of a round's two
-  // compressions launched behind its text emission, while the delivery thread is still moving the round in front
-  // (deflate_host.cpp df_begin on the slot's stream), so that the round's delivery starts with its first totals waiting
-  // instead of 2-4 ms of kernel latency.  A rank of eight gained 1-2 % (163-165 against 166-169 ms), the one-GPU jobs LOST 1.5-2 %
-  // (configs[1] 1102-1110 against 1083 ms, configs[4] 3175-3186 against 3130) with one, two or four pieces launched ahead: the
-  // kernels take the GPU from the round that is being delivered -- the same outcome as round 4's "next round's compression on a
-  // second worker".  Read only by an EXPERIMENTAL build (knobs.h), off in the product.
-  int prelaunch(const pbsim_batch_info &bi) {
-    static const bool on = exp_env("PBSIM_DEFLATE_PRELAUNCH") && atoi(exp_env("PBSIM_DEFLATE_PRELAUNCH")) == 1;
-    if (!on || !deflated() || bi.n_final <= 0) return PBSIM_SUCCEEDED;
-    return deflate_prelaunch(c, c->s(), sink->on_read_text != nullptr, sink->on_maf_text != nullptr, !multi);
   }
 
   // One round comes back.  Two shapes, chosen when the round was begun (Round::clear, the same on every rank):
@@ -951,7 +937,7 @@ struct Job {
     if (rd.clear) {
       if (code == 0) {  // every read final: the text leaves now, `before` arrives with the exchange
         const double tf = now_us();
-        fin_ok = finalize_uncut(c, &bi) && finalize_text(c, &bi) && prelaunch(bi);
+        fin_ok = finalize_uncut(c, &bi) && finalize_text(c, &bi);
         if (!fin_ok) my_err = g_err;
         t_fin += now_us() - tf;
       }
@@ -1012,7 +998,7 @@ struct Job {
     } else {
       // a failure here travels in the exchange's status word: every rank leaves the job at the same collective
       const double tf = now_us();
-      fin_ok = (untouched ? finalize_uncut(c, &bi) : finalize_cut(c, before, &bi)) && finalize_text(c, &bi) && prelaunch(bi);
+      fin_ok = (untouched ? finalize_uncut(c, &bi) : finalize_cut(c, before, &bi)) && finalize_text(c, &bi);
       if (!fin_ok) my_err = g_err;
       if (untouched) c->s().b_info.len_total_after = bi.len_total_after = before + pass0;
       t_fin += now_us() - tf;
@@ -1467,7 +1453,6 @@ static int job_run_impl(pbsim_ctx *c, const pbsim_comm *comm, const pbsim_record
                         atoi(getenv("PBSIM_COMM_ALWAYS")) != 0);
   J.trace = getenv("PBSIM_TRACE") != nullptr;
   J.t_start = now_us();
-  const char *jd = exp_env("PBSIM_JOB_DEPTH");
   // Rounds in flight (+ one pending delivery < the slots of the rounds).  Three keep a GPU full whose text stays in HBM or whose
   // link carries a fraction of the job (several ranks).  A job that delivers all its bytes over one or two links is bound by
   // them (80 ms a round against 18 ms of walk): one round in flight is as fast (1334 vs 1336 ms), its walk does not share the
@@ -1482,7 +1467,8 @@ static int job_run_impl(pbsim_ctx *c, const pbsim_comm *comm, const pbsim_record
   // Several ranks (round 4, measured per rank against virtual ranks -- profiles/r04_replay_depth_ab.txt): every rank delivers
   // its own blocks over its own link, so a rank of eight is in the same regime as one GPU alone: configs[4] 594 / 592 / 570 ms
   // per rank with 3 / 2 / 1 rounds in flight, configs[1] 190 / 189 / 191.
-  J.depth = std::max(1, std::min(kMaxSlots - 3, jd ? atoi(jd) : (delivers ? 1 : 3)));
+  static_assert(kMaxSlots - 3 >= 3, "the rounds in flight, one pending delivery and the two tail slots share kMaxSlots");
+  J.depth = delivers ? 1 : 3;
   c->bias.hp11_seen = c->hp11_before_job;  // every run of the job starts from the same Q15 state
   J.seen11 = c->bias.hp11_seen;
   J.recs.resize(n);
@@ -1558,7 +1544,6 @@ static int job_run_impl(pbsim_ctx *c, const pbsim_comm *comm, const pbsim_record
   // ---- batch size: a few rounds per record and rank, not below what keeps a walk longer than its longest read
   const int P = c->p.pass_num;
   const int regions = has_quality(c) ? 3 : 2;
-  const char *jr = exp_env("PBSIM_JOB_ROUNDS");  // experiment knob: rounds per record the batches are sized for
   // (several ranks that deliver their bytes: two rounds per record and rank -- every delivery call pays a start-up of a few ms,
   // and a rank of eight has a quarter of a record's bytes per round to spread it over; measured per rank against virtual
   // ranks, configs[4] on eight: 520-537 ms with four rounds per record, 496-504 with two, 525+ with one -- profiles/r04_replay_rounds_ab.txt)
@@ -1568,7 +1553,7 @@ static int job_run_impl(pbsim_ctx *c, const pbsim_comm *comm, const pbsim_record
   // per record, 208-215 at two (one: 211; the split, the wave walker's workgroups and the ramp-up rounds move nothing there): a
   // round of 850 000 reads amortises its longest lanes better and the wave walker's share of the GPU time drops.  A job that
   // delivers its text is bound by its link either way: 54.2 / 53.6 / 54.6 Gbases/s at two / three / four, it keeps four.)
-  const int rounds_per_record = std::max(1, jr ? atoi(jr) : (delivers_text ? (multi ? 2 : kRoundsPerRecord) : 2));
+  const int rounds_per_record = delivers_text ? (multi ? 2 : kRoundsPerRecord) : 2;  // rounds per record the batches are sized for
   double target = (double)max_quota * P / ((double)rounds_per_record * W);
   target = std::max(target, std::min(kMinBatchBases, (double)max_quota * P / W));
   if (J.sink && (J.sink->on_read_text || J.sink->on_maf_text)) target = std::min(target, kSinkBatchBases);

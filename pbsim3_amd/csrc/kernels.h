@@ -10,11 +10,8 @@ namespace pbsim {
 
 constexpr int kWG = 256;            // threads per workgroup of the walk kernels (4 waves)
 constexpr int kLenBuckets = 4096;   // length buckets per accuracy class in the task sort
-#ifndef PBSIM_BIN_PAD
-#define PBSIM_BIN_PAD 16
-#endif
-constexpr int kBinPad = PBSIM_BIN_PAD;  // int32 slots per counter of the sort's histogram / cursors: one counter per 64-byte line,
-                                      // neighbouring (hot) length buckets do not share a line that 8 XCDs fight over
+constexpr int kBinPad = 16;         // int32 slots per counter of the sort's histogram / cursors: one counter per 64-byte line,
+                                    // neighbouring (hot) length buckets do not share a line that 8 XCDs fight over
 constexpr int kLenShift = 8;        // bucket = len >> 8  (len_max 1e6 -> 3907 buckets)
 constexpr int kScratchPad = 64;     // per-task slack: a row holds factor * L + kScratchPad columns (factor <= 2: pbsim.cpp:5488 uses 2*len_max+1)
 constexpr int kMaxClasses = 64;

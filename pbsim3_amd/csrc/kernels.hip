@@ -32,38 +32,17 @@ constexpr int kScanBlock = 256;  // single-workgroup scan kernels
 // Wave priorities (s_setprio).  The walk of one slot shares the GPU with every other kernel of the other slot; its waves
 // live for milliseconds, the others' for microseconds.  Without a raised priority the short kernels' waves rarely get to
 // issue on a SIMD they share with walk waves (k_text_headers: 0.5 ms alone, 13 ms beside a QSHMM walk).
-#ifndef PBSIM_WALK_PRIO
-#define PBSIM_WALK_PRIO 1   // waves that carry the longest reads raise themselves (walk_priority)
-#endif
-#ifndef PBSIM_TEXT_PRIO
-#define PBSIM_TEXT_PRIO 3   // every kernel that is not a walk
-#endif
-__device__ __forceinline__ void short_kernel_priority() {
-  if (PBSIM_TEXT_PRIO) __builtin_amdgcn_s_setprio(PBSIM_TEXT_PRIO);
-}
+// Every kernel that is not a walk runs at priority 3; the walk's waves that carry the longest reads raise themselves
+// (walk_priority).
+__device__ __forceinline__ void short_kernel_priority() { __builtin_amdgcn_s_setprio(3); }
 constexpr uint32_t kATGC = 0x43475441u;  // "ATGC" little-endian (mut.ins_nt / sub_nt_n, pbsim.cpp:5485-5486)
 
 __device__ __forceinline__ uint32_t to_upper(uint32_t c) { return (c >= 'a' && c <= 'z') ? c - 32u : c; }
 
-// The per-column scratch rows are written once by a walk and read once by the text emission: streaming (nontemporal)
-// accesses keep them from evicting the reference lines the walk's gathers re-use from L2.
-#ifndef PBSIM_NT
-#define PBSIM_NT 1
-#endif
-__device__ __forceinline__ void scratch_store(uint32_t *p, uint32_t v) {
-#if PBSIM_NT & 1
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
-__device__ __forceinline__ uint32_t scratch_load(const uint32_t *p) {
-#if PBSIM_NT & 2
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
+// The per-column scratch rows are written once by a walk and read once by the text emission: streaming (nontemporal) stores
+// keep them from evicting the reference lines the walk's gathers re-use from L2 (profiles/r01o_walk_traffic.json); loads are plain.
+__device__ __forceinline__ void scratch_store(uint32_t *p, uint32_t v) { __builtin_nontemporal_store(v, p); }
+__device__ __forceinline__ uint32_t scratch_load(const uint32_t *p) { return *p; }
 
 // revcomp()'s base map (pbsim.cpp:5853-5863): A<->T, G<->C, everything else unchanged
 __device__ __forceinline__ uint32_t complement(uint32_t c) {
@@ -775,7 +754,6 @@ __global__ __launch_bounds__(256) void k_wg_scatter(SortArgs a, int32_t *wg_star
 
 // waves that carry the longest reads are the kernel's critical path: raise them
 __device__ __forceinline__ void walk_priority(int lmax_wave, int mean_len) {
-  if (!PBSIM_WALK_PRIO) return;
   const int r = lmax_wave / (2 * (mean_len > 0 ? mean_len : 1));
   if (r >= 3) __builtin_amdgcn_s_setprio(3);
   else if (r == 2) __builtin_amdgcn_s_setprio(2);
@@ -1506,7 +1484,6 @@ __device__ __forceinline__ void coop_walk_task(const WalkArgs &a, const uint8_t 
     s_tr[lane] = (uint8_t)rb;
     s_tr[64 + lane] = (uint8_t)fb;
     wave_sync();
-#ifndef PBSIM_COOP_NOSTORE  // experiment: the walk without its scratch writes
     if (lane * 4 < nv) {
       const uint32_t dr = reinterpret_cast<const uint32_t *>(s_tr)[lane];
       const uint32_t df = reinterpret_cast<const uint32_t *>(s_tr + 64)[lane];
@@ -1514,7 +1491,6 @@ __device__ __forceinline__ void coop_walk_task(const WalkArgs &a, const uint8_t 
       scratch_store(maf_read + step_dw + lane_dw, dr);
       scratch_store(maf_ref + step_dw + lane_dw, df);
     }
-#endif
   }
   if (lane == 0) {
     if (ro0 < L) atomicOr(&a.flags->error, kErrScratchOverflow);

@@ -224,7 +224,7 @@ extern "C++" int pbsim::simulate_units_range(pbsim_ctx *c, int64_t first_read, i
   DeferTextSync defer_guard(c);
   // (a delivering job keeps three slots busy: one whose bytes are leaving, one finalized behind it, one walking)
   const bool delivering = sink && c->deflate != 0 && (sink->on_read_text || sink->on_maf_text);
-  const int n_slots = std::max(1, std::min(kMaxSlots, delivering ? std::max(3, c->pipeline_depth) : c->pipeline_depth));
+  const int n_slots = delivering ? std::max(3, kPipelineDepth) : kPipelineDepth;
   const int64_t R = first_read - 1 + n_reads;  // last read of the range
   int64_t cap = batch_capacity(c);
   struct Pending {
@@ -246,13 +246,11 @@ extern "C++" int pbsim::simulate_units_range(pbsim_ctx *c, int64_t first_read, i
   // two streams compressed BEFORE the batch in front of it is delivered, so the link does not wait for the emission kernels nor
   // for a call's first deflate kernels between two batches; and the batch's statistics are added on a thread beside that
   // delivery instead of behind it.  The sink still receives the batches in read order.  Round 6, same box
-  // (tools/closed_ab/units_ab*.sh, profiles/r06_units_delivery_ab.txt): 121 -> 112 -> 102.5 ms per job.  MORE batches do not
+  // (profiles/r06_units_delivery_ab.txt): 121 -> 112 -> 102.5 ms per job.  MORE batches do not
   // help (every batch's walk lasts as long as its longest read: twelve batches walk at 40 instead of 120 Gbases/s), nor does a
   // ramp of batch sizes, nor walking the batches one after the other on the GPU (105 -> 108 ms).
-  const char *up = exp_env("PBSIM_UNITS_PARTS");  // experiment knobs: batches per job; prelaunch of a batch's first deflate piece
-  const char *upre = exp_env("PBSIM_UNITS_PRELAUNCH");
-  const int n_parts = up && atoi(up) > 0 ? atoi(up) : n_slots;
-  const bool prelaunch = delivering && (c->deflate & 3) == 3 && (upre ? atoi(upre) != 0 : true);
+  const int n_parts = n_slots;  // batches per job
+  const bool prelaunch = delivering && (c->deflate & 3) == 3;  // of a batch's first deflate piece
   int64_t next_begin = first_read, next_read = first_read;
   int next_slot = 0;
   bool have_prev = false;  // a batch that is finalized and not yet delivered (it keeps its slot)
@@ -300,7 +298,7 @@ extern "C++" int pbsim::simulate_units_range(pbsim_ctx *c, int64_t first_read, i
       next_slot = (next_slot + 1) % n_slots;
       next_begin += n;
     }
-    if (fifo.empty()) {  // (one slot: the finalized batch must leave before the next one can begin)
+    if (fifo.empty()) {  // (nothing could be begun beside the finalized batch: it leaves first.  A guard: the slots are two or more)
       if (!deliver_prev()) {
         give_up();
         return PBSIM_FAILED;
@@ -332,7 +330,7 @@ extern "C++" int pbsim::simulate_units_range(pbsim_ctx *c, int64_t first_read, i
     next_read += bi.n_final;
     // the table fit and the first piece of this batch's two streams go onto the slot's stream right behind its text emission:
     // when the batch's turn comes its first copies start at once instead of waiting for their kernels (deflate_host.cpp df_begin)
-    if (prelaunch && !deflate_prelaunch(c, c->s(), sink->on_read_text != nullptr, sink->on_maf_text != nullptr, true)) {
+    if (prelaunch && !deflate_prelaunch(c, c->s(), sink->on_read_text != nullptr, sink->on_maf_text != nullptr)) {
       give_up();
       return PBSIM_FAILED;
     }
