@@ -222,6 +222,34 @@ int pbsim_get_stats(pbsim_ctx *ctx, pbsim_stats *out);          /* pbsim.cpp:408
  * current reference record. */
 int pbsim_set_sample_profile(pbsim_ctx *ctx, int64_t n, const uint8_t *const *quals, const int64_t *lens);
 int pbsim_simulate_sample(pbsim_ctx *ctx, const pbsim_sink *sink);
+/* get_sample_inf itself (pbsim.cpp:1155-1330) on the context's GPU: the FASTQ's bytes go through HBM, every record's 4th
+ * line is summed and filtered there (length range: the params' len_min / len_max; accuracy range: the arguments, already
+ * int(x*100)*0.01 as pbsim.cpp:1620 leaves them) and the kept strings are packed into the pool pbsim_simulate_sample
+ * reads -- the context is then in the state pbsim_set_sample_profile leaves.  *out = the numbers print_sample_stats prints
+ * (pbsim.cpp:1336-1360) and the stored profile's .stats file holds (:1317-1326), bit for bit the host parser's.  Failures
+ * carry the reference's texts ("fastq is too long. Max acceptable length is 1000000." :1228/:1283, "fastq is too many. Max
+ * acceptable number is 100000000." :1236, "there is no sample in the valid range of length and accuracy." :1294); the context
+ * keeps the profile it had and stays usable.  A tables-only context refuses ("no HIP device").
+ *   pbsim_sample_profile_from_bytes   the bytes in host memory
+ *   pbsim_sample_profile_from_device  the bytes in the memory of the context's GPU (complete when the call is made)
+ *   pbsim_load_sample_fastq           a file: plain, BGZF (inflated by this GPU, the bytes stay in its memory) or other gzip
+ *                                     (zlib on the host); a pipe or an empty file goes through the host's stdio parse
+ *   pbsim_sample_profile_text         the kept strings one per line = the bytes of sample_profile_<ID>.fastq (:1264);
+ *                                     *bytes = their size; dst may be NULL to ask for it (else cap >= *bytes)
+ *   pbsim_set_sample_chunk_bytes      FASTQ bytes per window of the pass through HBM (0: the default, 64 MiB; 16 to 2^30).
+ *                                     The result does not depend on it. */
+typedef struct pbsim_sample_stats {
+  int64_t num, len_min, len_max, len_total;                                         /* all reads (pbsim.cpp:1232-1245) */
+  int64_t num_filtered, len_min_filtered, len_max_filtered, len_total_filtered;     /* kept reads (:1257-1271)         */
+  double len_mean_filtered, len_sd_filtered, accuracy_mean_filtered, accuracy_sd_filtered;  /* :1298-1315               */
+} pbsim_sample_stats;
+int pbsim_sample_profile_from_bytes(pbsim_ctx *ctx, const void *fastq, int64_t n, double accuracy_min, double accuracy_max,
+                                    pbsim_sample_stats *out);
+int pbsim_sample_profile_from_device(pbsim_ctx *ctx, const void *d_fastq, int64_t n, double accuracy_min, double accuracy_max,
+                                     pbsim_sample_stats *out);
+int pbsim_load_sample_fastq(pbsim_ctx *ctx, const char *path, double accuracy_min, double accuracy_max, pbsim_sample_stats *out);
+int pbsim_sample_profile_text(pbsim_ctx *ctx, char *dst, int64_t cap, int64_t *bytes);
+int pbsim_set_sample_chunk_bytes(pbsim_ctx *ctx, int64_t bytes);
 /* SAM header the reference's main() writes when it opens the samtools pipe for a
  * unit (pass_num > 1; pbsim.cpp:721-722 wgs, :784-785 trans/templ).  Returns the
  * byte count (excluding the NUL), or the size needed when buf is NULL/too small. */

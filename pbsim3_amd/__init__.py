@@ -47,6 +47,14 @@ class BatchInfo(C.Structure):
     ]
 
 
+class SampleStats(C.Structure):
+    """pbsim_sample_stats: what print_sample_stats prints about a --sample FASTQ and its filtered profile"""
+    _fields_ = [("num", C.c_int64), ("len_min", C.c_int64), ("len_max", C.c_int64), ("len_total", C.c_int64),
+                ("num_filtered", C.c_int64), ("len_min_filtered", C.c_int64), ("len_max_filtered", C.c_int64),
+                ("len_total_filtered", C.c_int64), ("len_mean_filtered", C.c_double), ("len_sd_filtered", C.c_double),
+                ("accuracy_mean_filtered", C.c_double), ("accuracy_sd_filtered", C.c_double)]
+
+
 SINK_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_char), C.c_int64)
 
 
@@ -185,6 +193,11 @@ API = [
     ("pbsim_bam_header", C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64]),
     ("pbsim_set_sample_profile", C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     ("pbsim_simulate_sample", C.c_int, [C.c_void_p, C.POINTER(Sink)]),
+    ("pbsim_sample_profile_from_bytes", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.POINTER(SampleStats)]),
+    ("pbsim_sample_profile_from_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.POINTER(SampleStats)]),
+    ("pbsim_load_sample_fastq", C.c_int, [C.c_void_p, C.c_char_p, C.c_double, C.c_double, C.POINTER(SampleStats)]),
+    ("pbsim_sample_profile_text", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("pbsim_set_sample_chunk_bytes", C.c_int, [C.c_void_p, C.c_int64]),
     ("pbsim_simulate_sample_comm", C.c_int, [C.c_void_p, C.POINTER(Comm), C.POINTER(RecordSink)]),
     ("pbsim_set_deflate", C.c_int, [C.c_void_p, C.c_int]),
     ("pbsim_deflate_bound", C.c_int64, [C.c_int64]),
@@ -637,6 +650,42 @@ class Context:
         ptrs = (C.c_void_p * n)(*[C.cast(b, C.c_void_p).value for b in keep])
         lens = (C.c_int64 * n)(*[len(q) for q in quals])
         _check(self.lib.pbsim_set_sample_profile(self.h, n, ptrs, lens))
+
+    def load_sample_fastq(self, path, acc_min=0.75, acc_max=1.0):
+        """The profile of the --sample FASTQ `path` (plain, BGZF or other gzip), parsed and filtered on the GPU: lengths within
+        the params' len_min / len_max, accuracies within [acc_min, acc_max].  Returns its SampleStats."""
+        st = SampleStats()
+        _check(self.lib.pbsim_load_sample_fastq(self.h, os.fsencode(path), acc_min, acc_max, C.byref(st)))
+        return st
+
+    def sample_profile_from_fastq(self, data, acc_min=0.75, acc_max=1.0):
+        """The same from FASTQ bytes: `bytes`, or a contiguous uint8 torch tensor on the context's device."""
+        st = SampleStats()
+        if isinstance(data, (bytes, bytearray, memoryview)):
+            data = bytes(data)
+            _check(self.lib.pbsim_sample_profile_from_bytes(self.h, data, len(data), acc_min, acc_max, C.byref(st)))
+            return st
+        import torch
+        if not (isinstance(data, torch.Tensor) and data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()):
+            raise TypeError("sample_profile_from_fastq: bytes or a contiguous uint8 tensor on the context's device")
+        if data.device.index != self.device:
+            raise ValueError("sample_profile_from_fastq: the tensor is on another device than the context")
+        torch.cuda.current_stream(data.device).synchronize()   # the bytes are complete when the library reads them
+        _check(self.lib.pbsim_sample_profile_from_device(self.h, C.c_void_p(data.data_ptr()), data.numel(), acc_min, acc_max,
+                                                         C.byref(st)))
+        return st
+
+    def sample_profile(self):
+        """The filtered quality strings the context holds, in file order (the lines of sample_profile_<ID>.fastq)."""
+        n = C.c_int64(0)
+        _check(self.lib.pbsim_sample_profile_text(self.h, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(max(n.value, 1))
+        _check(self.lib.pbsim_sample_profile_text(self.h, buf, n.value, C.byref(n)))
+        return buf.raw[:n.value].split(b"\n")[:-1]
+
+    def set_sample_chunk_bytes(self, n):
+        """FASTQ bytes per window of the GPU profile builder (0: the default); the profile does not depend on it."""
+        _check(self.lib.pbsim_set_sample_chunk_bytes(self.h, n))
 
     def simulate_sample(self, collect=True):
         return self._simulate(self.lib.pbsim_simulate_sample, collect)

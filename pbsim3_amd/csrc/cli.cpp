@@ -125,16 +125,9 @@ void open_sink(const Cli &c, Out *o, const std::string &plain_name, const std::s
 
 bool native_bam(const Cli &c) { return c.p.pass_num > 1 && !c.no_gzip && !c.use_samtools; }
 
-// a regular file that starts with the gzip magic (what input_file.h inflates)
-bool is_gzip_file(const char *file) {
+bool is_regular_file(const char *file) {
   struct stat sb;
-  if (stat(file, &sb) != 0 || !S_ISREG(sb.st_mode)) return false;  // (a FIFO is never opened here)
-  const int fd = open(file, O_RDONLY);
-  if (fd < 0) return false;
-  unsigned char m[2];
-  const bool gz = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && pread(fd, m, 2, 0) == 2 && m[0] == 0x1f && m[1] == 0x8b;
-  close(fd);
-  return gz;
+  return stat(file, &sb) == 0 && S_ISREG(sb.st_mode);  // (a FIFO is never opened here)
 }
 
 // what main() writes when it opens the samtools pipe (pbsim.cpp:721-722), as SAM text or as the BAM header
@@ -814,19 +807,45 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
   }
   if (rank0) print_sim_param(c);
 
-  // A gzip --sample is inflated (BGZF: on the GPU) while the profile is parsed, before the context would otherwise exist:
-  // the context comes first then.  A plain sample keeps the reference's order and output.
+  // A --sample that is a regular file (plain or gzip) is parsed, filtered and packed into the profile on this rank's GPU
+  // (pbsim_load_sample_fastq), so the context comes first then.  A pipe keeps the host's stdio parse, the reference's order
+  // and its output.
   pbsim_ctx *ctx = nullptr;
-  if (sampling && !c.sam_reuse && is_gzip_file(c.sample.c_str())) {
+  const bool sample_on_gpu = sampling && !c.sam_reuse && is_regular_file(c.sample.c_str());
+  if (sample_on_gpu) {
     ctx = pbsim_create(&c.p, c.device);
     if (!ctx) check(0);
     pbsim::set_input_context(ctx);
+    phase("parameters printed, context created (HIP initialised)");
   }
   pbsim::SampleProfile prof;
   if (sampling) {  // pbsim.cpp:580-617: read (or re-read) the profile, print its statistics
     std::string e;
     if (c.sam_reuse) {
       if (!pbsim::read_sample_profile(profile_fq, profile_stats, &prof, &e)) die(": %s", e.c_str());
+    } else if (sample_on_gpu) {
+      pbsim_sample_stats st;
+      check(pbsim_load_sample_fastq(ctx, c.sample.c_str(), c.accuracy_min, c.accuracy_max, &st));
+      prof.num = (long)st.num;
+      prof.len_min = (long)st.len_min;
+      prof.len_max = (long)st.len_max;
+      prof.len_total = st.len_total;
+      prof.num_filtered = (long)st.num_filtered;
+      prof.len_min_filtered = (long)st.len_min_filtered;
+      prof.len_max_filtered = (long)st.len_max_filtered;
+      prof.len_total_filtered = st.len_total_filtered;
+      prof.len_mean_filtered = st.len_mean_filtered;
+      prof.len_sd_filtered = st.len_sd_filtered;
+      prof.accuracy_mean_filtered = st.accuracy_mean_filtered;
+      prof.accuracy_sd_filtered = st.accuracy_sd_filtered;
+      phase("sample profile on the GPU");
+      if (c.sam_store && rank0) {  // the two profile files from the strings the GPU kept
+        int64_t n = 0;
+        check(pbsim_sample_profile_text(ctx, nullptr, 0, &n));
+        std::unique_ptr<char[]> text(new char[(size_t)n + 1]);
+        check(pbsim_sample_profile_text(ctx, text.get(), n, &n));
+        if (!pbsim::write_sample_profile_text(profile_fq, profile_stats, text.get(), (size_t)n, prof, &e)) die(": %s", e.c_str());
+      }
     } else {
       if (!pbsim::read_sample_fastq(c.sample.c_str(), (long)c.p.len_min, (long)c.p.len_max, c.accuracy_min,
                                     c.accuracy_max, &prof, &e))
@@ -856,12 +875,13 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
     }
   }
 
-  phase("parameters printed, sample profile parsed");
+  if (!sample_on_gpu) phase("parameters printed, sample profile parsed");
   if (!ctx) ctx = pbsim_create(&c.p, c.device);
   if (!ctx) check(0);
   pbsim::set_input_context(ctx);  // gzip inputs of this rank: inflated on its own device
-  phase("context created (HIP initialised)");
-  if (sampling) {
+  if (!sample_on_gpu) phase("context created (HIP initialised)");
+  if (sample_on_gpu) {  // (pbsim_load_sample_fastq left the profile in HBM)
+  } else if (sampling) {
     std::vector<const uint8_t *> qp;
     std::vector<int64_t> ql;
     for (const std::string &q : prof.quals) {

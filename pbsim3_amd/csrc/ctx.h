@@ -354,6 +354,7 @@ struct pbsim_ctx {
   std::vector<int32_t> sq_len;
   std::vector<int64_t> sq_off;
   int64_t sq_total = 0;        // sample.len_total_filtered
+  int64_t sp_chunk_bytes = 0;  // FASTQ bytes per window of the GPU profile builder (pbsim_set_sample_chunk_bytes; 0: its default)
   int64_t scratch_budget = 0;  // bytes of wave scratch per slot
   // Columns a task's rows are laid out for = scratch_factor x its length + pad.  The reference's own buffers take 2 x (the
   // bound that cannot overflow: every column consumes a reference base or is one of at most... in practice ~1.06-1.2 x); a

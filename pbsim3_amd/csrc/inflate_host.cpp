@@ -98,7 +98,8 @@ int64_t bgzf_inflated_size(const std::vector<BgzfMember> &mem) {
 
 // the members of src (indexed by bgzf_index) -> dst[0 .. inflated size), on the GPU, piece by piece: the host fills the
 // pinned input staging of piece k while the GPU decodes piece k - 1 and piece k - 2's output travels back (two buffer sets)
-int inflate_members(pbsim_ctx *c, const uint8_t *src, const std::vector<BgzfMember> &mem, uint8_t *dst) {
+// dst_on_device: dst is memory of the context's GPU -- a piece's output goes there GPU to GPU and only its status words travel
+int inflate_members(pbsim_ctx *c, const uint8_t *src, const std::vector<BgzfMember> &mem, uint8_t *dst, bool dst_on_device) {
   NEED_DEVICE(c);
   HIP_OK(hipSetDevice(c->device));
   if (mem.empty()) return PBSIM_SUCCEEDED;
@@ -171,6 +172,7 @@ int inflate_members(pbsim_ctx *c, const uint8_t *src, const std::vector<BgzfMemb
         snprintf(m, sizeof m, "gzip member at byte offset %lld: %s", (long long)mem[s.first + (size_t)i].offset, inflate_reason(st[i]));
         return fail(m);
       }
+    if (dst_on_device) return PBSIM_SUCCEEDED;
     uint8_t *to = dst + mem[s.first].out_off;
     const uint8_t *from = (const uint8_t *)s.h_out.p;
     parallel_ranges((size_t)s.out_bytes, (size_t)16 << 20, [&](size_t a, size_t e) { memcpy(to + a, from + a, e - a); });
@@ -178,7 +180,13 @@ int inflate_members(pbsim_ctx *c, const uint8_t *src, const std::vector<BgzfMemb
   };
   auto download = [&](Set &s) -> int {
     HIP_OK(hipStreamWaitEvent(s_copy, s.k1, 0));
-    HIP_OK(hipMemcpyAsync(s.h_out.p, s.d_out.p, (size_t)(s.status_off + s.n_mem * 4), hipMemcpyDeviceToHost, s_copy));
+    if (dst_on_device) {
+      HIP_OK(hipMemcpyAsync(dst + mem[s.first].out_off, s.d_out.p, (size_t)s.out_bytes, hipMemcpyDeviceToDevice, s_copy));
+      HIP_OK(hipMemcpyAsync((uint8_t *)s.h_out.p + s.status_off, s.d_out.as<uint8_t>() + s.status_off, (size_t)(s.n_mem * 4),
+                            hipMemcpyDeviceToHost, s_copy));
+    } else {
+      HIP_OK(hipMemcpyAsync(s.h_out.p, s.d_out.p, (size_t)(s.status_off + s.n_mem * 4), hipMemcpyDeviceToHost, s_copy));
+    }
     HIP_OK(hipEventRecord(s.down, s_copy));
     return PBSIM_SUCCEEDED;
   };

@@ -21,7 +21,8 @@ struct BgzfMember {
 bool bgzf_index(const uint8_t *p, int64_t n, std::vector<BgzfMember> *out);
 int64_t bgzf_inflated_size(const std::vector<BgzfMember> &mem);
 // the indexed members of src -> dst (bgzf_inflated_size bytes), on the context's GPU; PBSIM_FAILED with
-// "gzip member at byte offset N: <reason>" for the first member that is not good
-int inflate_members(pbsim_ctx *c, const uint8_t *src, const std::vector<BgzfMember> &mem, uint8_t *dst);
+// "gzip member at byte offset N: <reason>" for the first member that is not good.  dst_on_device: dst is memory of that
+// GPU and the inflated bytes never leave it (the sample FASTQ of sample_profile.cpp)
+int inflate_members(pbsim_ctx *c, const uint8_t *src, const std::vector<BgzfMember> &mem, uint8_t *dst, bool dst_on_device = false);
 
 }  // namespace pbsim

@@ -343,4 +343,28 @@ const char *inflate_reason(int32_t status);
 void launch_inflate(const uint8_t *in, const InflateMember *members, int64_t n_members, uint8_t *out, int32_t *status,
                     const uint32_t *d_crc_table, const uint32_t *d_pow128, hipStream_t s);
 
+// ---- sample_profile.hip: the sampling method's profile (get_sample_inf, pbsim.cpp:1155-1330) from FASTQ bytes in HBM.
+// A window buf[b0, b1) of the file starts `phase` line feeds into a record (0-3; with phase 3 it starts at the quality line's
+// first byte).  Tiles of kSpTile bytes from the kSpTile boundary at or below b0; buf is readable up to the end of the last tile
+// and 16 bytes further.
+constexpr int kSpTile = 1024;  // one 16-byte load per lane of a wave
+inline int64_t sp_tiles(int64_t b0, int64_t b1) { return b1 > b0 ? (b1 - (b0 & ~(int64_t)(kSpTile - 1)) + kSpTile - 1) / kSpTile : 0; }
+// tile_count[t] = line feeds of tile t; *nul |= 1 when the window holds a NUL byte
+void launch_sp_count(const uint8_t *buf, int64_t b0, int64_t b1, int64_t *tile_count, int32_t *nul, hipStream_t s);
+// tile_base = the exclusive scan of tile_count.  Record r of the window = the quality line between line feeds 4r + 2 - phase
+// and 4r + 3 - phase of the window: rec_start[r] = its first byte, rec_end[r] = its line feed (offsets into buf);
+// rec_start[n_rec] is also written when the window ends inside a quality line (its first byte)
+void launch_sp_lines(const uint8_t *buf, int64_t b0, int64_t b1, int phase, const int64_t *tile_base, uint32_t *rec_start,
+                     uint32_t *rec_end, hipStream_t s);
+// One lane per record: rec_len[r]; for a length in [len_min, len_max] accuracy[r] = 1.0 - prob / len with prob the sum of
+// qprob[clamp(byte - 33, 0, 93)] from 0.0 in string order (pbsim.cpp:1263-1268, the host's IEEE additions and division);
+// padded[r] = (len + 7) & ~7 when also acc_min <= accuracy <= acc_max (the string is kept), else 0
+void launch_sp_sums(const uint8_t *buf, const uint32_t *rec_start, const uint32_t *rec_end, int64_t n_rec, int32_t len_min,
+                    int32_t len_max, double acc_min, double acc_max, const double *qprob /* 94, device */, int32_t *rec_len,
+                    double *accuracy, int64_t *padded, hipStream_t s);
+// the kept strings to pool + off[r] (off = the exclusive scan of padded; pool 8-byte aligned), pad bytes 0: the layout of
+// pbsim_set_sample_profile
+void launch_sp_pool(const uint8_t *buf, const uint32_t *rec_start, const int32_t *rec_len, const int64_t *padded, const int64_t *off,
+                    int64_t n_rec, uint8_t *pool, hipStream_t s);
+
 }  // namespace pbsim

@@ -761,6 +761,63 @@ bool read_sample_fastq(const char *file, long len_min, long len_max, double acc_
   return finish_sample_stats(s, acc_total, freq_len, freq_acc, len_max, err);
 }
 
+bool read_sample_fastq_mem(const void *bytes, size_t n, long len_min, long len_max, double acc_min, double acc_max,
+                           SampleProfile *out, std::string *err) {
+  FILE *fp = mem_stream(bytes, n);
+  if (!fp) {
+    *err = "Cannot open the sample bytes as a stream";
+    return false;
+  }
+  return sample_stdio(fp, len_min, len_max, acc_min, acc_max, out, err);
+}
+
+bool sample_stats_from_records(const int32_t *len, const double *accuracy, size_t n, long len_max, double acc_min, double acc_max,
+                               SampleProfile *out, std::string *err) {
+  SampleProfile &s = *out;
+  s.num_filtered = s.len_max_filtered = 0;
+  s.len_total_filtered = 0;
+  s.len_min_filtered = LONG_MAX;
+  std::vector<long> freq_len((size_t)len_max + 1, 0), freq_acc(100001, 0);
+  double acc_total = 0.0;
+  for (size_t r = 0; r < n; r++) {
+    const double a = accuracy[r];
+    if (!(a >= acc_min && a <= acc_max)) continue;
+    const long l = len[r];
+    acc_total += a;
+    s.num_filtered++;
+    s.len_total_filtered += l;
+    freq_len[(size_t)l]++;
+    freq_acc[(size_t)(int)(a * 100000 + 0.5)]++;
+    s.len_max_filtered = std::max(s.len_max_filtered, l);
+    s.len_min_filtered = std::min(s.len_min_filtered, l);
+  }
+  return finish_sample_stats(s, acc_total, freq_len, freq_acc, len_max, err);
+}
+
+namespace {
+bool write_profile_stats(FILE *g, const SampleProfile &p) {
+  fprintf(g, "num\t%ld\nlen_total\t%lld\nlen_min\t%ld\nlen_max\t%ld\n", p.num_filtered, p.len_total_filtered,
+          p.len_min_filtered, p.len_max_filtered);
+  fprintf(g, "len_mean\t%f\nlen_sd\t%f\naccuracy_mean\t%f\naccuracy_sd\t%f\n", p.len_mean_filtered, p.len_sd_filtered,
+          p.accuracy_mean_filtered, p.accuracy_sd_filtered);
+  return fclose(g) == 0;
+}
+}  // namespace
+
+bool write_sample_profile_text(const std::string &fq, const std::string &stats, const char *text, size_t n, const SampleProfile &p,
+                               std::string *err) {
+  FILE *f = fopen(fq.c_str(), "w"), *g = fopen(stats.c_str(), "w");
+  if (!f || !g) {
+    if (f) fclose(f);
+    if (g) fclose(g);
+    *err = "Cannot open sample_profile";
+    return false;
+  }
+  const bool wrote = n == 0 || fwrite(text, 1, n, f) == n;
+  const bool ok = (fclose(f) == 0) && wrote;
+  return write_profile_stats(g, p) && ok;
+}
+
 bool write_sample_profile(const std::string &fq, const std::string &stats, const SampleProfile &p, std::string *err) {
   FILE *f = fopen(fq.c_str(), "w"), *g = fopen(stats.c_str(), "w");
   if (!f || !g) {
@@ -770,12 +827,8 @@ bool write_sample_profile(const std::string &fq, const std::string &stats, const
     return false;
   }
   for (const std::string &q : p.quals) fprintf(f, "%s\n", q.c_str());
-  fprintf(g, "num\t%ld\nlen_total\t%lld\nlen_min\t%ld\nlen_max\t%ld\n", p.num_filtered, p.len_total_filtered,
-          p.len_min_filtered, p.len_max_filtered);
-  fprintf(g, "len_mean\t%f\nlen_sd\t%f\naccuracy_mean\t%f\naccuracy_sd\t%f\n", p.len_mean_filtered, p.len_sd_filtered,
-          p.accuracy_mean_filtered, p.accuracy_sd_filtered);
   const bool ok = fclose(f) == 0;
-  return (fclose(g) == 0) && ok;
+  return write_profile_stats(g, p) && ok;
 }
 
 bool read_sample_profile(const std::string &fq, const std::string &stats, SampleProfile *out, std::string *err) {

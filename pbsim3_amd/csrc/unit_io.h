@@ -81,7 +81,17 @@ bool read_sample_fastq(const char *file, long len_min, long len_max, double acc_
 // the same through fgets, chunk by chunk as the reference reads it (files with NUL bytes, pipes; the checker of the fast path)
 bool read_sample_fastq_stdio(const char *file, long len_min, long len_max, double acc_min, double acc_max, SampleProfile *out,
                              std::string *err);
+// ... and over bytes in memory instead of a file
+bool read_sample_fastq_mem(const void *bytes, size_t n, long len_min, long len_max, double acc_min, double acc_max,
+                           SampleProfile *out, std::string *err);
+// The filtered half of the statistics (pbsim.cpp:1269-1330) from the records whose length lies in [len_min, len_max], in
+// file order: their lengths and accuracies (1.0 - prob / len, as computed by whoever summed the strings -- the GPU profile
+// builder, sample_profile.cpp).  *out keeps its all-reads numbers and its strings.
+bool sample_stats_from_records(const int32_t *len, const double *accuracy, size_t n, long len_max, double acc_min, double acc_max,
+                               SampleProfile *out, std::string *err);
 // sample_profile_<ID>.fastq (one quality string per line) + .stats ("key<TAB>value" lines)
+bool write_sample_profile_text(const std::string &fq, const std::string &stats, const char *text, size_t n, const SampleProfile &p,
+                               std::string *err);  // `text`: the strings already one per line
 bool write_sample_profile(const std::string &fq, const std::string &stats, const SampleProfile &p, std::string *err);
 bool read_sample_profile(const std::string &fq, const std::string &stats, SampleProfile *out, std::string *err);
 
