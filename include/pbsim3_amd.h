@@ -543,7 +543,17 @@ int pbsim_device_synchronize(pbsim_ctx *ctx);
 void pbsim_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 /* sha256-able dumps of the host-built tables (Q13 fixtures): returns bytes
  * written, or the size needed when buf is NULL. which: 0 prob2len (int32
- * [len_rand_value+1]), 1 prob2acc (uint8 [acc_rand_value+1]), 2 class tables */
+ * [len_rand_value+1]), 1 prob2acc (uint8 [acc_rand_value+1]), 2 class tables.
+ * Test infrastructure as well, read back from the device behind the context's stream: what the preparation kernels
+ * (k_hp_breaks / k_hp_carry / k_hp_final) made of the context's CURRENT unit -- 3 the prepared sequence bytes, ref_len of
+ * them (trans / templ: the units in load order, each followed by one line feed); 4 the hp bytes, ref_len of them -- refused
+ * (-1, pbsim_last_error) when bit 7 of the sequence bytes carries hp == 11 instead (--hp-del-bias 1, no byte >= 0x80), as
+ * the array is not written then; 5 the twelve int64 census counts of the most recent preparation alone (pbsim_set_reference*,
+ * an adopted prefetch, pbsim_set_transcripts / pbsim_set_templates / their file loaders); 6 the census accumulated by
+ * pbsim_add_hp_census so far.  3, 4 and 5 are valid only directly behind one of the preparations listed: pbsim_add_hp_census
+ * prepares its record in the same buffers (and rewrites the bit-7 state) without making it the current unit, so a dump taken
+ * between it and the next pbsim_set_reference* returns that record's bytes, cut to the old ref_len, beside the old census.
+ * Returns -1 for an unknown `which` or when there is nothing to dump. */
 int64_t pbsim_dump_table(pbsim_ctx *ctx, int which, void *buf, int64_t cap);
 
 #ifdef __cplusplus

@@ -740,6 +740,15 @@ class Context:
         _check(self.lib.pbsim_set_transcripts(self.h, n, c_ids, c_plus, c_minus, c_seqs, c_lens))
         self._keep = None
 
+    def set_templates(self, ids, seqs):
+        """ids: list[str]; seqs: list[bytes] -- every template is one unit with one read over its whole length."""
+        n = len(ids)
+        c_ids = (C.c_char_p * n)(*[i.encode() for i in ids])
+        keep = [C.create_string_buffer(s, len(s)) for s in seqs]
+        c_seqs = (C.c_void_p * n)(*[C.cast(b, C.c_void_p).value for b in keep])
+        c_lens = (C.c_int64 * n)(*[len(s) for s in seqs])
+        _check(self.lib.pbsim_set_templates(self.h, n, c_ids, c_seqs, c_lens))
+
     def load_transcript_file(self, path):
         """--transcript file -> units; returns (transcripts, total expression value)"""
         st = (C.c_int64 * 2)()
@@ -996,9 +1005,13 @@ class Context:
         return a.value
 
     def dump_table(self, which):
+        """pbsim_dump_table (test infrastructure): 0 prob2len, 1 prob2acc, 2 class tables; of the current unit as the
+        preparation kernels left it: 3 sequence bytes, 4 hp bytes (PbsimError when bit 7 of the sequence bytes carries
+        hp == 11 instead), 5 its census (12 int64), 6 the census pbsim_add_hp_census has accumulated (12 int64)"""
         n = self.lib.pbsim_dump_table(self.h, which, None, 0)
         if n < 0:
             raise PbsimError(self.lib.pbsim_last_error().decode(errors="replace"))
         buf = C.create_string_buffer(n)
-        self.lib.pbsim_dump_table(self.h, which, C.cast(buf, C.c_void_p), n)
+        if self.lib.pbsim_dump_table(self.h, which, C.cast(buf, C.c_void_p), n) != n:
+            raise PbsimError(self.lib.pbsim_last_error().decode(errors="replace"))
         return buf.raw

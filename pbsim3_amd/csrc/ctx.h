@@ -342,6 +342,7 @@ struct pbsim_ctx {
   int64_t ref_len = 0;
   int64_t unit = 0;
   int64_t census[kHpSlots] = {0};
+  int64_t unit_census[kHpSlots] = {0};  // of the current unit's preparation alone (pbsim_dump_table 5)
   bool census_done = false;
   bool census_from_job = false;  // census_done was set by pbsim_job_run from the job's own records (recomputed per run), not by pbsim_finish_hp_census
   bool hp11_explicit = false;    // an hp == 11 base was counted by pbsim_add_hp_census (the pre-pass over all records, pbsim.cpp:677-696)

@@ -471,6 +471,7 @@ static int set_reference_common(pbsim_ctx *c, uint8_t *d_seq, int64_t len, int64
     return PBSIM_FAILED;
   }
   note_hp11(c, census);
+  memcpy(c->unit_census, census, sizeof census);
   c->d_seq = d_seq;
   c->ref_len = len;
   c->unit = record_index;
@@ -1593,6 +1594,31 @@ int64_t pbsim_dump_table(pbsim_ctx *c, int which, void *buf, int64_t cap) {
       src = c->qct.blob.data();
       n = (int64_t)c->qct.blob.size();
     }
+  } else if (which == 3 || which == 4) {
+    // test infrastructure: the current unit as the preparation kernels left it, read back behind the context's stream
+    if (c->device < 0 || !c->stream || !c->d_seq || c->ref_len < 1) {
+      fail("pbsim_dump_table: no prepared unit (pbsim_set_reference*, pbsim_set_transcripts, pbsim_set_templates)");
+      return -1;
+    }
+    if (which == 4 && c->seq_hp_flag) {
+      fail("pbsim_dump_table: the hp array is not written when bit 7 of the sequence bytes carries hp == 11");
+      return -1;
+    }
+    n = c->ref_len;
+    if (buf && cap >= n) {
+      const void *d = which == 3 ? (const void *)c->d_seq : c->d_hp.p;
+      hipError_t he = hipSetDevice(c->device);
+      if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+      if (he == hipSuccess) he = hipMemcpy(buf, d, (size_t)n, hipMemcpyDeviceToHost);
+      if (he != hipSuccess) {
+        fail(std::string("pbsim_dump_table: HIP error: ") + hipGetErrorString(he));
+        return -1;
+      }
+    }
+    return n;
+  } else if (which == 5 || which == 6) {
+    src = which == 5 ? c->unit_census : c->census;
+    n = (int64_t)sizeof c->census;
   } else {
     return -1;
   }

@@ -120,6 +120,7 @@ static int set_units(pbsim_ctx *c, int64_t n, const char *const *ids, const int6
   HIP_OK(hipMemsetAsync(c->d_seq_own.as<uint8_t>() + total, 0, 64, c->stream));
   int64_t census[kHpSlots] = {0};
   if (!prepare_reference(c, c->d_seq_own.as<uint8_t>(), total, keep_first, census)) return PBSIM_FAILED;
+  memcpy(c->unit_census, census, sizeof census);
   if (reads > 0) {
     if (!upload(c->d_read_unit, runit.data(), runit.size() * 4, c->stream)) return PBSIM_FAILED;
     if (!upload(c->d_read_base, rbase.data(), rbase.size() * 8, c->stream)) return PBSIM_FAILED;

@@ -86,6 +86,18 @@ def test_no_device_context_refuses_compute():
     ctx.close()
 
 
+def test_read_back_hook_without_a_unit():
+    """pbsim_dump_table 3-6 on a tables-only context: nothing was prepared, so the bytes are refused with a message (not
+    handed back from wherever) and both censuses are twelve zeros"""
+    with P.Context(P.default_params(strategy=P.STRATEGY_WGS, method=P.METHOD_ERR), -1) as ctx:
+        for which in (3, 4):
+            with pytest.raises(P.PbsimError, match="no prepared unit"):
+                ctx.dump_table(which)
+        for which in (5, 6):
+            assert np.frombuffer(ctx.dump_table(which), dtype=np.int64).tolist() == [0] * 12
+        assert ctx.lib.pbsim_dump_table(ctx.h, 7, None, 0) == -1
+
+
 def test_header_tables_known_answers():
     """SURVEY A.1 known answers measured on the compiled reference: len_rv 99911,
     acc_rv 100000, classes 63..89, sha1 of prob2len as int64[100001]."""

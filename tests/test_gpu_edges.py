@@ -29,6 +29,18 @@ def _rand_seq(rng, n, alphabet="ACGT"):
     return "".join(np.array(list(alphabet))[rng.integers(0, len(alphabet), n)])
 
 
+def _carry_chunk_seam(rng):
+    """4 194 304 + 8192 bases: k_hp_carry scans the 4096-base tiles 1024 at a time, so base 4 194 304 is the seam between
+    its chunks.  6001 x T from base 4 190 000 (odd -> hp 11, tiles 1022..1024) lie across it; only one run can, so the run
+    of 13 x A lies across the tile seam behind it (base 4 198 400), and 12 x C (hp 10) end at the chunk seam's tile 1021."""
+    seam = 1024 * 4096
+    s = list(_rand_seq(rng, seam + 8192))
+    for start, run, left, right in ((4_190_000, "T" * 6001, "c", "g"), (seam + 4096 - 6, "a" * 6 + "A" * 7, "C", "G"),
+                                    (1022 * 4096 - 12, "C" * 12, "A", "G")):
+        s[start - 1:start + len(run) + 1] = left + run + right
+    return ["".join(s)]
+
+
 def _compare(args, tmp_path, scratch_mb=None):
     outs, _ = product.run_wgs(harness.resolve(args), scratch_mb=scratch_mb)
     want = harness.run_oracle(args, "philox", str(tmp_path))
@@ -72,6 +84,11 @@ EDGE = {
     # scratch pool far too small for one default batch: the driver must shrink batches, same bytes
     "many_small_batches": (lambda rng: [_rand_seq(rng, 600000)],
                            ONT + ["--depth", "15", "--seed", "18", "--length-mean", "1000", "--length-sd", "700"]),
+    # runs across base 4 194 304, where the one-workgroup scans of k_hp_carry pass from their first 1024 tiles to the next;
+    # --hp-del-bias 5: every hp class has its own deletion threshold (test_gpu_reference_prep.py reads the same seam back
+    # base by base; this is the seam in simulated reads)
+    "carry_chunk_seam": (_carry_chunk_seam,
+                         ONT + ["--depth", "2", "--seed", "23", "--hp-del-bias", "5", "--length-mean", "2500", "--length-sd", "1500"]),
 }
 
 
