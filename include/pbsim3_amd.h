@@ -260,6 +260,24 @@ int64_t pbsim_sam_header(pbsim_ctx *ctx, char *buf, int64_t cap);
  * caller BGZF-frames the stream (the CLI does, replacing the samtools child of pbsim.cpp:716). */
 int pbsim_set_bam_output(pbsim_ctx *ctx, int on);
 int64_t pbsim_bam_header(pbsim_ctx *ctx, char *buf, int64_t cap);
+/* The truth as aligned BAM instead of MAF (any strategy x method that writes MAF, any pass_num).  While on, everything that
+ * delivers the MAF stream -- pbsim_sink::on_maf_text, pbsim_record_sink::on_maf_text, pbsim_batch_fetch's maf_text, with
+ * pbsim_set_deflate their BGZF members -- delivers one BAM alignment record (SAMv1 4.2) per task instead of one MAF block, in
+ * the same task order and under the same offsets contract; pbsim_batch_info::maf_text_bytes counts those bytes.  The read
+ * stream, the statistics and pbsim_simulate_arrays are untouched.  A record: refID = wgs 0, trans / templ the unit's 0-based
+ * load order; pos = the MAF reference line's start; mapq 60; bin = reg2bin(pos, pos + span) (low 16 bits); flag 0 / 16 for a
+ * '+' / '-' MAF read line; read_name = the id of the FASTQ / SAM record; CIGAR = the maximal M / I / D runs of the MAF columns
+ * in reference orientation ('-' on the reference line: I, on the read line: D); SEQ / QUAL = the MAF read line without its
+ * '-' and the qualities in the same orientation (ERRHMM: zeros); one tag, NM = n_sub + n_ins + n_del of the task.  More than
+ * 65535 runs: n_cigar_op 2 with <q>S<span>N and the runs in a CG:B,I tag behind NM (SAMv1 4.2.2).
+ * pbsim_truth_bam_header / pbsim_job_truth_bam_header: the bytes in front of the first record ("BAM\1", @HD, one @SQ per
+ * reference -- wgs: "ref" with the record's length; trans / templ: every loaded unit, its MAF name cut at the first whitespace
+ * byte -- , @PG, the reference list); same return convention as pbsim_bam_header.  Unit names that are empty after the cut, equal
+ * to another unit's or outside SAMv1's RNAME character set make pbsim_set_truth_bam (units already loaded) or the first
+ * simulate call fail; the message names the unit. */
+int pbsim_set_truth_bam(pbsim_ctx *ctx, int on);
+int64_t pbsim_truth_bam_header(pbsim_ctx *ctx, char *buf, int64_t cap);
+int64_t pbsim_job_truth_bam_header(pbsim_ctx *ctx, int64_t record, char *buf, int64_t cap);
 /* Compression on the GPU, replacing the `gzip -c` children of pbsim.cpp:708-730 and the BGZF layer of
  * `samtools view -b` (pbsim.cpp:716).  pbsim_set_deflate(ctx, mask): bit 0 makes the read sink, bit 1
  * the MAF sink receive gzip members (RFC 1952) instead of text: one member per 32 KiB of text, each carrying the BGZF 'BC'

@@ -191,6 +191,9 @@ API = [
     ("pbsim_sam_header", C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64]),
     ("pbsim_set_bam_output", C.c_int, [C.c_void_p, C.c_int]),
     ("pbsim_bam_header", C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64]),
+    ("pbsim_set_truth_bam", C.c_int, [C.c_void_p, C.c_int]),
+    ("pbsim_truth_bam_header", C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64]),
+    ("pbsim_job_truth_bam_header", C.c_int64, [C.c_void_p, C.c_int64, C.c_char_p, C.c_int64]),
     ("pbsim_set_sample_profile", C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     ("pbsim_simulate_sample", C.c_int, [C.c_void_p, C.POINTER(Sink)]),
     ("pbsim_sample_profile_from_bytes", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.POINTER(SampleStats)]),
@@ -844,6 +847,24 @@ class Context:
         n = self.lib.pbsim_bam_header(self.h, None, 0)
         buf = C.create_string_buffer(n)
         self.lib.pbsim_bam_header(self.h, buf, n)
+        return buf.raw[:n]
+
+    def set_truth_bam(self, on=True):
+        """the MAF stream carries aligned BAM records (one per task) instead of MAF blocks"""
+        _check(self.lib.pbsim_set_truth_bam(self.h, 1 if on else 0))
+
+    def truth_bam_header(self):
+        n = self.lib.pbsim_truth_bam_header(self.h, None, 0)
+        buf = C.create_string_buffer(n)
+        self.lib.pbsim_truth_bam_header(self.h, buf, n)
+        return buf.raw[:n]
+
+    def job_truth_bam_header(self, record):
+        n = self.lib.pbsim_job_truth_bam_header(self.h, record, None, 0)
+        if n < 0:
+            raise PbsimError("no record %d in the job" % record)
+        buf = C.create_string_buffer(n)
+        self.lib.pbsim_job_truth_bam_header(self.h, record, buf, n)
         return buf.raw[:n]
 
     # ---- the whole job (pbsim_job_*)

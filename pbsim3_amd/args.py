@@ -70,3 +70,17 @@ def read_sample_fastq(path, len_min=100, len_max=1000000, acc_min=0.75, acc_max=
         if acc_min <= acc <= acc_max:
             out.append(q)
     return out
+
+
+def truth_format(a):
+    """--truth-format maf|bam from parse()'s raw options (default maf): what the truth file holds, MAF blocks or aligned BAM
+    records (pbsim_set_truth_bam).  argv-style flags without a value (--no-gzip, --samtools) are looked up as keys too.  The
+    combinations pbsim_cli_main refuses raise ValueError with its message."""
+    fmt = a.get("--truth-format", "maf")
+    if fmt not in ("maf", "bam"):
+        raise ValueError("--truth-format must be maf or bam")
+    if fmt == "bam":
+        for flag in ("--no-gzip", "--samtools"):
+            if flag in a:
+                raise ValueError("--truth-format bam cannot be combined with %s (the .aln.bam file is BGZF made on the GPU)" % flag)
+    return fmt

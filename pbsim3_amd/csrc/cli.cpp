@@ -52,6 +52,7 @@ struct Cli {
   bool no_gzip = false, use_samtools = false;
   bool gzip_on_gpu = true;  // --gzip gpu|host: where the .gz / BGZF members are produced
   int gzip_threads = 0;
+  bool truth_bam = false;   // --truth-format bam: <prefix>[_NNNN].aln.bam (aligned BAM records) instead of .maf.gz
 };
 
 // the reference's exit(-1).  Other ranks of the process may be inside HIP calls on their own threads: leave without running
@@ -124,6 +125,37 @@ void open_sink(const Cli &c, Out *o, const std::string &plain_name, const std::s
 }
 
 bool native_bam(const Cli &c) { return c.p.pass_num > 1 && !c.no_gzip && !c.use_samtools; }
+
+// --truth-format bam: the BAM header in front of the truth stream's records (`record`: genome.num of a job's record; a unit
+// that is not a record of the job -- trans / templ, the sampling method -- has the current unit's), as a gzip member of
+// its own where the members come from the GPU
+std::vector<char> truth_header_bytes(const Cli &c, pbsim_ctx *ctx, int64_t record) {
+  std::vector<char> h;
+  int64_t n = record > 0 ? pbsim_job_truth_bam_header(ctx, record, NULL, 0) : -1;
+  const bool job = n >= 0;
+  if (!job) n = pbsim_truth_bam_header(ctx, NULL, 0);
+  h.resize((size_t)n);
+  if (job) pbsim_job_truth_bam_header(ctx, record, h.data(), n);
+  else pbsim_truth_bam_header(ctx, h.data(), n);
+  if (c.gzip_on_gpu) {
+    std::vector<char> z((size_t)pbsim_deflate_bound(n) + 64);
+    int64_t k = 0;
+    if (!pbsim_deflate_buffer(ctx, h.data(), n, z.data(), (int64_t)z.size(), &k)) die(": %s", pbsim_last_error());
+    z.resize((size_t)k);
+    return z;
+  }
+  return h;
+}
+// the truth file of a unit, opened for a sequential consumer
+void open_truth_sink(const Cli &c, pbsim_ctx *ctx, Out *o, const std::string &stem, int64_t record) {
+  if (!c.truth_bam) {
+    open_sink(c, o, stem + ".maf", stem + ".maf.gz", false);
+    return;
+  }
+  open_sink(c, o, stem + ".aln.bam", stem + ".aln.bam", true);
+  const std::vector<char> h = truth_header_bytes(c, ctx, record);
+  o->write(h.data(), h.size());
+}
 
 bool is_regular_file(const char *file) {
   struct stat sb;
@@ -230,6 +262,7 @@ void print_help() {
           "  --length-mean (9000.0) --length-sd (7000.0) --accuracy-mean (0.85) --pass-num (1) --hp-del-bias (1)\n"
           "  --device N (0)   --devices a,b,.. (one rank per GPU)   --no-gzip (plain .fq/.maf/.sam instead of gzip/samtools pipes)\n"
           "  --gzip gpu|host (gpu)   --gzip-threads N (host)   --samtools (pipe SAM into samtools view -b)\n"
+          "  --truth-format maf|bam (maf): bam writes the truth alignments as <prefix>[_NNNN].aln.bam instead of .maf.gz\n"
           "  --genome, --transcript, --template and --sample may be gzip-compressed (recognised by content): BGZF is\n"
           "  inflated on the GPU, other gzip by zlib on the host; the whole inflated file is held in host memory\n\n");
 }
@@ -259,7 +292,8 @@ void parse_args(int argc, char **argv, Cli &c) {
       {"length-sd", 1, NULL, 0},  {"accuracy-mean", 1, NULL, 0}, {"pass-num", 1, NULL, 0},
       {"template", 1, NULL, 0},   {"hp-del-bias", 1, NULL, 0},   {"device", 1, NULL, 0},
       {"no-gzip", 0, NULL, 0},    {"gzip-threads", 1, NULL, 0}, {"gzip-file", 1, NULL, 0}, {"samtools", 0, NULL, 0},
-      {"gzip", 1, NULL, 0},       {"devices", 1, NULL, 0},      {"comm", 1, NULL, 0},          {0, 0, 0, 0}};
+      {"gzip", 1, NULL, 0},       {"devices", 1, NULL, 0},      {"comm", 1, NULL, 0},          {"truth-format", 1, NULL, 0},
+      {0, 0, 0, 0}};
   optind = 0;  // glibc: a full re-initialisation (this function runs once per rank)
   int opt, idx = 0;
   while ((opt = getopt_long(argc, argv, "", long_options, &idx)) != -1) {
@@ -356,6 +390,11 @@ void parse_args(int argc, char **argv, Cli &c) {
       else if (!strcmp(optarg, "host")) c.gzip_on_gpu = false;
       else die(" (gzip: %s): gpu or host.", optarg);
       break;
+    case 31:
+      if (!strcmp(optarg, "bam")) c.truth_bam = true;
+      else if (!strcmp(optarg, "maf")) c.truth_bam = false;
+      else die(" (truth-format: %s): maf or bam.", optarg);
+      break;
     case 29: case 30: break;  // --devices / --comm: main.cpp (one rank per GPU); a rank itself runs on `device`
     case 26: {  // utility/self-test: gzip FILE -> FILE.gz with the parallel writer, nothing else
       pbsim::ParallelGz gz;
@@ -376,6 +415,8 @@ void parse_args(int argc, char **argv, Cli &c) {
     print_help();
     quit(-1);
   }
+  if (c.truth_bam && c.no_gzip) die(": --truth-format bam writes BGZF (<prefix>.aln.bam): it cannot be combined with --no-gzip.");
+  if (c.truth_bam && c.use_samtools) die(": --truth-format bam makes its BAM records on the GPU: it cannot be combined with --samtools.");
   // ---- set_sim_param (pbsim.cpp:1451-1688)
   if (!c.set_flg[0] || !c.set_flg[1]) die(": --strategy and --method must be set.");
   if (c.p.strategy == PBSIM_STRATEGY_WGS && !c.set_flg[2]) die(": for --strategy wgs, --genome must be set.");
@@ -685,8 +726,9 @@ std::string read_name(const Cli &c, long n) {
 }
 std::string maf_name(const Cli &c, long n) {
   char name[4096];
-  snprintf(name, sizeof name, "%s_%04ld.maf", c.prefix.c_str(), n);
-  return std::string(name) + (c.no_gzip ? "" : ".gz");
+  snprintf(name, sizeof name, "%s_%04ld", c.prefix.c_str(), n);
+  if (c.truth_bam) return std::string(name) + ".aln.bam";
+  return std::string(name) + (c.no_gzip ? ".maf" : ".maf.gz");
 }
 
 // header bytes in front of the read stream (pbsim.cpp:721-722): SAM text, or the BAM header as a gzip member of its own
@@ -735,12 +777,15 @@ void open_record(JobFiles &jf, long n, bool creator) {
     }
   }
   if (rf.maf.positional) {
-    if (creator) rf.maf.pos.create(maf_name(c, n), nullptr, 0);
+    std::vector<char> h;
+    if (c.truth_bam) h = truth_header_bytes(c, jf.ctx, n);
+    rf.maf.pos.base = (int64_t)h.size();
+    if (creator) rf.maf.pos.create(maf_name(c, n), h.data(), (int64_t)h.size());
     else rf.maf.pos.attach(maf_name(c, n));
   } else if (creator) {
     char name[4096];
-    snprintf(name, sizeof name, "%s_%04ld.maf", c.prefix.c_str(), n);
-    open_sink(c, &rf.maf.seq, name, std::string(name) + ".gz", false);
+    snprintf(name, sizeof name, "%s_%04ld", c.prefix.c_str(), n);
+    open_truth_sink(c, jf.ctx, &rf.maf.seq, name, n);
   }
 }
 
@@ -758,7 +803,7 @@ int job_done(void *u, int64_t record, const pbsim_stats *st, int64_t read_bytes,
     if (s.positional) {
       // compressed streams end with the BGZF EOF marker when they are BAM, or when they would otherwise be empty files
       const bool members = !c.no_gzip;
-      const bool bam = which == 0 && c.p.pass_num > 1;
+      const bool bam = which == 0 ? c.p.pass_num > 1 : c.truth_bam;
       if (rank0 && members && (bam || s.pos.base + bytes == 0) &&
           !s.pos.write_at((const char *)kBgzfEof, sizeof kBgzfEof, s.pos.base + bytes))
         return 0;
@@ -894,6 +939,7 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
     check(c.p.method == PBSIM_METHOD_ERR ? pbsim_load_errhmm(ctx, c.model.c_str()) : pbsim_load_qshmm(ctx, c.model.c_str()));
   }
   if (native_bam(c)) check(pbsim_set_bam_output(ctx, 1));
+  if (c.truth_bam) check(pbsim_set_truth_bam(ctx, 1));
   if (!c.no_gzip && c.gzip_on_gpu) {  // bit 0: read sink, bit 1: MAF sink; a samtools pipe still wants SAM text
     // bit 2: the read file and the MAF file are written by two host threads (each Out is touched by one of them only)
     const char *one = getenv("PBSIM_CLI_ONE_WRITER");  // measurement knob: both files from the calling thread
@@ -1141,8 +1187,8 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
         open_sink(c, &o_read, std::string(name) + ".sam", std::string(name) + ".bam", true);
         write_read_header(c, ctx, &o_read, n);
       }
-      snprintf(name, sizeof name, "%s_%04ld.maf", c.prefix.c_str(), n);
-      open_sink(c, &o_maf, name, std::string(name) + ".gz", false);
+      snprintf(name, sizeof name, "%s_%04ld", c.prefix.c_str(), n);
+      open_truth_sink(c, ctx, &o_maf, name, 0);  // (the current unit's header: the record is no record of a job)
       Two two = {&o_read, &o_maf};
       pbsim_sink sink = {&two, cb_read, cb_maf};
       phase("record loaded, sinks open");
@@ -1200,7 +1246,7 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
         open_sink(c, &o_read, c.prefix + ".sam", c.prefix + ".bam", true);
         write_read_header(c, ctx, &o_read, 0);
       }
-      open_sink(c, &o_maf, c.prefix + ".maf", c.prefix + ".maf.gz", false);
+      open_truth_sink(c, ctx, &o_maf, c.prefix, 0);
       Two two = {&o_read, &o_maf};
       pbsim_sink sink = {&two, cb_read, cb_maf};
       check(pbsim_simulate_trans(ctx, &sink));
@@ -1226,7 +1272,9 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
       check(pbsim_stats_merge(ctx, comm));
       const bool bam = c.p.pass_num > 1;
       const std::string rname = c.prefix + (c.p.pass_num == 1 ? (c.no_gzip ? ".fq" : ".fq.gz") : (c.no_gzip ? ".sam" : ".bam"));
-      const std::string mname = c.prefix + (c.no_gzip ? ".maf" : ".maf.gz");
+      const std::string mname = c.prefix + (c.truth_bam ? ".aln.bam" : c.no_gzip ? ".maf" : ".maf.gz");
+      std::vector<char> hm;
+      if (c.truth_bam) hm = truth_header_bytes(c, ctx, 0);
       std::vector<char> h;
       if (bam) {
         if (native_bam(c)) {
@@ -1246,7 +1294,7 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
       const int64_t mine[2] = {(int64_t)buf_r.size(), (int64_t)buf_m.size()};
       std::vector<int64_t> all((size_t)world * 2);
       if (!comm->all_gather_i64(comm->user, mine, 2, all.data())) die(": communicator failed");
-      int64_t at_r = (int64_t)h.size(), at_m = 0, tot_r = (int64_t)h.size(), tot_m = 0;
+      int64_t at_r = (int64_t)h.size(), at_m = (int64_t)hm.size(), tot_r = (int64_t)h.size(), tot_m = (int64_t)hm.size();
       for (int q = 0; q < world; q++) {
         if (q < rank) {
           at_r += all[(size_t)q * 2];
@@ -1258,10 +1306,10 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
       PosFile fr, fm;
       if (rank0) {
         fr.create(rname, h.data(), (int64_t)h.size());
-        fm.create(mname, nullptr, 0);
+        fm.create(mname, hm.data(), (int64_t)hm.size());
         if (!c.no_gzip) {  // BAM: the BGZF end-of-file marker; .gz: an empty member keeps an empty output a valid gzip file
           if ((bam || tot_r == 0) && !fr.write_at((const char *)kBgzfEof, sizeof kBgzfEof, tot_r)) die(": write error on %s", rname.c_str());
-          if (tot_m == 0 && !fm.write_at((const char *)kBgzfEof, sizeof kBgzfEof, 0)) die(": write error on %s", mname.c_str());
+          if ((c.truth_bam || tot_m == 0) && !fm.write_at((const char *)kBgzfEof, sizeof kBgzfEof, tot_m)) die(": write error on %s", mname.c_str());
         }
       }
       barrier(comm);

@@ -266,6 +266,8 @@ struct Slot {
   DevBuf d_task_of_slot, d_slot_of_task, d_wave_cap, d_wave_off, d_wg_tmp, d_wg_order;
   DevBuf d_out_len, d_maf_len, d_nsub, d_nins, d_ndel, d_qsum;
   DevBuf d_cum, d_scan_tmp, d_rt_len, d_mt_len, d_row_dst;
+  DevBuf d_n_runs;                     // truth as BAM records: CIGAR runs per task (k_cigar_rows<false>)
+  hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;  // timing: around that count pass (it belongs to the text emission's time)
   DevBuf d_chain, d_chain_mask;        // a chain of truncated reads: ChainState; the step's view of task_of_slot
   DevBuf d_scratch, d_read_text, d_maf_text;
   HostBuf h_read_text, h_maf_text, h_stats, h_flags;
@@ -371,6 +373,9 @@ struct pbsim_ctx {
   bool defer_account = false;    // deliver() leaves the batch's statistics to its caller (units.cpp accounts batch k + 1 on a thread beside the delivery of batch k)
   int walk_lds_kb = 27;        // walk workgroups per CU: 27 KB -> five (batch primitives), 41 KB -> three (the job pipeline)
   bool bam_output = false;     // pass_num > 1: BAM records instead of SAM text
+  bool truth_bam = false;      // pbsim_set_truth_bam: the MAF stream carries aligned BAM records instead of MAF blocks
+  std::vector<std::string> unit_sn;  // trans / templ: the units' MAF names cut at the first whitespace byte (@SQ SN), load order
+  std::vector<int64_t> unit_ln;      // their lengths
   int deflate = 0;             // bit 0 / 1: read / MAF sink receives BGZF-framed gzip members (deflate.hip)
   bool deflate_parallel = false;  // pbsim_set_deflate bit 2: the two sinks are served from two host threads
   DevBuf d_df_tables;          // crc slice-by-4 tables [4][256] + x^(8*128*k) [256]
@@ -427,6 +432,10 @@ int finalize_cut(pbsim_ctx *c, int64_t len_total_before, pbsim_batch_info *out);
 int finalize_text(pbsim_ctx *c, pbsim_batch_info *info);
 int finalize_uncut(pbsim_ctx *c, pbsim_batch_info *out);
 std::string sam_header_text(const pbsim_ctx *c, int64_t unit);
+// pbsim_set_truth_bam: the BAM header of the truth stream (SAMv1 4.2) -- wgs: one reference "ref" of ref_len bases; trans /
+// templ: the loaded units -- and the check of the units' names against SAMv1's RNAME set (PBSIM_FAILED names the unit)
+std::string truth_bam_header_bytes(const pbsim_ctx *c, int64_t ref_len);
+int truth_bam_check_names(const pbsim_ctx *c);
 // pbsim.cpp:3986-4005 / 2293-2316 for the n_final reads of the selected slot's finalized batch, into `st`
 int account_slot(pbsim_ctx *c, StatsAcc *st);
 int account_of(pbsim_ctx *c, Slot &sl, StatsAcc *st);  // the same on an explicit slot (no use of the selected-slot cursor)

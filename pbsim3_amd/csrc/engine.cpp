@@ -21,6 +21,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "ctx.h"
@@ -274,6 +275,8 @@ pbsim_ctx *pbsim_create(const pbsim_params *p, int device) {
     (void)hipEventCreateWithFlags(&sl.ev_coop, hipEventDisableTiming);
     (void)hipEventCreateWithFlags(&sl.ev_text, hipEventDisableTiming);
     (void)hipEventCreate(&sl.ev_t0);
+    (void)hipEventCreate(&sl.ev_c0);
+    (void)hipEventCreate(&sl.ev_c1);
     (void)hipEventCreate(&sl.ev_t1);
     // (normal priority: streams of one priority share a few hardware queues, and a packet waits for the one in front of it in
     // its queue -- a 10 ms walk of long reads among the HIGH priority streams held up other slots' flag reads for 30 ms)
@@ -322,6 +325,8 @@ void pbsim_destroy(pbsim_ctx *c) {
     if (sl.ev_coop) (void)hipEventDestroy(sl.ev_coop);
     if (sl.ev_text) (void)hipEventDestroy(sl.ev_text);
     if (sl.ev_t0) (void)hipEventDestroy(sl.ev_t0);
+    if (sl.ev_c0) (void)hipEventDestroy(sl.ev_c0);
+    if (sl.ev_c1) (void)hipEventDestroy(sl.ev_c1);
     if (sl.ev_t1) (void)hipEventDestroy(sl.ev_t1);
   }
   for (auto &lane : c->df_streams)
@@ -1027,6 +1032,11 @@ static void fill_text_args(pbsim_ctx *c, TextArgs *t, int64_t n_emit) {
   memcpy(t->id_prefix, c->p.id_prefix, sizeof t->id_prefix);
   t->rq_len = snprintf(t->rq_text, sizeof t->rq_text, "%f", c->p.accuracy_mean);  // pbsim.cpp:4027
   t->bam = c->bam_output && c->p.pass_num > 1;
+  t->truth_bam = c->truth_bam;
+  t->nsub = c->s().d_nsub.as<int32_t>();
+  t->nins = c->s().d_nins.as<int32_t>();
+  t->ndel = c->s().d_ndel.as<int32_t>();
+  t->n_runs = c->s().d_n_runs.as<int32_t>();
   {
     const float f = strtof(t->rq_text, nullptr);
     memcpy(&t->rq_bits, &f, 4);
@@ -1116,6 +1126,8 @@ static void collect_text_timing(pbsim_ctx *c, Slot &sl) {
   sl.text_timed = false;
 }
 extern "C++" int pbsim::finalize_text(pbsim_ctx *c, pbsim_batch_info *info) {
+  // (units loaded after pbsim_set_truth_bam: their names are checked when the first batch is due)
+  if (c->truth_bam && !truth_bam_check_names(c)) return PBSIM_FAILED;
   DeviceFlags *flags = c->s().d_flags.as<DeviceFlags>();
   DeviceFlags f;
   pbsim_batch_info bi = c->s().b_info;
@@ -1132,14 +1144,28 @@ extern "C++" int pbsim::finalize_text(pbsim_ctx *c, pbsim_batch_info *info) {
     c->s().stats_fetched = c->defer_text_sync;
     if (c->defer_text_sync && !fetch_stats(c, c->s(), n_tasks)) return PBSIM_FAILED;
     HIP_OK(hipMemsetAsync(&flags->sums[1], 0, 5 * sizeof(int64_t), c->s().stream));
+    if (c->truth_bam) HIP_OK(c->s().d_n_runs.ensure(n_tasks * 4));
     TextArgs t;
     fill_text_args(c, &t, n_final);
+    if (c->truth_bam) {  // the record sizes depend on the CIGAR run counts
+      HIP_OK(hipEventRecord(c->s().ev_c0, c->s().stream));
+      launch_cigar_count(t, c->s().b_slots_max, flags, c->s().stream);
+      HIP_OK(hipEventRecord(c->s().ev_c1, c->s().stream));
+    }
     launch_text_sizes(t, flags, c->s().stream);
     launch_exclusive_scan_i64(t.read_text_len, t.read_text_len, n_tasks, c->s().d_scan_tmp.as<int64_t>(), &flags->sums[1],
                               c->s().stream);
     launch_exclusive_scan_i64(t.maf_text_len, t.maf_text_len, n_tasks, c->s().d_scan_tmp.as<int64_t>(), &flags->sums[2],
                               c->s().stream);
     if (!read_flags(c, &f)) return PBSIM_FAILED;
+    if (c->truth_bam) {  // (read_flags waited for the stream)
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, c->s().ev_c0, c->s().ev_c1) == hipSuccess) {
+        std::lock_guard<std::mutex> lk(c->prof_mu);
+        c->prof_text_ms += ms;
+        c->prof_text_in += 2 * f.sums[5];
+      }
+    }
     bi.read_text_bytes = f.sums[1];
     bi.maf_text_bytes = f.sums[2];
     bi.bases = f.sums[3];
@@ -1293,6 +1319,67 @@ int64_t pbsim_bam_header(pbsim_ctx *c, char *buf, int64_t cap) {
     memcpy(buf + 8 + lt, &zero, 4);
   }
   return n;
+}
+
+// ---- the truth stream as aligned BAM records
+static bool rname_ok(const std::string &s) {  // SAMv1 1.2.1: [0-9A-Za-z!#$%&+./:;?@^_|~-][0-9A-Za-z!#$%&*+./:;=?@^_|~-]*
+  if (s.empty()) return false;
+  for (size_t i = 0; i < s.size(); i++) {
+    const unsigned char ch = (unsigned char)s[i];
+    if (ch < '!' || ch > '~') return false;
+    if (strchr("\\,\"`'()[]{}<>", ch)) return false;
+    if (i == 0 && (ch == '*' || ch == '=')) return false;
+  }
+  return true;
+}
+extern "C++" int pbsim::truth_bam_check_names(const pbsim_ctx *c) {
+  if (c->p.strategy == PBSIM_STRATEGY_WGS) return PBSIM_SUCCEEDED;
+  std::unordered_map<std::string, size_t> seen;
+  for (size_t u = 0; u < c->unit_sn.size(); u++) {
+    const std::string &s = c->unit_sn[u];
+    const std::string which = "unit " + std::to_string(u + 1) + " ('" + s + "')";
+    if (s.empty()) return fail(("truth BAM: the name of " + which + " is empty up to its first whitespace").c_str());
+    if (!rname_ok(s)) return fail(("truth BAM: the name of " + which + " is not a reference name SAM allows").c_str());
+    const auto it = seen.find(s);
+    if (it != seen.end())
+      return fail(("truth BAM: the name of " + which + " is also that of unit " + std::to_string(it->second + 1)).c_str());
+    seen.emplace(s, u);
+  }
+  return PBSIM_SUCCEEDED;
+}
+extern "C++" std::string pbsim::truth_bam_header_bytes(const pbsim_ctx *c, int64_t ref_len) {
+  std::vector<std::pair<std::string, int64_t>> refs;
+  if (c->p.strategy == PBSIM_STRATEGY_WGS) {
+    refs.emplace_back("ref", ref_len);
+  } else {
+    for (size_t u = 0; u < c->unit_sn.size(); u++) refs.emplace_back(c->unit_sn[u], c->unit_ln[u]);
+  }
+  std::string text = "@HD\tVN:1.6\tSO:unknown\n";
+  for (const auto &r : refs) text += "@SQ\tSN:" + r.first + "\tLN:" + std::to_string((long long)r.second) + "\n";
+  text += std::string("@PG\tID:pbsim3_amd\tPN:pbsim3_amd\tVN:") + pbsim_version() + "\n";
+  std::string h = "BAM\1";
+  auto u32 = [&h](uint32_t v) { h.append(reinterpret_cast<const char *>(&v), 4); };
+  u32((uint32_t)text.size());
+  h += text;
+  u32((uint32_t)refs.size());
+  for (const auto &r : refs) {
+    u32((uint32_t)r.first.size() + 1);
+    h.append(r.first.c_str(), r.first.size() + 1);
+    u32((uint32_t)r.second);
+  }
+  return h;
+}
+int pbsim_set_truth_bam(pbsim_ctx *c, int on) {
+  if (!c) return fail("bad argument");
+  if (on && !truth_bam_check_names(c)) return PBSIM_FAILED;
+  c->truth_bam = on != 0;
+  return PBSIM_SUCCEEDED;
+}
+int64_t pbsim_truth_bam_header(pbsim_ctx *c, char *buf, int64_t cap) {
+  if (!c) return -1;
+  const std::string h = truth_bam_header_bytes(c, c->ref_len);
+  if (buf && cap >= (int64_t)h.size()) memcpy(buf, h.data(), h.size());
+  return (int64_t)h.size();
 }
 
 extern "C++" int pbsim::prepare_enqueue(pbsim_ctx *c, uint8_t *d_seq, DevBuf &hp, DevBuf &tiles, DevBuf &flags, int64_t len,

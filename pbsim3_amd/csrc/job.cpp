@@ -1398,6 +1398,22 @@ int64_t pbsim_job_bam_header(pbsim_ctx *c, int64_t record, char *buf, int64_t ca
   return n;
 }
 
+int64_t pbsim_job_truth_bam_header(pbsim_ctx *c, int64_t record, char *buf, int64_t cap) {
+  if (!c) return -1;
+  const int64_t i = record - c->job_first_unit;
+  int64_t len = 0;
+  {
+    std::lock_guard<std::mutex> lk(c->job_mu);
+    if (i < 0) return -1;
+    if (i < (int64_t)c->job_records.size()) len = c->job_records[(size_t)i]->len;
+    else if (i < (int64_t)c->job_expect_len.size()) len = c->job_expect_len[(size_t)i];
+    else return -1;
+  }
+  const std::string h = truth_bam_header_bytes(c, len);
+  if (buf && cap >= (int64_t)h.size()) memcpy(buf, h.data(), h.size());
+  return (int64_t)h.size();
+}
+
 int pbsim_job_breakdown(pbsim_ctx *c, double out[16]) {
   if (!c || !out) return fail("bad argument");
   memcpy(out, c->job_breakdown, sizeof c->job_breakdown);
@@ -1595,7 +1611,9 @@ static int job_run_impl(pbsim_ctx *c, const pbsim_comm *comm, const pbsim_record
       // bytes are delivered: bound the batch so that all of them fit 75 % of what the GPU has left
       // FASTQ 2.0 | SAM text ~6.1 | BAM records ~3.5 (bases 0.5, qualities 1, the ip and pw arrays 1 each); MAF 2.23; the text
       // buffers are grown with 12.5 % of slack (DevBuf::ensure)
-      const double text_per_base = 1.125 * (P > 1 ? (c->bam_output ? 5.8 : 8.4) : 4.25);
+      // the truth as BAM records: 0.5 packed bases + 1 quality + 4 bytes per CIGAR run (a run per ~5 columns at the shipped
+      // models' error rates; the exact sizes come from the count pass) ~ 2.4 in place of MAF's 2.23
+      const double text_per_base = 1.125 * ((P > 1 ? (c->bam_output ? 5.8 : 8.4) : 4.25) + (c->truth_bam ? 0.2 : 0.0));
       const double scratch_per_base = (double)regions * sf * 1.12 * 1.08 + 0.1;
       // (rounds in flight + one whose delivery is pending + one with the worker; nothing is held back when the text stays put)
       const bool delivering_text = J.sink && (J.sink->on_read_text || J.sink->on_maf_text);

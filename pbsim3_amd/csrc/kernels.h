@@ -196,6 +196,10 @@ struct TextArgs {
   const char *unit_names;       // [n_units][132] NUL-terminated ids
   int32_t name_pad3;            // templ: the name is the id but pads as "ref" (digit_num1[0] = 3, pbsim.cpp:5290)
   const uint8_t *read_minus;    // [n_reads] strand for trans (NULL for wgs)
+  // truth as aligned BAM records (pbsim_set_truth_bam): the MAF stream carries one placed record per task instead of a block
+  int32_t truth_bam;
+  const int32_t *nsub, *nins, *ndel;  // the walk's counters of each task (the NM tag)
+  int32_t *n_runs;              // [n_tasks] CIGAR runs of each task (k_cigar_rows<false>)
 };
 
 // pbsim_read_arrays (include/pbsim3_amd.h): device arrays of the final tasks, task t = read r, pass h at t = r * pass_num + h
@@ -278,6 +282,8 @@ void launch_gather_pass0_scan(const int32_t *out_len, int64_t n_reads, int32_t p
 // flags->n_final = first read r with  before+cum[r] >= quota  or  before+cum[r]+rawlen[r] > quota (else n_reads)
 void launch_quota_cut(const int64_t *cum, const int32_t *rawlen, int64_t n_reads, int64_t len_total_before,
                       int64_t quota, int force_all, DeviceFlags *flags, hipStream_t s);
+// a.truth_bam only, in front of launch_text_sizes: a.n_runs[t] = maximal M / I / D runs of task t's MAF columns
+void launch_cigar_count(const TextArgs &a, int64_t n_slots_max, const DeviceFlags *flags, hipStream_t s);
 void launch_text_sizes(const TextArgs &a, DeviceFlags *flags, hipStream_t s);
 void launch_text_emit(const TextArgs &a, int64_t n_slots_max, const DeviceFlags *flags, hipStream_t s);
 // the arrays of a batch: first the sizes (task_off = exclusive scan of out_len, total -> task_off[tasks]; flags->sums[3..5] +=

@@ -2749,6 +2749,26 @@ __device__ __forceinline__ int64_t bam_record_size(int idl, int q, int64_t readn
   return 4 + 32 + (idl + 1) + (q + 1) / 2 + q + tags;
 }
 
+// ---- aligned BAM records of the truth stream (pbsim_set_truth_bam): one placed record per task, SAMv1 4.2.  A CIGAR of
+// more than 65535 operations moves into a CG:B,I tag behind NM and leaves <q>S<span>N in its place (SAMv1 4.2.2).
+constexpr int kCigarMaxOps = 65535;
+__device__ __forceinline__ int64_t aln_record_size(int idl, int q, int n_runs, int64_t nm) {
+  const bool big = n_runs > kCigarMaxOps;
+  return 4 + 32 + (idl + 1) + 4LL * (big ? 2 : n_runs) + (q + 1) / 2 + q + 3 + bam_int_size(nm) + (big ? 8 + 4LL * n_runs : 0);
+}
+// SAMv1 5.3, reg2bin(beg, end) as the specification writes it
+__device__ __forceinline__ int aln_reg2bin(int64_t beg, int64_t end) {
+  --end;
+  if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
+  if (beg >> 17 == end >> 17) return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
+  if (beg >> 20 == end >> 20) return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
+  if (beg >> 23 == end >> 23) return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
+  if (beg >> 26 == end >> 26) return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
+  return 0;
+}
+
+// kTruth (the MAF stream carries BAM records, a.truth_bam): an instance of its own, so that the MAF instance stays the kernel it was
+template <bool kTruth>
 __global__ __launch_bounds__(256) void k_text_sizes(TextArgs a, DeviceFlags *flags) {
   short_kernel_priority();
   __shared__ unsigned long long s_sum[3];  // one global atomic per workgroup and counter: all tasks hit the same line
@@ -2773,8 +2793,9 @@ __global__ __launch_bounds__(256) void k_text_sizes(TextArgs a, DeviceFlags *fla
            PB_LEN(PB_SAM_T1) + dec_len((int64_t)q - 1) + PB_LEN(PB_SAM_T2) + a.rq_len + PB_LEN(PB_SAM_T3) +
            count_digit(x.readnum) + PB_LEN(PB_SAM_T4);
     }
-    const int64_t mt = (11LL + (x.name_len - x.r0) + x.w0 + x.w1 + x.w2 + x.w3 + m) +
-                       (10LL + x.idl + (x.w0 - x.q0) + x.w1 + x.w2 + x.w3 + m);
+    int64_t mt = (11LL + (x.name_len - x.r0) + x.w0 + x.w1 + x.w2 + x.w3 + m) +
+                 (10LL + x.idl + (x.w0 - x.q0) + x.w1 + x.w2 + x.w3 + m);
+    if (kTruth) mt = aln_record_size(x.idl, q, a.n_runs[t], (int64_t)a.nsub[t] + a.nins[t] + a.ndel[t]);
     a.read_text_len[t] = rt;
     a.maf_text_len[t] = mt;
     atomicAdd(&s_sum[0], (unsigned long long)q);
@@ -2796,6 +2817,7 @@ __device__ __forceinline__ char *g_pad(char *o, int n) {
   return o + (n > 0 ? n : 0);
 }
 
+template <bool kTruth>
 __global__ __launch_bounds__(256) void k_text_headers(TextArgs a) {
   short_kernel_priority();
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -2892,6 +2914,49 @@ __global__ __launch_bounds__(256) void k_text_headers(TextArgs a) {
     o = g_lit(o, PB_SAM_T3, PB_LEN(PB_SAM_T3));
     o += put_dec(o, readnum);
     o = g_lit(o, PB_SAM_T4, PB_LEN(PB_SAM_T4));
+  }
+
+  // ---------------- the truth as a placed BAM record instead of the MAF block ----------------
+  if (kTruth) {
+    const int n_runs = a.n_runs[t];
+    const int64_t nm = (int64_t)a.nsub[t] + a.nins[t] + a.ndel[t];
+    const bool big = n_runs > kCigarMaxOps;
+    const int64_t pos = a.off[r], span = a.len[r];  // the MAF reference line's start and size
+    const int bin = aln_reg2bin(pos, pos + span);
+    o = a.maf_text + a.maf_text_off[t];
+    o = bam_put_u32(o, (uint32_t)(aln_record_size(idl, q, n_runs, nm) - 4));  // block_size
+    o = bam_put_u32(o, a.read_unit ? (uint32_t)a.read_unit[r] : 0u);         // refID
+    o = bam_put_u32(o, (uint32_t)pos);
+    *o++ = (char)(idl + 1);                    // l_read_name
+    *o++ = 60;                                 // mapq
+    *o++ = (char)(bin & 0xff);
+    *o++ = (char)((bin >> 8) & 0xff);
+    *o++ = (char)((big ? 2 : n_runs) & 0xff);  // n_cigar_op
+    *o++ = (char)((big ? 2 : n_runs) >> 8);
+    *o++ = minus ? 16 : 0;                     // flag
+    *o++ = 0;
+    o = bam_put_u32(o, (uint32_t)q);           // l_seq
+    o = bam_put_u32(o, 0xffffffffu);           // next_refID
+    o = bam_put_u32(o, 0xffffffffu);           // next_pos
+    o = bam_put_u32(o, 0);                     // tlen
+    o = g_lit(o, idbuf, idl);
+    *o++ = 0;
+    if (big) {
+      o = bam_put_u32(o, ((uint32_t)q << 4) | 4u);     // <q>S
+      o = bam_put_u32(o, ((uint32_t)span << 4) | 3u);  // <span>N
+    } else {
+      rd[2] = o - a.maf_text;                  // the CIGAR (k_cigar_rows<true>)
+      o += 4LL * n_runs;
+    }
+    rd[3] = o - a.maf_text;                    // packed bases, then the qualities (k_aln_finish)
+    o += (q + 1) / 2 + q;
+    o = bam_put_int_tag(o, 'N', 'M', nm);
+    if (big) {
+      *o++ = 'C'; *o++ = 'G'; *o++ = 'B'; *o++ = 'I';
+      o = bam_put_u32(o, (uint32_t)n_runs);
+      rd[2] = o - a.maf_text;
+    }
+    return;
   }
 
   // ---------------- MAF (pbsim.cpp:4030-4078) ----------------
@@ -3165,6 +3230,9 @@ __device__ __forceinline__ SqueezeStep squeeze_window(char *dst_base, long long 
   return st;
 }
 
+// kMaf = false (the truth leaves as BAM records): no MAF lines, so no workgroups for the reference row either -- blockIdx.y 0
+// squeezes the read row, 1 the quality row.  The <true> instance is the kernel as it was.
+template <bool kMaf>
 __global__ __launch_bounds__(256) void k_text_rows(TextArgs a, const DeviceFlags *flags) {
   __shared__ uint32_t s_tile[64 * kTileStride + 4];  // + the dwords an aligned alignbyte of the last row reads past it
   __shared__ __attribute__((aligned(16))) uint32_t s_out[16 * kOutStride];  // one squeezed row per (wave, group)
@@ -3174,7 +3242,7 @@ __global__ __launch_bounds__(256) void k_text_rows(TextArgs a, const DeviceFlags
   __shared__ int s_minus[64];
   __shared__ long long s_dmaf[64], s_dsq[64];       // destination offsets of the task's MAF line / squeezed line
   const int64_t wave = blockIdx.x;
-  const int pass = blockIdx.y;
+  const int pass = kMaf ? (int)blockIdx.y : 2 * (int)blockIdx.y;
   short_kernel_priority();
   if (wave * 64 >= flags->total_slots) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -3255,11 +3323,11 @@ __global__ __launch_bounds__(256) void k_text_rows(TextArgs a, const DeviceFlags
       const int m = s_m[j], minus = s_minus[j];
       const bool act = task >= 0 && s0 < m;
       const uint32_t *trow = tile + i * kTileStride;
-      if (pass == 1) {
+      if (kMaf && pass == 1) {
         if (act) write_maf_tile(a.maf_text, s_dmaf[j], m, t, trow, minus, false, sub);
         continue;
       }
-      if (pass == 0 && act) write_maf_tile(a.maf_text, s_dmaf[j], m, t, trow, minus, true, sub);
+      if (kMaf && pass == 0 && act) write_maf_tile(a.maf_text, s_dmaf[j], m, t, trow, minus, true, sub);
       // the read bases (pass 0) / the qualities (pass 2): the columns whose byte is not 0
       const int ncol = act ? ((m - s0 < 256) ? m - s0 : 256) : 0;
       squeeze_window<false>(a.read_text, s_dsq[j], trow, ncol, act, s0 + 256 >= m, sub, lane, outb, s_sel, s_pend + j * 4, s_done + j);
@@ -3392,6 +3460,216 @@ __global__ __launch_bounds__(256) void k_bam_finish(TextArgs a) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   fill_run(reinterpret_cast<char *>(pw), q, 9, 9, lane);  // every lane has read its bases: the pw array takes its values
+}
+
+// ---------------------------------------------------------------------------
+// The truth as aligned BAM records: CIGAR, then SEQ / QUAL.
+// ---------------------------------------------------------------------------
+// One workgroup per scratch wave, the tile loader of k_text_rows on BOTH MAF rows at once: loader lane (lt, lc) holds columns
+// 64 lc .. 64 lc + 63 of a 256-column window of task lt, which it reduces to two 64-bit gap masks (I: '-' on the reference
+// row, D: 0 on the read row; neither: M).  A column starts a run when its class differs from the column's in front of it
+// (popc of mask ^ shifted mask); the class of a lane's column -1 comes from the lane 16 below, across windows from the
+// task's last lane of the window before.  No LDS on the way: the four lanes of a task talk through shuffles.
+//   kWrite = false  n_runs[task] = run starts of the task (the record sizes depend on it)
+//   kWrite = true   every run leaves as len << 4 | op when it ENDS (at the next start, or with the row): its index is the count
+//                   of starts in front of it, its first column the last start in front (both carried from lane to lane and
+//                   window to window).  The scratch rows are in read orientation, the record in reference orientation: a '-'
+//                   task's run i goes to slot n_runs - 1 - i.  The values leave as dwords (a record's CIGAR sits at a byte
+//                   offset; a lane's consecutive runs are consecutive dwords).
+template <bool kWrite>
+__global__ __launch_bounds__(256) void k_cigar_rows(TextArgs a, const DeviceFlags *flags) {
+  __shared__ int s_m[64], s_task[64], s_minus[64], s_nrun[64];
+  __shared__ long long s_dst[64];
+  const int64_t wave = blockIdx.x;
+  short_kernel_priority();
+  if (wave * 64 >= flags->total_slots) return;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (tid < 64) {
+    const int task = a.task_of_slot[wave * 64 + tid];
+    int m = 0, minus = 0, tk = -1, nrun = 0;
+    long long dst = 0;
+    if (task >= 0) {
+      const int64_t r = task / a.pass_num;
+      if (r < a.n_reads) {
+        const int64_t readnum = a.first_read + r;
+        minus = a.read_minus ? (a.read_minus[r] != 0) : ((readnum & 1) == 0);
+        m = a.maf_len[task];
+        tk = task;
+        if (kWrite) {
+          dst = a.row_dst[(int64_t)task * 6 + 2];
+          nrun = a.n_runs[task];
+        }
+      }
+    }
+    s_m[tid] = m;
+    s_task[tid] = tk;
+    s_minus[tid] = minus;
+    s_nrun[tid] = nrun;
+    s_dst[tid] = dst;
+  }
+  __syncthreads();
+  const int lt = lane & 15, lc = lane >> 4;  // task-in-wave, which 64 columns of the window
+  const int j = wv * 16 + lt;
+  const int m = s_m[j], task = s_task[j];
+  int mmax = 0;
+  {
+    int v = (task >= 0) ? m : 0;
+#pragma unroll
+    for (int d = 8; d > 0; d >>= 1) {
+      const int t = __shfl_xor(v, d, 64);
+      v = (t > v) ? t : v;
+    }
+    mmax = __shfl(v, 0, 64);
+  }
+  int runs = 0;  // run starts of the task in front of the window (the same in its four lanes)
+  if (mmax > 0) {
+    const int cap_raw = __builtin_amdgcn_readfirstlane(a.wave_cap[wave]);
+    const int cap_dw = cap_raw & ~kWaveTransposed;
+    const bool transposed = (cap_raw & kWaveTransposed) != 0;
+    const uint8_t *wave_rows = a.scratch + a.wave_off[wave];
+    const RowLane rq = row_lane(reinterpret_cast<const uint32_t *>(wave_rows), transposed, cap_dw, wv, lt, lc);
+    const RowLane rr = row_lane(reinterpret_cast<const uint32_t *>(wave_rows + (size_t)cap_dw * 256), transposed, cap_dw, wv, lt, lc);
+    const int minus = s_minus[j], nrun = s_nrun[j];
+    char *cig = a.maf_text + s_dst[j];
+    uint32_t pre_q[16], pre_r[16];
+    tile_fetch(pre_q, rq, 0);
+    tile_fetch(pre_r, rr, 0);
+    uint32_t tile_cls = 0;  // class of the task's last column of the window before: bit 0 I, bit 1 D
+    int tile_open = 0;      // first column of the run that is open at the window's first column
+    for (int s0 = 0; s0 < mmax; s0 += 256) {
+      unsigned long long gi = 0, gd = 0;
+#pragma unroll
+      for (int c = 0; c < 16; ++c) {
+        const uint32_t ni = eq_bytes(pre_r[c], 0x2Du), nd = eq_bytes(pre_q[c], 0u);
+        gi |= (unsigned long long)((((ni >> 7) * 0x00204081u) >> 21) & 15u) << (4 * c);
+        gd |= (unsigned long long)((((nd >> 7) * 0x00204081u) >> 21) & 15u) << (4 * c);
+      }
+      if (s0 + 256 < mmax) {
+        tile_fetch(pre_q, rq, (s0 + 256) >> 2);
+        tile_fetch(pre_r, rr, (s0 + 256) >> 2);
+      }
+      const int base = s0 + 64 * lc;
+      const int nv = m - base;  // valid columns of this lane
+      const unsigned long long valid = (nv >= 64) ? ~0ull : (nv > 0 ? (1ull << nv) - 1ull : 0ull);
+      const uint32_t last_cls = (uint32_t)(gi >> 63) | ((uint32_t)(gd >> 63) << 1);
+      const uint32_t below_cls = __shfl_up(last_cls, 16, 64);
+      const uint32_t prev_cls = (lc == 0) ? tile_cls : below_cls;
+      tile_cls = __shfl(last_cls, 48 + lt, 64);
+      unsigned long long st = (gi ^ ((gi << 1) | (prev_cls & 1u))) | (gd ^ ((gd << 1) | (prev_cls >> 1)));
+      if (base == 0) st |= 1ull;  // column 0 starts the first run
+      st &= valid;
+      const int cnt = __popcll(st);
+      const int c1 = __shfl_up(cnt, 16, 64), c2 = __shfl_up(cnt, 32, 64), c3 = __shfl_up(cnt, 48, 64);
+      const int excl = (lc >= 1 ? c1 : 0) + (lc >= 2 ? c2 : 0) + (lc >= 3 ? c3 : 0);
+      const int total = __shfl(excl + cnt, 48 + lt, 64);
+      if (kWrite) {
+        const int ls = st ? base + 63 - __clzll((long long)st) : -1;  // the lane's last start
+        const int l1 = __shfl_up(ls, 16, 64), l2 = __shfl_up(ls, 32, 64), l3 = __shfl_up(ls, 48, 64);
+        int open = tile_open;
+        open = (lc >= 1 && l1 > open) ? l1 : open;
+        open = (lc >= 2 && l2 > open) ? l2 : open;
+        open = (lc >= 3 && l3 > open) ? l3 : open;
+        tile_open = __shfl(ls > open ? ls : open, 48 + lt, 64);
+        int idx = runs + excl - 1;  // the run open at the lane's first column
+        int cur_start = open;
+        uint32_t cur_cls = prev_cls;
+        auto emit = [&](int i, uint32_t cls, int len) {
+          const uint32_t v = ((uint32_t)len << 4) | ((cls & 1u) ? 1u : (cls & 2u) ? 2u : 0u);  // M 0, I 1, D 2
+          const int slot = minus ? nrun - 1 - i : i;
+          if ((unsigned)slot < (unsigned)nrun) __builtin_memcpy(cig + 4LL * slot, &v, 4);  // (never outside the record)
+        };
+        for (unsigned long long k = st; k; k &= k - 1) {
+          const int b = __builtin_ctzll(k), col = base + b;
+          if (col > 0) emit(idx, cur_cls, col - cur_start);
+          idx++;
+          cur_start = col;
+          cur_cls = (uint32_t)((gi >> b) & 1ull) | ((uint32_t)((gd >> b) & 1ull) << 1);
+        }
+        if (nv > 0 && nv <= 64) emit(idx, cur_cls, m - cur_start);  // the row ends in this lane
+      }
+      runs += total;
+    }
+  }
+  if (!kWrite && lc == 0 && task >= 0) a.n_runs[task] = runs;
+}
+
+// One wave per task, after the rows: SEQ and QUAL of the task's record from the bases and qualities that k_text_rows squeezed
+// into the READ stream (FASTQ / SAM lines; BAM: the bases parked in the pw array, before k_bam_finish packs them).  Those are
+// in read orientation; the record is in reference orientation, so a '-' task reads from the far end, bytes swapped and
+// complemented.  16-byte stores at the destination's alignment, the source as aligned dwords shifted into place (k_bam_finish).
+__global__ __launch_bounds__(256) void k_aln_finish(TextArgs a) {
+  short_kernel_priority();
+  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (t >= a.n_reads * a.pass_num) return;
+  const int64_t r = t / a.pass_num;
+  const bool minus = a.read_minus ? (a.read_minus[r] != 0) : (((a.first_read + r) & 1) == 0);
+  const int q = a.out_len[t];
+  const int64_t *rd = a.row_dst + t * 6;
+  const uint8_t *src = reinterpret_cast<const uint8_t *>(a.read_text) + rd[a.bam ? 5 : 0];
+  const uint8_t *qsrc = reinterpret_cast<const uint8_t *>(a.read_text) + rd[1];
+  uint8_t *seq = reinterpret_cast<uint8_t *>(a.maf_text) + rd[3];
+  uint8_t *qual = seq + (q + 1) / 2;
+  auto base_at = [&](int jb) -> uint32_t { return minus ? complement(src[q - 1 - jb]) : (uint32_t)src[jb]; };
+  {
+    const int nfull = q >> 1;
+    const int head = min(nfull, (int)((16 - (reinterpret_cast<uintptr_t>(seq) & 15)) & 15));
+    if (lane < head) seq[lane] = (uint8_t)((bam_base_code(base_at(2 * lane)) << 4) | bam_base_code(base_at(2 * lane + 1)));
+    const int nvec = (nfull - head) >> 4;
+    uint4 *d16 = reinterpret_cast<uint4 *>(seq + head);
+    for (int v = lane; v < nvec; v += 64) {
+      const int j0 = 2 * (head + 16 * v);  // first of the 32 bases, in record order
+      const uint8_t *s = minus ? src + (q - j0 - 32) : src + j0;
+      const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(s) & 3);
+      const uint32_t *p = reinterpret_cast<const uint32_t *>(s - sh);
+      uint32_t in[9], w[8];
+#pragma unroll
+      for (int k = 0; k < 9; k++) in[k] = p[k];
+#pragma unroll
+      for (int k = 0; k < 8; k++) w[k] = __builtin_amdgcn_alignbyte(in[k + 1], in[k], sh);
+      uint32_t o[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const uint32_t w0 = minus ? complement4(__builtin_amdgcn_perm(0u, w[7 - 2 * k], 0x00010203u)) : w[2 * k];
+        const uint32_t w1 = minus ? complement4(__builtin_amdgcn_perm(0u, w[6 - 2 * k], 0x00010203u)) : w[2 * k + 1];
+        o[k] = bam_pack4(w0) | (bam_pack4(w1) << 16);
+      }
+      d16[v] = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+    const int done = head + 16 * nvec;
+    for (int i = done + lane; i < (q + 1) / 2; i += 64) {
+      const uint32_t hi = bam_base_code(base_at(2 * i));
+      const uint32_t lo = (2 * i + 1 < q) ? bam_base_code(base_at(2 * i + 1)) : 0u;
+      seq[i] = (uint8_t)((hi << 4) | lo);
+    }
+  }
+  if (!a.is_qs) {  // ERRHMM: a line of '!' (pbsim.cpp:4007-4010) = phred 0
+    fill_run(reinterpret_cast<char *>(qual), q, 0, 0, lane);
+    return;
+  }
+  {
+    const int head = min(q, (int)((16 - (reinterpret_cast<uintptr_t>(qual) & 15)) & 15));
+    if (lane < head) qual[lane] = (uint8_t)(qsrc[minus ? q - 1 - lane : lane] - 33u);
+    const int nvec = (q - head) >> 4;
+    uint4 *d16 = reinterpret_cast<uint4 *>(qual + head);
+    for (int v = lane; v < nvec; v += 64) {
+      const int j0 = head + 16 * v;
+      const uint8_t *s = minus ? qsrc + (q - j0 - 16) : qsrc + j0;
+      const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(s) & 3);
+      const uint32_t *p = reinterpret_cast<const uint32_t *>(s - sh);
+      uint32_t in[5], w[4];
+#pragma unroll
+      for (int k = 0; k < 5; k++) in[k] = p[k];
+#pragma unroll
+      for (int k = 0; k < 4; k++) w[k] = __builtin_amdgcn_alignbyte(in[k + 1], in[k], sh);
+      uint32_t o[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) o[k] = (minus ? __builtin_amdgcn_perm(0u, w[3 - k], 0x00010203u) : w[k]) - 0x21212121u;
+      d16[v] = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+    const int done = head + 16 * nvec;
+    if (lane < q - done) qual[done + lane] = (uint8_t)(qsrc[minus ? q - 1 - (done + lane) : done + lane] - 33u);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -3770,18 +4048,31 @@ void launch_gather_pass0_scan(const int32_t *out_len, int64_t n_reads, int32_t p
   launch_exclusive_scan_i64(cum, cum, n_reads, tmp, total, s);
 }
 
+void launch_cigar_count(const TextArgs &a, int64_t n_slots_max, const DeviceFlags *flags, hipStream_t s) {
+  if (a.n_reads * a.pass_num <= 0) return;
+  hipLaunchKernelGGL(k_cigar_rows<false>, dim3((unsigned)(n_slots_max / 64)), dim3(256), 0, s, a, flags);
+}
+
 void launch_text_sizes(const TextArgs &a, DeviceFlags *flags, hipStream_t s) {
   const int64_t n_tasks = a.n_reads * a.pass_num;
   if (n_tasks <= 0) return;
-  hipLaunchKernelGGL(k_text_sizes, dim3(blocks_for(n_tasks, 256)), dim3(256), 0, s, a, flags);
+  if (a.truth_bam) hipLaunchKernelGGL(k_text_sizes<true>, dim3(blocks_for(n_tasks, 256)), dim3(256), 0, s, a, flags);
+  else hipLaunchKernelGGL(k_text_sizes<false>, dim3(blocks_for(n_tasks, 256)), dim3(256), 0, s, a, flags);
 }
 
 void launch_text_emit(const TextArgs &a, int64_t n_slots_max, const DeviceFlags *flags, hipStream_t s) {
   const int64_t n_tasks = a.n_reads * a.pass_num;
   if (n_tasks <= 0) return;
-  hipLaunchKernelGGL(k_text_headers, dim3(blocks_for(n_tasks, 256)), dim3(256), 0, s, a);
+  if (a.truth_bam) hipLaunchKernelGGL(k_text_headers<true>, dim3(blocks_for(n_tasks, 256)), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_text_headers<false>, dim3(blocks_for(n_tasks, 256)), dim3(256), 0, s, a);
   if (!a.is_qs || a.pass_num > 1) hipLaunchKernelGGL(k_text_fill, dim3(blocks_for(n_tasks, 4)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_text_rows, dim3((unsigned)(n_slots_max / 64), a.is_qs ? 3 : 2), dim3(256), 0, s, a, flags);
+  if (a.truth_bam) {
+    hipLaunchKernelGGL(k_text_rows<false>, dim3((unsigned)(n_slots_max / 64), a.is_qs ? 2 : 1), dim3(256), 0, s, a, flags);
+    hipLaunchKernelGGL(k_cigar_rows<true>, dim3((unsigned)(n_slots_max / 64)), dim3(256), 0, s, a, flags);
+    hipLaunchKernelGGL(k_aln_finish, dim3(blocks_for(n_tasks, 4)), dim3(256), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(k_text_rows<true>, dim3((unsigned)(n_slots_max / 64), a.is_qs ? 3 : 2), dim3(256), 0, s, a, flags);
+  }
   if (a.bam) hipLaunchKernelGGL(k_bam_finish, dim3(blocks_for(n_tasks, 4)), dim3(256), 0, s, a);
 }
 

@@ -1,6 +1,7 @@
 // units.cpp -- the trans and templ strategies behind the C ABI (simulate_by_*_trans pbsim.cpp:4428-4770 / 2738-3017,
 // simulate_by_*_templ :5055-5362): all units resident as one buffer, a fixed read count per unit (no quota), reads numbered
 // globally; the drivers and the unit-file loaders.  Split out of engine.cpp in round 5; the batch machinery stays there.
+#include <ctype.h>
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -138,6 +139,14 @@ static int set_units(pbsim_ctx *c, int64_t n, const char *const *ids, const int6
   c->unit = 0;
   c->n_units = n;
   c->trans_reads = reads;
+  c->unit_sn.clear();
+  c->unit_ln.assign(lens, lens + n);
+  for (int64_t u = 0; u < n; u++) {  // the name a FASTA indexer keeps: up to the first whitespace byte
+    const char *nm = &names[(size_t)u * 132];
+    size_t k = 0;
+    while (nm[k] && !isspace((unsigned char)nm[k])) k++;
+    c->unit_sn.emplace_back(nm, k);
+  }
   for (Slot &sl : c->slots) sl.b_enqueued = sl.b_walked = sl.b_finalized = false;
   return PBSIM_SUCCEEDED;
 }
