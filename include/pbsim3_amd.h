@@ -302,6 +302,38 @@ int pbsim_deflate_buffer(pbsim_ctx *ctx, const void *src, int64_t n, void *dst, 
  * tables-only context give PBSIM_FAILED, and the context stays usable. */
 int64_t pbsim_inflate_bound(const void *src, int64_t n);
 int pbsim_inflate_buffer(pbsim_ctx *ctx, const void *src, int64_t n, void *dst, int64_t cap, int64_t *out_bytes);
+/* A finished truth BAM, sorted by coordinate and indexed on the GPU: what `samtools sort` and `samtools index -c` would make of
+ * a file of pbsim_set_truth_bam's records.  bam[0..n) is the whole file: BGZF members of any legal size, "BAM\1", header text,
+ * reference list, then records that are all placed and single-end (0 <= refID < n_ref, pos >= 0, next_refID = next_pos = -1,
+ * tlen = 0); anything else fails with a message that names the inflated byte offset of the first record that does not fit.
+ * The file is inflated into HBM, every byte position is tested against those fields in parallel, the host walks the
+ * block_size chain over the hits (that walk alone decides what a record is), the records are sorted by (refID, pos) -- stable:
+ * ties keep their input order, so the output is a function of the input alone -- and gathered into a second stream, which leaves
+ * as BGZF members of 32 KiB of text behind a header that differs in one place: its @HD line says SO:coordinate (the SO: value
+ * replaced; "@HD\tVN:1.6\tSO:coordinate\n" in front of a text without @HD; l_text adjusted).  The header is compressed as
+ * members of its own, the file ends with the BGZF EOF block, and the 16-bit bin fields of the records stay as they are.
+ * on_bam receives the sorted file piece by piece in offset order; on_index then the whole .csi file, once: CSIv1, BGZF with
+ * EOF block, min_shift 14, depth the smallest value >= 5 with 2^(14 + 3 depth) >= the longest reference, l_aux 0, the trailing
+ * n_no_coor (0) present.  A record's bin is reg2bin(pos, end, 14, depth) of the CSI specification, end = pos + the reference
+ * span of its CIGAR (M D N = X; a span of 0 counts as 1; a <q>S<span>N record takes its span from the N).  A bin's chunks are
+ * the maximal runs of records, consecutive in file order on that reference, that have the bin -- one chunk per run, not merged
+ * further -- from the virtual offset of the run's first record to that of the record behind its last (the EOF block's
+ * coffset << 16 behind the file's last record); a virtual offset is (offset of the member that holds the record's first
+ * byte) << 16 | offset in that member's text.  loffset of a bin that covers [s, s + len) is the virtual offset of the first
+ * record in file order on that reference with end > s.  Bins ascend by number, chunks keep file order; a reference with
+ * records ends with the pseudo-bin ((1 << 3 (depth + 1)) - 1) / 7 + 1: loffset 0, two chunks (first record's offset, end of
+ * the last; n_mapped = its record count, n_unmapped = 0); a reference without records has n_bin = 0.
+ * stats (may be NULL): records, references with records, inflated record bytes, index bins (pseudo-bins not counted).
+ * A callback that returns 0 aborts the call.  The stage holds the inflated stream, the sorted stream and their compressed
+ * pieces in HBM at once and does not chunk: a file that does not fit fails with the bytes the refused allocation needed.
+ * A tables-only context fails as pbsim_inflate_buffer does.  After any failure the context stays usable and on_index has not
+ * been called. */
+typedef struct pbsim_sorted_bam_sink {
+  void *user;
+  int (*on_bam)(void *user, const char *bytes, int64_t n, int64_t offset); /* the sorted file, in offset order */
+  int (*on_index)(void *user, const char *bytes, int64_t n);               /* the .csi file, once, whole */
+} pbsim_sorted_bam_sink;
+int pbsim_truth_bam_sort(pbsim_ctx *ctx, const void *bam, int64_t n, const pbsim_sorted_bam_sink *sink, int64_t stats[4]);
 
 /* ---- batch primitives (used by the drivers above, bench.py, multi-GPU) ------
  * pbsim_batch_walk     header draw + bucketing + HMM walk of reads

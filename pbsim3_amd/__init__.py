@@ -130,6 +130,14 @@ class RecordSink(C.Structure):
                 ("on_record_done", REC_DONE_CB)]
 
 
+SORTED_BAM_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64)
+SORTED_INDEX_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
+
+
+class SortedBamSink(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("on_bam", SORTED_BAM_CB), ("on_index", SORTED_INDEX_CB)]
+
+
 # every symbol include/pbsim3_amd.h declares: (name, restype, argtypes)
 API = [
     ("pbsim_job_add_record", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
@@ -209,6 +217,7 @@ API = [
     ("pbsim_deflate_buffer", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_inflate_bound", C.c_int64, [C.c_void_p, C.c_int64]),
     ("pbsim_inflate_buffer", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("pbsim_truth_bam_sort", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(SortedBamSink), C.POINTER(C.c_int64)]),
     ("pbsim_batch_walk", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_slot_count", C.c_int, []),
     ("pbsim_select_slot", C.c_int, [C.c_void_p, C.c_int]),
@@ -730,6 +739,29 @@ class Context:
         n = C.c_int64(0)
         _check(self.lib.pbsim_inflate_buffer(self.h, data, len(data), dst, cap, C.byref(n)))
         return dst.raw[:n.value]
+
+    def sort_truth_bam(self, data, on_index=None):
+        """A finished truth BAM (the bytes of a --truth-format bam file) -> (the coordinate-sorted BAM, its .csi index,
+        (records, references with records, inflated record bytes, index bins)): pbsim_truth_bam_sort.  `on_index`
+        (optional) is called when the index arrives -- after the last piece of the BAM, and never when the call fails."""
+        parts, index, at = [], [], [0]
+
+        def on_bam(user, ptr, n, offset):
+            if offset != at[0]:      # (the pieces come in offset order)
+                return 0
+            parts.append(C.string_at(ptr, n))
+            at[0] += n
+            return 1
+
+        def on_idx(user, ptr, n):
+            index.append(C.string_at(ptr, n))
+            if on_index:
+                on_index(index[-1])
+            return 1
+        sink = SortedBamSink(None, SORTED_BAM_CB(on_bam), SORTED_INDEX_CB(on_idx))
+        stats = (C.c_int64 * 4)()
+        _check(self.lib.pbsim_truth_bam_sort(self.h, bytes(data), len(data), C.byref(sink), stats))
+        return b"".join(parts), b"".join(index), tuple(stats)
 
     def set_transcripts(self, ids, plus, minus, seqs):
         """ids: list[str]; plus/minus: expression counts; seqs: list[bytes]."""

@@ -84,3 +84,17 @@ def truth_format(a):
             if flag in a:
                 raise ValueError("--truth-format bam cannot be combined with %s (the .aln.bam file is BGZF made on the GPU)" % flag)
     return fmt
+
+
+def truth_sort(a):
+    """--truth-sort coordinate from parse()'s raw options (default: None, the truth file stays in task order): the finished
+    <prefix>[_NNNN].aln.bam files are sorted by coordinate and indexed (pbsim_truth_bam_sort).  Valid only with --truth-format
+    bam; what pbsim_cli_main refuses raises ValueError with its message."""
+    how = a.get("--truth-sort")
+    if how is None:
+        return None
+    if how != "coordinate":
+        raise ValueError("--truth-sort must be coordinate")
+    if truth_format(a) != "bam":
+        raise ValueError("--truth-sort coordinate sorts the .aln.bam file: it needs --truth-format bam")
+    return how

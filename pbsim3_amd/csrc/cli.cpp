@@ -6,7 +6,9 @@
 // the text plainly to <prefix>_NNNN.{fq,maf,sam}), --gzip gpu|host, --gzip-threads N, --samtools.  Instead of one `gzip`
 // child per file, the .fq.gz/.maf.gz/.bam bytes are compressed on the GPU (deflate.hip: BGZF-framed gzip members, only
 // compressed bytes cross PCIe) and written here; --gzip host uses the in-process multi-threaded zlib writer (gzout.h);
-// --samtools pipes SAM text into `samtools view -b` like the reference.
+// --samtools pipes SAM text into `samtools view -b` like the reference.  --truth-format bam writes the truth as aligned BAM;
+// --truth-sort coordinate then sorts and indexes each finished <prefix>[_NNNN].aln.bam on the GPU (pbsim_truth_bam_sort), and
+// `pbsim --sort-truth-bam FILE ...` does that alone for files made earlier.
 //
 // wgs (errhmm / qshmm) runs as ONE job over all records (pbsim_job_run): the records are resident in HBM, and on several
 // ranks every rank pwrite()s its own byte ranges of the final files.  Rank 0 alone prints and creates files.
@@ -43,7 +45,7 @@
 namespace {
 
 struct Cli {
-  int set_flg[32] = {0};
+  int set_flg[40] = {0};
   pbsim_params p;
   std::string genome, transcript, templ, prefix = "sd", model, sample, profile_id;
   bool sam_store = false, sam_reuse = false;  // METHOD_SAM_STORE / METHOD_SAM_REUSE (pbsim.cpp:40-41, 1567-1580)
@@ -53,6 +55,7 @@ struct Cli {
   bool gzip_on_gpu = true;  // --gzip gpu|host: where the .gz / BGZF members are produced
   int gzip_threads = 0;
   bool truth_bam = false;   // --truth-format bam: <prefix>[_NNNN].aln.bam (aligned BAM records) instead of .maf.gz
+  bool truth_sort = false;  // --truth-sort coordinate: each finished .aln.bam sorted by coordinate, with a .csi beside it
 };
 
 // the reference's exit(-1).  Other ranks of the process may be inside HIP calls on their own threads: leave without running
@@ -263,6 +266,8 @@ void print_help() {
           "  --device N (0)   --devices a,b,.. (one rank per GPU)   --no-gzip (plain .fq/.maf/.sam instead of gzip/samtools pipes)\n"
           "  --gzip gpu|host (gpu)   --gzip-threads N (host)   --samtools (pipe SAM into samtools view -b)\n"
           "  --truth-format maf|bam (maf): bam writes the truth alignments as <prefix>[_NNNN].aln.bam instead of .maf.gz\n"
+          "  --truth-sort coordinate (with --truth-format bam): each finished .aln.bam is sorted by coordinate on the GPU\n"
+          "  and indexed (<name>.aln.bam.csi); pbsim --sort-truth-bam FILE [FILE ...] does the same for files made earlier\n"
           "  --genome, --transcript, --template and --sample may be gzip-compressed (recognised by content): BGZF is\n"
           "  inflated on the GPU, other gzip by zlib on the host; the whole inflated file is held in host memory\n\n");
 }
@@ -293,6 +298,7 @@ void parse_args(int argc, char **argv, Cli &c) {
       {"template", 1, NULL, 0},   {"hp-del-bias", 1, NULL, 0},   {"device", 1, NULL, 0},
       {"no-gzip", 0, NULL, 0},    {"gzip-threads", 1, NULL, 0}, {"gzip-file", 1, NULL, 0}, {"samtools", 0, NULL, 0},
       {"gzip", 1, NULL, 0},       {"devices", 1, NULL, 0},      {"comm", 1, NULL, 0},          {"truth-format", 1, NULL, 0},
+      {"truth-sort", 1, NULL, 0},
       {0, 0, 0, 0}};
   optind = 0;  // glibc: a full re-initialisation (this function runs once per rank)
   int opt, idx = 0;
@@ -395,6 +401,10 @@ void parse_args(int argc, char **argv, Cli &c) {
       else if (!strcmp(optarg, "maf")) c.truth_bam = false;
       else die(" (truth-format: %s): maf or bam.", optarg);
       break;
+    case 32:
+      if (strcmp(optarg, "coordinate")) die(" (truth-sort: %s): Acceptable value: coordinate.", optarg);
+      c.truth_sort = true;
+      break;
     case 29: case 30: break;  // --devices / --comm: main.cpp (one rank per GPU); a rank itself runs on `device`
     case 26: {  // utility/self-test: gzip FILE -> FILE.gz with the parallel writer, nothing else
       pbsim::ParallelGz gz;
@@ -417,6 +427,7 @@ void parse_args(int argc, char **argv, Cli &c) {
   }
   if (c.truth_bam && c.no_gzip) die(": --truth-format bam writes BGZF (<prefix>.aln.bam): it cannot be combined with --no-gzip.");
   if (c.truth_bam && c.use_samtools) die(": --truth-format bam makes its BAM records on the GPU: it cannot be combined with --samtools.");
+  if (c.truth_sort && !c.truth_bam) die(": --truth-sort coordinate sorts the <prefix>.aln.bam file: it needs --truth-format bam.");
   // ---- set_sim_param (pbsim.cpp:1451-1688)
   if (!c.set_flg[0] || !c.set_flg[1]) die(": --strategy and --method must be set.");
   if (c.p.strategy == PBSIM_STRATEGY_WGS && !c.set_flg[2]) die(": for --strategy wgs, --genome must be set.");
@@ -816,11 +827,112 @@ int job_done(void *u, int64_t record, const pbsim_stats *st, int64_t read_bytes,
   return 1;
 }
 
+// One finished truth BAM through pbsim_truth_bam_sort, in place: the file is mapped (not read into a second buffer), the sorted
+// bytes go to <name>.tmp, and only when the whole stage has succeeded is the index written to <name>.csi and the .tmp renamed
+// over the unsorted file.  false: the unsorted file is as it was, neither .tmp nor .csi is left, *err says why.
+bool sort_truth_file(pbsim_ctx *ctx, const std::string &name, bool trace, std::string *err) {
+  const std::string tmp = name + ".tmp", csi = name + ".csi";
+  const int fd = open(name.c_str(), O_RDONLY);
+  struct stat sb;
+  if (fd < 0 || fstat(fd, &sb) != 0 || sb.st_size <= 0) {
+    if (fd >= 0) close(fd);
+    *err = "Cannot open file: " + name;
+    return false;
+  }
+  void *map = mmap(NULL, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+  close(fd);
+  if (map == MAP_FAILED) {
+    *err = "Cannot map file: " + name;
+    return false;
+  }
+  (void)madvise(map, (size_t)sb.st_size, MADV_SEQUENTIAL);
+  if (trace) fprintf(stderr, "[pbsim sort] %s: %.1f MB mapped\n", name.c_str(), sb.st_size / 1e6);
+  struct Files {
+    FILE *fp;
+    std::string index;
+    bool write_failed;
+  } f = {fopen(tmp.c_str(), "wb"), std::string(), false};
+  if (!f.fp) {
+    munmap(map, (size_t)sb.st_size);
+    *err = "Cannot open output file: " + tmp;
+    return false;
+  }
+  pbsim_sorted_bam_sink sink = {&f,
+                                [](void *u, const char *z, int64_t k, int64_t) {
+                                  Files *x = (Files *)u;
+                                  if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
+                                  return x->write_failed ? 0 : 1;
+                                },
+                                [](void *u, const char *z, int64_t k) {
+                                  ((Files *)u)->index.assign(z, (size_t)k);
+                                  return 1;
+                                }};
+  int64_t stats[4];
+  bool ok = pbsim_truth_bam_sort(ctx, map, (int64_t)sb.st_size, &sink, stats) != 0;
+  if (!ok) *err = f.write_failed ? "write error on " + tmp : std::string(pbsim_last_error());
+  munmap(map, (size_t)sb.st_size);
+  if (fclose(f.fp) != 0 && ok) {
+    ok = false;
+    *err = "write error on " + tmp;
+  }
+  if (ok) {
+    FILE *ci = fopen(csi.c_str(), "wb");
+    if (!ci || fwrite(f.index.data(), 1, f.index.size(), ci) != f.index.size() || fclose(ci) != 0) {
+      ok = false;
+      *err = "write error on " + csi;
+    } else if (rename(tmp.c_str(), name.c_str()) != 0) {
+      ok = false;
+      *err = "cannot rename " + tmp + " over " + name;
+    }
+  }
+  if (!ok) {
+    unlink(tmp.c_str());
+    unlink(csi.c_str());
+    return false;
+  }
+  if (trace)
+    fprintf(stderr, "[pbsim sort] %s: %lld records on %lld references, %.1f MB of records, %lld index bins\n", name.c_str(),
+            (long long)stats[0], (long long)stats[1], stats[2] / 1e6, (long long)stats[3]);
+  return true;
+}
+
+// the files one after the other; the first failure ends the process with the reference's exit(-1)
+void sort_truth_files(pbsim_ctx *ctx, const std::vector<std::string> &names, bool trace) {
+  for (const std::string &n : names) {
+    std::string err;
+    if (!sort_truth_file(ctx, n, trace, &err)) {
+      fprintf(stderr, "ERROR: %s\n", err.c_str());
+      fprintf(stderr, "ERROR: %s is unsorted and intact; it can be sorted later with: pbsim --sort-truth-bam %s\n", n.c_str(), n.c_str());
+      quit(-1);
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int device) {
   struct timeval tv0;
   gettimeofday(&tv0, NULL);
+  if (argc >= 2 && !strcmp(argv[1], "--sort-truth-bam")) {
+    // the standalone mode: no simulation, the named files sorted and indexed in place on one GPU
+    if (comm && comm->world > 1) die(": --sort-truth-bam runs on one GPU.");
+    if (argc < 3) die(": --sort-truth-bam FILE [FILE ...]: name the .aln.bam files to sort.");
+    std::vector<std::string> names;
+    for (int i = 2; i < argc; i++) {
+      if (!strncmp(argv[i], "--", 2)) die(" (%s): --sort-truth-bam takes file names and no other option.", argv[i]);
+      names.push_back(argv[i]);
+    }
+    pbsim_params p;
+    pbsim_params_default(&p);
+    p.strategy = PBSIM_STRATEGY_WGS;
+    p.method = PBSIM_METHOD_ERR;
+    pbsim_ctx *sctx = pbsim_create(&p, device >= 0 ? device : 0);
+    if (!sctx) check(0);
+    sort_truth_files(sctx, names, getenv("PBSIM_TRACE") != nullptr);
+    const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
+    if (!(leave && *leave == '1')) pbsim_destroy(sctx);
+    return 0;
+  }
   Cli c;
   {
     // getopt_long keeps its state in globals: the ranks of one process (main.cpp: one thread per GPU) parse one after the other
@@ -846,6 +958,13 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
   };
   const std::string profile_fq = "sample_profile_" + c.profile_id + ".fastq",
                     profile_stats = "sample_profile_" + c.profile_id + ".stats";
+  if (world > 1 && c.truth_sort) {
+    if (rank0)
+      fprintf(stderr, "ERROR: --truth-sort runs on one GPU: run the job without it (several ranks write the same bytes as one) and sort "
+                      "the finished files with: pbsim --sort-truth-bam <prefix>[_NNNN].aln.bam\n");
+    else usleep(300000);  // (rank 0 reports; the ranks of one process share its exit)
+    quit(-1);
+  }
   if (world > 1) {
     if (!c.no_gzip && (!c.gzip_on_gpu || c.use_samtools))
       die(": several GPUs write their own byte ranges of the outputs: use --gzip gpu (default) or --no-gzip.");
@@ -947,7 +1066,14 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
   }
   std::string err;
   char name[4096];
-
+  std::vector<std::string> truth_files;  // --truth-sort: the <prefix>[_NNNN].aln.bam files of this run, in the order it wrote them
+  auto note_truth_file = [&](long n) {
+    if (!c.truth_sort) return;
+    char t[4096];
+    if (n > 0) snprintf(t, sizeof t, "%s_%04ld.aln.bam", c.prefix.c_str(), n);
+    else snprintf(t, sizeof t, "%s.aln.bam", c.prefix.c_str());
+    truth_files.push_back(t);
+  };
   if (c.p.strategy == PBSIM_STRATEGY_WGS && !sampling && !(c.p.pass_num > 1 && c.use_samtools && !c.no_gzip && c.gzip_on_gpu)) {
     // ---- pbsim.cpp:667-759 as one job: rank 0 splits the FASTA into <prefix>_NNNN.ref (and prints the reference stats),
     // every rank loads the records (C1: broadcast GPU to GPU when the communicator can, else from the .ref files),
@@ -1051,6 +1177,7 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
       jf.use_async_writes();
       if (jf.pool) check(pbsim_job_set_interleave(ctx, (int)std::min<long>(4, gi.num_seq)));
       for (long n = 1; n <= gi.num_seq; n++) jf.recs.emplace_back(new RecFiles);
+      for (long n = 1; n <= gi.num_seq; n++) note_truth_file(n);
       if (rank0) for (long n = 1; n <= gi.num_seq; n++) open_record(jf, n, true);
       barrier(comm);  // the files exist
       if (!rank0) for (long n = 1; n <= gi.num_seq; n++) open_record(jf, n, false);
@@ -1130,6 +1257,7 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
       jf.use_async_writes();
       if (jf.pool) check(pbsim_job_set_interleave(ctx, (int)std::min<long>(4, g.second - g.first + 1)));
       for (long n = g.first; n <= g.second; n++) jf.recs.emplace_back(new RecFiles);
+      for (long n = g.first; n <= g.second; n++) note_truth_file(n);
       if (rank0) for (long n = g.first; n <= g.second; n++) open_record(jf, n, true);
       barrier(comm);  // the files exist
       if (!rank0) for (long n = g.first; n <= g.second; n++) open_record(jf, n, false);
@@ -1188,6 +1316,7 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
         write_read_header(c, ctx, &o_read, n);
       }
       snprintf(name, sizeof name, "%s_%04ld", c.prefix.c_str(), n);
+      note_truth_file(n);
       open_truth_sink(c, ctx, &o_maf, name, 0);  // (the current unit's header: the record is no record of a job)
       Two two = {&o_read, &o_maf};
       pbsim_sink sink = {&two, cb_read, cb_maf};
@@ -1246,6 +1375,7 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
         open_sink(c, &o_read, c.prefix + ".sam", c.prefix + ".bam", true);
         write_read_header(c, ctx, &o_read, 0);
       }
+      note_truth_file(0);
       open_truth_sink(c, ctx, &o_maf, c.prefix, 0);
       Two two = {&o_read, &o_maf};
       pbsim_sink sink = {&two, cb_read, cb_maf};
@@ -1327,6 +1457,12 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
     }
   }
   phase("simulation done");
+  if (c.truth_sort) {  // every file of the job is closed: the truth files, one after the other, through the sort stage
+    // (what the job's pools held is the stage's to use; a context that cannot give them back sorts beside them)
+    if (!pbsim_release_pools(ctx) && trace) fprintf(stderr, "[pbsim cli] pools kept: %s\n", pbsim_last_error());
+    sort_truth_files(ctx, truth_files, trace);
+    phase("truth files sorted and indexed");
+  }
   // The `pbsim` binary ends the process right behind this call (main.cpp sets PBSIM_CLI_LEAVE_CONTEXT=1 for a single rank):
   // handing 150 GB of HBM pools and the pinned staging back piece by piece takes 0.8 s that the process exit does at once.
   // A caller that lives on (pbsim3_amd.cli_main, a rank thread of --devices) gets its memory back here.

@@ -14,6 +14,7 @@
 //                                     before this process has made any HIP call), child i = --rank i --world N on GPU i, a
 //                                     rendezvous file of the launch's own under /dev/shm (or $TMPDIR); exit status = the first
 //                                     child's that is not 0
+//   pbsim --sort-truth-bam FILE ..   no simulation: finished truth BAMs sorted by coordinate and indexed in place (cli.cpp)
 // Every rank runs the same pbsim_cli_main(argv): the job is deterministic in the values the ranks exchange, so they stay
 // in lockstep; rank 0 prints the report and creates the files, every rank writes its own byte ranges.
 #include <hip/hip_runtime.h>
@@ -71,6 +72,17 @@ int main(int argc, char **argv) {
     if (!strcmp(a, "--world") && i + 1 < argc) proc_world = atoi(argv[i + 1]);
     if (!strcmp(a, "--rendezvous") && i + 1 < argc) rendezvous = argv[i + 1];
     if (!strcmp(a, "--device") && i + 1 < argc) proc_device = atoi(argv[i + 1]);
+  }
+  {
+    // --truth-sort belongs to the one-rank command line: a front that starts several ranks refuses it before any of them starts
+    bool truth_sort = false;
+    for (int i = 1; i < argc; i++)
+      if (!strcmp(argv[i], "--truth-sort") || !strncmp(argv[i], "--truth-sort=", 13)) truth_sort = true;
+    if (truth_sort && (devices.size() > 1 || n_processes > 0 || proc_world > 0 || proc_rank >= 0 || !rendezvous.empty())) {
+      fprintf(stderr, "ERROR: --truth-sort runs on one GPU: run the job without it (several ranks write the same bytes as one) and sort "
+                      "the finished files with: pbsim --sort-truth-bam <prefix>[_NNNN].aln.bam\n");
+      return 255;
+    }
   }
   if (n_processes > 0) {
     if (!devices.empty() || proc_rank >= 0 || proc_world > 0 || !rendezvous.empty()) {
