@@ -250,6 +250,31 @@ int pbsim_sample_profile_from_device(pbsim_ctx *ctx, const void *d_fastq, int64_
 int pbsim_load_sample_fastq(pbsim_ctx *ctx, const char *path, double accuracy_min, double accuracy_max, pbsim_sample_stats *out);
 int pbsim_sample_profile_text(pbsim_ctx *ctx, char *dst, int64_t cap, int64_t *bytes);
 int pbsim_set_sample_chunk_bytes(pbsim_ctx *ctx, int64_t bytes);
+/* The same profile from a BAM, unaligned (PacBio, dorado) or aligned: bit for bit -- statistics, kept strings, pool -- the
+ * profile the calls above make from the FASTQ that `samtools fastq` (default options) writes from that BAM.  A BAM is a stream
+ * whose first four bytes, behind any gzip layer, are "BAM\1".  Records with flag 0x100 (secondary) or 0x800 (supplementary)
+ * are skipped; every other record is one read of l_seq qualities, quality byte q standing for the character min(q, 93) + 33,
+ * taken from the last byte to the first with flag 0x10 (the read's own orientation).  Names, bases, CIGARs and tags are only
+ * stepped over.  The record starts are found by a parallel test of every byte position and decided by a walk along
+ * block_size from the first record; the stream passes through HBM in windows of pbsim_set_sample_chunk_bytes inflated
+ * bytes, an unfinished record carried in front of the next one (a record may be larger than a window).
+ * Failures, besides the texts above (l_seq > 1 000 000 is "fastq is too long...", as its FASTQ line would be):
+ *   "<path>: truncated BAM header"                                       the header overruns the stream
+ *   "<path>: malformed or truncated BAM record at inflated offset <n>"   block_size < 32 + l_read_name + 4 n_cigar_op +
+ *       (l_seq + 1) / 2 + l_seq or > 64 MiB, l_read_name == 0, a name without its NUL, refID / next_refID outside [-1, n_ref),
+ *       pos / next_pos < -1, or a record that runs past the end of the stream
+ *   "<path>: BAM record <index> (<read name>) has no qualities"          l_seq > 0 and a first quality byte 0xFF; <index>
+ *       counts every record of the file from 1
+ * (<path> is "BAM bytes" where there is no file).  The context keeps the profile it had and stays usable.
+ *   pbsim_load_sample                       a file of either format -- FASTQ exactly as pbsim_load_sample_fastq reads it, or BAM
+ *                                           (BGZF inflated by this GPU, other gzip by zlib, or not compressed)
+ *   pbsim_sample_profile_from_bam_bytes     the inflated BAM bytes in host memory
+ *   pbsim_sample_profile_from_bam_device    the inflated BAM bytes in the memory of the context's GPU */
+int pbsim_load_sample(pbsim_ctx *ctx, const char *path, double accuracy_min, double accuracy_max, pbsim_sample_stats *out);
+int pbsim_sample_profile_from_bam_bytes(pbsim_ctx *ctx, const void *bam, int64_t n, double accuracy_min, double accuracy_max,
+                                        pbsim_sample_stats *out);
+int pbsim_sample_profile_from_bam_device(pbsim_ctx *ctx, const void *d_bam, int64_t n, double accuracy_min, double accuracy_max,
+                                         pbsim_sample_stats *out);
 /* SAM header the reference's main() writes when it opens the samtools pipe for a
  * unit (pass_num > 1; pbsim.cpp:721-722 wgs, :784-785 trans/templ).  Returns the
  * byte count (excluding the NUL), or the size needed when buf is NULL/too small. */

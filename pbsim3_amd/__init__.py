@@ -207,6 +207,9 @@ API = [
     ("pbsim_sample_profile_from_bytes", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.POINTER(SampleStats)]),
     ("pbsim_sample_profile_from_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.POINTER(SampleStats)]),
     ("pbsim_load_sample_fastq", C.c_int, [C.c_void_p, C.c_char_p, C.c_double, C.c_double, C.POINTER(SampleStats)]),
+    ("pbsim_load_sample", C.c_int, [C.c_void_p, C.c_char_p, C.c_double, C.c_double, C.POINTER(SampleStats)]),
+    ("pbsim_sample_profile_from_bam_bytes", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.POINTER(SampleStats)]),
+    ("pbsim_sample_profile_from_bam_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.POINTER(SampleStats)]),
     ("pbsim_sample_profile_text", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_set_sample_chunk_bytes", C.c_int, [C.c_void_p, C.c_int64]),
     ("pbsim_simulate_sample_comm", C.c_int, [C.c_void_p, C.POINTER(Comm), C.POINTER(RecordSink)]),
@@ -687,6 +690,31 @@ class Context:
                                                          C.byref(st)))
         return st
 
+    def load_sample(self, path, acc_min=0.75, acc_max=1.0):
+        """The profile of the --sample file `path`, FASTQ or BAM (unaligned or aligned), recognised by content behind any gzip
+        layer.  A BAM gives the profile of the FASTQ `samtools fastq` would write from it: secondary and supplementary
+        records skipped, reverse-strand records in the read's own orientation.  Returns its SampleStats."""
+        st = SampleStats()
+        _check(self.lib.pbsim_load_sample(self.h, os.fsencode(path), acc_min, acc_max, C.byref(st)))
+        return st
+
+    def sample_profile_from_bam(self, data, acc_min=0.75, acc_max=1.0):
+        """The same from inflated BAM bytes: `bytes`, or a contiguous uint8 torch tensor on the context's device."""
+        st = SampleStats()
+        if isinstance(data, (bytes, bytearray, memoryview)):
+            data = bytes(data)
+            _check(self.lib.pbsim_sample_profile_from_bam_bytes(self.h, data, len(data), acc_min, acc_max, C.byref(st)))
+            return st
+        import torch
+        if not (isinstance(data, torch.Tensor) and data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()):
+            raise TypeError("sample_profile_from_bam: bytes or a contiguous uint8 tensor on the context's device")
+        if data.device.index != self.device:
+            raise ValueError("sample_profile_from_bam: the tensor is on another device than the context")
+        torch.cuda.current_stream(data.device).synchronize()   # the bytes are complete when the library reads them
+        _check(self.lib.pbsim_sample_profile_from_bam_device(self.h, C.c_void_p(data.data_ptr()), data.numel(), acc_min, acc_max,
+                                                             C.byref(st)))
+        return st
+
     def sample_profile(self):
         """The filtered quality strings the context holds, in file order (the lines of sample_profile_<ID>.fastq)."""
         n = C.c_int64(0)
@@ -696,7 +724,7 @@ class Context:
         return buf.raw[:n.value].split(b"\n")[:-1]
 
     def set_sample_chunk_bytes(self, n):
-        """FASTQ bytes per window of the GPU profile builder (0: the default); the profile does not depend on it."""
+        """FASTQ (or inflated BAM) bytes per window of the GPU profile builder (0: the default); the profile does not depend on it."""
         _check(self.lib.pbsim_set_sample_chunk_bytes(self.h, n))
 
     def simulate_sample(self, collect=True):

@@ -25,6 +25,7 @@
 #include <sys/syscall.h>
 #include <sys/time.h>
 #include <time.h>
+#include <zlib.h>
 
 #include <algorithm>
 #include <atomic>
@@ -163,6 +164,74 @@ void open_truth_sink(const Cli &c, pbsim_ctx *ctx, Out *o, const std::string &st
 bool is_regular_file(const char *file) {
   struct stat sb;
   return stat(file, &sb) == 0 && S_ISREG(sb.st_mode);  // (a FIFO is never opened here)
+}
+
+// A --sample that is no regular file (a pipe) is a FASTQ for the host's stdio parse; a BAM needs a regular file.  A pipe is
+// read once, so its first bytes are taken here, looked at (BAM\1, plain or as the first bytes of a gzip stream), and given
+// to the parse again in front of the rest.
+struct PipeHead {
+  int fd = -1;
+  std::string head;
+  size_t at = 0;
+};
+ssize_t pipe_head_read(void *cookie, char *buf, size_t n) {
+  PipeHead *h = (PipeHead *)cookie;
+  if (h->at < h->head.size()) {
+    const size_t k = std::min(n, h->head.size() - h->at);
+    memcpy(buf, h->head.data() + h->at, k);
+    h->at += k;
+    return (ssize_t)k;
+  }
+  return read(h->fd, buf, n);
+}
+int pipe_head_close(void *cookie) {
+  PipeHead *h = (PipeHead *)cookie;
+  close(h->fd);
+  delete h;
+  return 0;
+}
+bool begins_as_bam(const std::string &head) {
+  if (head.size() >= 4 && !memcmp(head.data(), "BAM\1", 4)) return true;
+  if (head.size() < 18 || (unsigned char)head[0] != 0x1f || (unsigned char)head[1] != 0x8b) return false;
+  z_stream z;
+  memset(&z, 0, sizeof z);
+  if (inflateInit2(&z, 16 + MAX_WBITS) != Z_OK) return false;
+  unsigned char four[4] = {0, 0, 0, 0};
+  z.next_in = (Bytef *)head.data();
+  z.avail_in = (uInt)head.size();
+  z.next_out = four;
+  z.avail_out = 4;
+  (void)inflate(&z, Z_SYNC_FLUSH);
+  const bool bam = z.avail_out == 0 && !memcmp(four, "BAM\1", 4);
+  inflateEnd(&z);
+  return bam;
+}
+// nullptr: the file cannot be opened here (the stdio parse says so); *bam: it is a BAM (nothing is returned then)
+FILE *open_sample_pipe(const char *file, bool *bam) {
+  *bam = false;
+  struct stat sb;
+  if (stat(file, &sb) != 0 || S_ISREG(sb.st_mode) || S_ISDIR(sb.st_mode)) return nullptr;
+  const int fd = open(file, O_RDONLY);
+  if (fd < 0) return nullptr;
+  PipeHead *h = new PipeHead;
+  h->fd = fd;
+  h->head.resize(4096);
+  size_t have = 0;
+  while (have < h->head.size()) {
+    const ssize_t k = read(fd, &h->head[have], h->head.size() - have);
+    if (k <= 0) break;
+    have += (size_t)k;
+  }
+  h->head.resize(have);
+  if (begins_as_bam(h->head)) {
+    *bam = true;
+    pipe_head_close(h);
+    return nullptr;
+  }
+  cookie_io_functions_t io = {pipe_head_read, nullptr, nullptr, pipe_head_close};
+  FILE *fp = fopencookie(h, "r", io);
+  if (!fp) pipe_head_close(h);
+  return fp;
 }
 
 // what main() writes when it opens the samtools pipe (pbsim.cpp:721-722), as SAM text or as the BAM header
@@ -972,7 +1041,7 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
   if (rank0) print_sim_param(c);
 
   // A --sample that is a regular file (plain or gzip) is parsed, filtered and packed into the profile on this rank's GPU
-  // (pbsim_load_sample_fastq), so the context comes first then.  A pipe keeps the host's stdio parse, the reference's order
+  // (pbsim_load_sample: a FASTQ or a BAM), so the context comes first then.  A pipe keeps the host's stdio parse, the reference's order
   // and its output.
   pbsim_ctx *ctx = nullptr;
   const bool sample_on_gpu = sampling && !c.sam_reuse && is_regular_file(c.sample.c_str());
@@ -989,7 +1058,7 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
       if (!pbsim::read_sample_profile(profile_fq, profile_stats, &prof, &e)) die(": %s", e.c_str());
     } else if (sample_on_gpu) {
       pbsim_sample_stats st;
-      check(pbsim_load_sample_fastq(ctx, c.sample.c_str(), c.accuracy_min, c.accuracy_max, &st));
+      check(pbsim_load_sample(ctx, c.sample.c_str(), c.accuracy_min, c.accuracy_max, &st));
       prof.num = (long)st.num;
       prof.len_min = (long)st.len_min;
       prof.len_max = (long)st.len_max;
@@ -1011,8 +1080,12 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
         if (!pbsim::write_sample_profile_text(profile_fq, profile_stats, text.get(), (size_t)n, prof, &e)) die(": %s", e.c_str());
       }
     } else {
-      if (!pbsim::read_sample_fastq(c.sample.c_str(), (long)c.p.len_min, (long)c.p.len_max, c.accuracy_min,
-                                    c.accuracy_max, &prof, &e))
+      bool bam = false;
+      FILE *fp = open_sample_pipe(c.sample.c_str(), &bam);
+      if (bam) die(": --sample: a BAM must be a regular file");
+      if (fp ? !pbsim::read_sample_fastq_stream(fp, (long)c.p.len_min, (long)c.p.len_max, c.accuracy_min, c.accuracy_max, &prof, &e)
+             : !pbsim::read_sample_fastq(c.sample.c_str(), (long)c.p.len_min, (long)c.p.len_max, c.accuracy_min, c.accuracy_max,
+                                         &prof, &e))
         die(": %s", e.c_str());
       if (c.sam_store && rank0 && !pbsim::write_sample_profile(profile_fq, profile_stats, prof, &e)) die(": %s", e.c_str());
     }
@@ -1044,7 +1117,7 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
   if (!ctx) check(0);
   pbsim::set_input_context(ctx);  // gzip inputs of this rank: inflated on its own device
   if (!sample_on_gpu) phase("context created (HIP initialised)");
-  if (sample_on_gpu) {  // (pbsim_load_sample_fastq left the profile in HBM)
+  if (sample_on_gpu) {  // (pbsim_load_sample left the profile in HBM)
   } else if (sampling) {
     std::vector<const uint8_t *> qp;
     std::vector<int64_t> ql;

@@ -4,6 +4,11 @@
 // per record only its length and its accuracy come back, and the statistics are the host's arithmetic over them in file
 // order (unit_io.cpp), so every number and every error text is the stdio parser's.  The kept strings never leave the GPU:
 // they are packed into the pool pbsim_set_sample_profile would have uploaded.
+//
+// A BAM (unaligned or aligned; pbsim_load_sample, pbsim_sample_profile_from_bam_*) gives the profile of the FASTQ that
+// `samtools fastq` would write from it, through sample_bam.hip: the stream behind the header passes through HBM in the same
+// windows, the bytes of an unfinished record in front of the next one; the scan's candidates come back, the chain walk over
+// them (bam_chain.cpp) says which are records, and from there on the pass is the FASTQ's.
 #include <hip/hip_runtime.h>
 #include <fcntl.h>
 #include <limits.h>
@@ -18,6 +23,7 @@
 #include <thread>
 #include <vector>
 
+#include "bam_chain.h"
 #include "ctx.h"
 #include "engine_internal.h"
 #include "inflate_host.h"
@@ -330,6 +336,296 @@ int build(pbsim_ctx *c, const Source &src, double acc_min, double acc_max, pbsim
   return commit_host_profile(c, prof, out);
 }
 
+// ---- BAM
+
+struct BamMeta {  // device -> host per window
+  int64_t n_hits, kept_bytes;
+};
+
+struct BamBuilder {
+  pbsim_ctx *c;
+  hipStream_t st = nullptr;
+  DevBuf d_buf[2], d_tiles, d_scan_tmp, d_meta, d_qprob, d_hits, d_rec, d_qual, d_len, d_status, d_acc, d_padded, d_off, d_pool;
+  HostBuf h_meta;
+  ~BamBuilder() {  // whatever happens: nothing in flight when the buffers go
+    if (st) {
+      (void)hipStreamSynchronize(st);
+      (void)hipStreamDestroy(st);
+    }
+  }
+
+  // `label`: what the error texts call the input (the path)
+  int run(const Source &src, const std::string &label, double acc_min, double acc_max, pbsim_sample_stats *out) {
+    const int64_t chunk = std::min(c->sp_chunk_bytes > 0 ? c->sp_chunk_bytes : kDefaultChunk, kMaxChunk);
+    const long len_min = (long)c->p.len_min, len_max = (long)c->p.len_max;
+    const bool trace = getenv("PBSIM_TRACE") != nullptr;
+    // ---- the header: only as far as the first record
+    int64_t n_ref = 0, first = 0;
+    {
+      std::vector<uint8_t> down;
+      for (int64_t have = src.host ? src.n : std::min<int64_t>(src.n, 64 << 10);; have = std::min<int64_t>(src.n, have * 4)) {
+        const uint8_t *h = src.host;
+        if (!h) {
+          down.resize((size_t)have);
+          if (have) HIP_OK(hipMemcpy(down.data(), src.dev, (size_t)have, hipMemcpyDeviceToHost));
+          h = down.data();
+        }
+        const int ok = bam_parse_header(h, have, src.n, &n_ref, &first);
+        if (ok == -2) return fail(label + ": not a BAM stream (no BAM\\1 magic)");
+        if (ok < 0 || (ok == 0 && have >= src.n)) return fail(label + ": truncated BAM header");
+        if (ok > 0) break;
+      }
+    }
+    HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    HIP_OK(d_meta.ensure(sizeof(BamMeta)));
+    HIP_OK(h_meta.ensure(sizeof(BamMeta)));
+    HIP_OK(hipMemsetAsync(d_meta.p, 0, sizeof(BamMeta), st));
+    {
+      double qprob[94];
+      for (int q = 0; q < 94; q++) qprob[q] = pow(10, (double)q / -10);  // pbsim.cpp:546-549
+      HIP_OK(d_qprob.ensure(sizeof qprob));
+      HIP_OK(hipMemcpyAsync(d_qprob.p, qprob, sizeof qprob, hipMemcpyHostToDevice, st));
+      HIP_OK(hipStreamSynchronize(st));
+    }
+    int64_t pool_fill = 0;
+    HIP_OK(d_pool.ensure((size_t)(src.n / 2 + (64 << 10)), true));
+
+    SampleProfile prof;
+    prof.len_min = LONG_MAX;
+    std::vector<int32_t> in_len;  // the counted records whose length is in range, in file order
+    std::vector<double> in_acc;
+    std::vector<int32_t> sq_len;
+    std::vector<int64_t> sq_off;
+    std::vector<uint64_t> hits, rec;
+    std::vector<int32_t> hl, hs;
+    std::vector<double> ha;
+    BamMeta *dm = d_meta.as<BamMeta>(), *hm = (BamMeta *)h_meta.p;
+    int64_t at = first;      // stream offset of the window buffer's first byte: where the next record starts
+    int64_t upto = first;    // stream bytes that have been in a window
+    int64_t carry_from = 0, carry_len = 0;  // the unfinished record in the previous window's buffer
+    int64_t index = 0;       // records so far, skipped ones included
+    for (int64_t k = 0; upto < src.n; k++) {
+      const int b = (int)(k & 1);
+      const int64_t fresh = std::min(chunk, src.n - upto), size = carry_len + fresh;
+      const bool last = upto + fresh == src.n;
+      HIP_OK(d_buf[b].ensure((size_t)(size + kSbSlack)));
+      uint8_t *buf = d_buf[b].as<uint8_t>();
+      if (carry_len > 0)
+        HIP_OK(hipMemcpyAsync(buf, d_buf[1 - b].as<uint8_t>() + carry_from, (size_t)carry_len, hipMemcpyDeviceToDevice, st));
+      if (src.dev) HIP_OK(hipMemcpyAsync(buf + carry_len, src.dev + upto, (size_t)fresh, hipMemcpyDeviceToDevice, st));
+      else HIP_OK(hipMemcpyAsync(buf + carry_len, src.host + upto, (size_t)fresh, hipMemcpyHostToDevice, st));
+      HIP_OK(hipMemsetAsync(buf + size, 0, (size_t)kSbSlack, st));
+      upto += fresh;
+      // ---- candidates, ascending
+      const int64_t n_tiles = sb_tiles(size);
+      HIP_OK(d_tiles.ensure((size_t)(n_tiles + 2) * 8));
+      HIP_OK(d_scan_tmp.ensure((size_t)(n_tiles / 1024 + 8) * 8));
+      launch_sb_scan(buf, 0, size, (int32_t)n_ref, d_tiles.as<int64_t>(), nullptr, nullptr, st);
+      launch_exclusive_scan_i64(d_tiles.as<int64_t>(), d_tiles.as<int64_t>(), n_tiles, d_scan_tmp.as<int64_t>(), &dm->n_hits, st);
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipMemcpyAsync(hm, dm, sizeof(BamMeta), hipMemcpyDeviceToHost, st));
+      HIP_OK(hipStreamSynchronize(st));
+      const int64_t n_hits = hm->n_hits;
+      hits.resize((size_t)n_hits);
+      if (n_hits > 0) {
+        HIP_OK(d_hits.ensure((size_t)n_hits * 8));
+        launch_sb_scan(buf, 0, size, (int32_t)n_ref, nullptr, d_tiles.as<int64_t>(), d_hits.as<uint64_t>(), st);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(hits.data(), d_hits.p, (size_t)n_hits * 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+      }
+      // ---- the chain: the records that lie whole in this window
+      rec.clear();
+      int64_t stop = 0;
+      const BamChainEnd end = bam_walk_chain(hits.data(), hits.size(), 0, size, last, &rec, &stop);
+      const int64_t n_rec = (int64_t)rec.size();
+      int64_t kept_bytes = 0;
+      if (n_rec > 0) {
+        HIP_OK(d_rec.ensure((size_t)n_rec * 8));
+        HIP_OK(d_qual.ensure((size_t)n_rec * 4));
+        HIP_OK(d_len.ensure((size_t)n_rec * 4));
+        HIP_OK(d_status.ensure((size_t)n_rec * 4));
+        HIP_OK(d_acc.ensure((size_t)n_rec * 8));
+        HIP_OK(d_padded.ensure((size_t)n_rec * 8));
+        HIP_OK(d_off.ensure((size_t)n_rec * 8));
+        HIP_OK(d_scan_tmp.ensure((size_t)(n_rec / 1024 + 8) * 8));
+        hl.resize((size_t)n_rec);
+        hs.resize((size_t)n_rec);
+        ha.resize((size_t)n_rec);
+        HIP_OK(hipMemcpyAsync(d_rec.p, rec.data(), (size_t)n_rec * 8, hipMemcpyHostToDevice, st));
+        launch_sb_sums(buf, d_rec.as<uint64_t>(), n_rec, (int32_t)std::min<long>(std::max<long>(len_min, 0), kMaxQual + 1),
+                       (int32_t)std::min<long>(len_max, kMaxQual), acc_min, acc_max, d_qprob.as<double>(), d_qual.as<uint32_t>(),
+                       d_len.as<int32_t>(), d_status.as<int32_t>(), d_acc.as<double>(), d_padded.as<int64_t>(), st);
+        launch_exclusive_scan_i64(d_padded.as<int64_t>(), d_off.as<int64_t>(), n_rec, d_scan_tmp.as<int64_t>(), &dm->kept_bytes, st);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(hl.data(), d_len.p, (size_t)n_rec * 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(hs.data(), d_status.p, (size_t)n_rec * 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(ha.data(), d_acc.p, (size_t)n_rec * 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(hm, dm, sizeof(BamMeta), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+      }
+      // ---- the window's records in file order, as the FASTQ's: the all-reads numbers, the reference's limits, the filter
+      for (int64_t r = 0; r < n_rec; r++) {
+        index++;
+        if (hs[(size_t)r] == kSbSkipped) continue;  // secondary, supplementary: not a read of `samtools fastq`
+        if (hs[(size_t)r] == kSbNoQual) {
+          uint8_t head[36 + 256];
+          const size_t n = (size_t)std::min<int64_t>((int64_t)sizeof head, 4 + (int64_t)(rec[(size_t)r] & kSbSizeMask));
+          HIP_OK(hipMemcpy(head, buf + (rec[(size_t)r] >> kSbSizeBits), n, hipMemcpyDeviceToHost));
+          const size_t l_name = std::min<size_t>(head[12], n - 36);
+          return fail(label + ": BAM record " + std::to_string(index) + " (" +
+                      std::string((const char *)head + 36, strnlen((const char *)head + 36, l_name)) + ") has no qualities");
+        }
+        const long len = hl[(size_t)r];
+        if (len > kMaxQual) return fail(kTooLong);
+        prof.num++;
+        prof.len_total += len;
+        if (prof.num > kMaxNum) return fail(kTooMany);
+        prof.len_max = std::max(prof.len_max, len);
+        prof.len_min = std::min(prof.len_min, len);
+        if (len < len_min || len > len_max) continue;
+        in_len.push_back((int32_t)len);
+        in_acc.push_back(ha[(size_t)r]);
+        if (ha[(size_t)r] >= acc_min && ha[(size_t)r] <= acc_max) {
+          sq_len.push_back((int32_t)len);
+          sq_off.push_back(pool_fill + kept_bytes);
+          kept_bytes += (len + 7) & ~7L;
+        }
+      }
+      if (n_rec > 0 && kept_bytes != hm->kept_bytes) return fail("internal: the GPU's sample filter disagrees with the host's");
+      if (end == kBamChainMalformed)
+        return fail(label + ": malformed or truncated BAM record at inflated offset " + std::to_string(at + stop));
+      if (kept_bytes > 0) {
+        if ((size_t)(pool_fill + kept_bytes + 8) > d_pool.bytes) {  // grow, keeping what is there
+          DevBuf bigger;
+          HIP_OK(bigger.ensure((size_t)(pool_fill + kept_bytes + 8) + (size_t)(pool_fill + kept_bytes) / 2, true));
+          HIP_OK(hipMemcpyAsync(bigger.p, d_pool.p, (size_t)pool_fill, hipMemcpyDeviceToDevice, st));
+          HIP_OK(hipStreamSynchronize(st));
+          std::swap(bigger.p, d_pool.p);
+          std::swap(bigger.bytes, d_pool.bytes);
+        }
+        launch_sb_pool(buf, d_rec.as<uint64_t>(), d_qual.as<uint32_t>(), d_len.as<int32_t>(), d_padded.as<int64_t>(), d_off.as<int64_t>(),
+                       n_rec, d_pool.as<uint8_t>() + pool_fill, st);
+        HIP_OK(hipGetLastError());
+        pool_fill += kept_bytes;
+      }
+      // ---- what the next window inherits: the bytes of the record that this one does not complete
+      carry_from = stop;
+      carry_len = size - stop;
+      at += stop;
+      if (trace)
+        fprintf(stderr, "[pbsim sample profile] BAM window %lld: %lld bytes, %lld candidates, %lld records, %lld pool bytes, carry %lld\n",
+                (long long)k, (long long)size, (long long)n_hits, (long long)n_rec, (long long)kept_bytes, (long long)carry_len);
+    }
+    {
+      std::string e;
+      if (!sample_stats_from_records(in_len.data(), in_acc.data(), in_len.size(), len_max, acc_min, acc_max, &prof, &e)) return fail(e);
+    }
+    if (sq_len.size() > 0x7fffffffULL) return fail("too many sample reads");
+    HIP_OK(hipMemsetAsync(d_pool.as<uint8_t>() + pool_fill, 0, 8, st));  // the 8 spare bytes of pbsim_set_sample_profile's pool
+    HIP_OK(hipStreamSynchronize(st));
+    // ---- the context's profile, replaced only now
+    std::swap(c->d_sq.p, d_pool.p);
+    std::swap(c->d_sq.bytes, d_pool.bytes);
+    c->sq_len.swap(sq_len);
+    c->sq_off.swap(sq_off);
+    c->sq_total = prof.len_total_filtered;
+    to_abi(prof, out);
+    return PBSIM_SUCCEEDED;
+  }
+};
+
+int build_bam(pbsim_ctx *c, const Source &src, const std::string &label, double acc_min, double acc_max, pbsim_sample_stats *out) {
+  BamBuilder b;
+  b.c = c;
+  return b.run(src, label, acc_min, acc_max, out);
+}
+
+bool is_bam(const uint8_t *four) { return memcmp(four, "BAM\1", 4) == 0; }
+
+}  // namespace
+}  // namespace pbsim
+
+namespace pbsim {
+namespace {
+// a --sample file on the context's GPU; `bam_ok`: a stream that begins with BAM\1 is read as a BAM, else as the FASTQ it is not
+int load_file(pbsim_ctx *c, const char *path, double accuracy_min, double accuracy_max, pbsim_sample_stats *out, bool bam_ok) {
+  const long len_min = (long)c->p.len_min, len_max = (long)c->p.len_max;
+  struct stat sb;
+  int fd = -1;
+  if (stat(path, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0) {  // (a FIFO is opened once, by the stdio parse)
+    fd = open(path, O_RDONLY);
+    if (fd < 0) return fail(std::string("Cannot open file: ") + path);
+  }
+  if (fd < 0) {  // a pipe, an empty file, a file that is not there: the stdio parse (and its message), uploaded as ever
+    SampleProfile prof;
+    std::string e;
+    if (!read_sample_fastq_stdio(path, len_min, len_max, accuracy_min, accuracy_max, &prof, &e)) return fail(e);
+    return commit_host_profile(c, prof, out);
+  }
+  struct Close {
+    int fd;
+    ~Close() { close(fd); }
+  } closer{fd};
+  Source src;
+  src.fd = fd;
+  src.path = path;
+  src.n = (int64_t)sb.st_size;
+  unsigned char magic[4] = {0, 0, 0, 0};
+  const ssize_t got = pread(fd, magic, 4, 0);
+  if (bam_ok && got == 4 && is_bam(magic)) {  // an uncompressed BAM: the mapped file is the stream
+    void *map = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+    if (map == MAP_FAILED) return fail(std::string(path) + ": cannot map the BAM file");
+    struct Unmap {
+      void *p;
+      size_t n;
+      ~Unmap() { munmap(p, n); }
+    } unmap{map, (size_t)sb.st_size};
+    (void)madvise(map, (size_t)sb.st_size, MADV_SEQUENTIAL);
+    src.fd = -1;
+    src.host = (const uint8_t *)map;
+    return build_bam(c, src, path, accuracy_min, accuracy_max, out);
+  }
+  if (got < 2 || magic[0] != 0x1f || magic[1] != 0x8b) return build(c, src, accuracy_min, accuracy_max, out);
+  // ---- gzip: BGZF is inflated by this GPU, and the bytes stay in its memory when they fit there; else as any gzip input
+  src.fd = -1;
+  const size_t size = (size_t)sb.st_size;
+  void *map = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+  if (map == MAP_FAILED) return fail(std::string(path) + ": cannot map the gzip file");
+  struct Unmap {
+    void *p;
+    size_t n;
+    ~Unmap() { munmap(p, n); }
+  } unmap{map, size};
+  (void)madvise(map, size, MADV_SEQUENTIAL);
+  const uint8_t *bytes = (const uint8_t *)map;
+  DevBuf d_inflated;
+  InputBytes gz;
+  std::vector<BgzfMember> mem;
+  const bool bgzf = bgzf_index(bytes, (int64_t)size, &mem);
+  const int64_t total = bgzf ? bgzf_inflated_size(mem) : 0;
+  if (bgzf && total > 0 && d_inflated.ensure((size_t)total + 16, true) == hipSuccess) {
+    if (!inflate_members(c, bytes, mem, d_inflated.as<uint8_t>(), true)) return fail(std::string(path) + ": " + g_err);
+    src.dev = d_inflated.as<uint8_t>();
+    src.n = total;
+    if (bam_ok && total >= 4) {
+      uint8_t four[4];
+      HIP_OK(hipMemcpy(four, src.dev, 4, hipMemcpyDeviceToHost));
+      if (is_bam(four)) return build_bam(c, src, path, accuracy_min, accuracy_max, out);
+    }
+  } else {
+    (void)hipGetLastError();
+    pbsim_ctx *was = set_input_context(c);
+    std::string e;
+    const int g = open_input(path, &gz, &e);
+    set_input_context(was);
+    if (g <= 0) return fail(g < 0 ? e : std::string("Cannot open file: ") + path);
+    src.host = (const uint8_t *)(gz.map ? gz.map : (const void *)"");
+    src.n = (int64_t)gz.size;
+    if (bam_ok && src.n >= 4 && is_bam(src.host)) return build_bam(c, src, path, accuracy_min, accuracy_max, out);
+  }
+  return build(c, src, accuracy_min, accuracy_max, out);
+}
 }  // namespace
 }  // namespace pbsim
 
@@ -362,61 +658,31 @@ int pbsim_sample_profile_from_device(pbsim_ctx *c, const void *d_fastq, int64_t 
 
 int pbsim_load_sample_fastq(pbsim_ctx *c, const char *path, double accuracy_min, double accuracy_max, pbsim_sample_stats *out) {
   if (!check_args(c, "pbsim_load_sample_fastq", path != nullptr, 0, accuracy_min, accuracy_max, out)) return PBSIM_FAILED;
-  const long len_min = (long)c->p.len_min, len_max = (long)c->p.len_max;
-  struct stat sb;
-  int fd = -1;
-  if (stat(path, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0) {  // (a FIFO is opened once, by the stdio parse)
-    fd = open(path, O_RDONLY);
-    if (fd < 0) return fail(std::string("Cannot open file: ") + path);
-  }
-  if (fd < 0) {  // a pipe, an empty file, a file that is not there: the stdio parse (and its message), uploaded as ever
-    SampleProfile prof;
-    std::string e;
-    if (!read_sample_fastq_stdio(path, len_min, len_max, accuracy_min, accuracy_max, &prof, &e)) return fail(e);
-    return commit_host_profile(c, prof, out);
-  }
-  struct Close {
-    int fd;
-    ~Close() { close(fd); }
-  } closer{fd};
+  return load_file(c, path, accuracy_min, accuracy_max, out, false);
+}
+
+int pbsim_load_sample(pbsim_ctx *c, const char *path, double accuracy_min, double accuracy_max, pbsim_sample_stats *out) {
+  if (!check_args(c, "pbsim_load_sample", path != nullptr, 0, accuracy_min, accuracy_max, out)) return PBSIM_FAILED;
+  return load_file(c, path, accuracy_min, accuracy_max, out, true);
+}
+
+int pbsim_sample_profile_from_bam_bytes(pbsim_ctx *c, const void *bam, int64_t n, double accuracy_min, double accuracy_max,
+                                        pbsim_sample_stats *out) {
+  if (!check_args(c, "pbsim_sample_profile_from_bam_bytes", bam || n == 0, n, accuracy_min, accuracy_max, out)) return PBSIM_FAILED;
   Source src;
-  src.fd = fd;
-  src.path = path;
-  src.n = (int64_t)sb.st_size;
-  unsigned char magic[2] = {0, 0};
-  if (pread(fd, magic, 2, 0) != 2 || magic[0] != 0x1f || magic[1] != 0x8b) return build(c, src, accuracy_min, accuracy_max, out);
-  // ---- gzip: BGZF is inflated by this GPU, and the bytes stay in its memory when they fit there; else as any gzip input
-  src.fd = -1;
-  const size_t size = (size_t)sb.st_size;
-  void *map = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-  if (map == MAP_FAILED) return fail(std::string(path) + ": cannot map the gzip file");
-  struct Unmap {
-    void *p;
-    size_t n;
-    ~Unmap() { munmap(p, n); }
-  } unmap{map, size};
-  (void)madvise(map, size, MADV_SEQUENTIAL);
-  const uint8_t *bytes = (const uint8_t *)map;
-  DevBuf d_inflated;
-  InputBytes gz;
-  std::vector<BgzfMember> mem;
-  const bool bgzf = bgzf_index(bytes, (int64_t)size, &mem);
-  const int64_t total = bgzf ? bgzf_inflated_size(mem) : 0;
-  if (bgzf && total > 0 && d_inflated.ensure((size_t)total + 16, true) == hipSuccess) {
-    if (!inflate_members(c, bytes, mem, d_inflated.as<uint8_t>(), true)) return fail(std::string(path) + ": " + g_err);
-    src.dev = d_inflated.as<uint8_t>();
-    src.n = total;
-  } else {
-    (void)hipGetLastError();
-    pbsim_ctx *was = set_input_context(c);
-    std::string e;
-    const int g = open_input(path, &gz, &e);
-    set_input_context(was);
-    if (g <= 0) return fail(g < 0 ? e : std::string("Cannot open file: ") + path);
-    src.host = (const uint8_t *)(gz.map ? gz.map : (const void *)"");
-    src.n = (int64_t)gz.size;
-  }
-  return build(c, src, accuracy_min, accuracy_max, out);
+  src.host = (const uint8_t *)(bam ? bam : (const void *)"");
+  src.n = n;
+  return build_bam(c, src, "BAM bytes", accuracy_min, accuracy_max, out);
+}
+
+int pbsim_sample_profile_from_bam_device(pbsim_ctx *c, const void *d_bam, int64_t n, double accuracy_min, double accuracy_max,
+                                         pbsim_sample_stats *out) {
+  if (!check_args(c, "pbsim_sample_profile_from_bam_device", d_bam || n == 0, n, accuracy_min, accuracy_max, out)) return PBSIM_FAILED;
+  Source src;
+  if (n == 0) src.host = (const uint8_t *)"";
+  else src.dev = (const uint8_t *)d_bam;
+  src.n = n;
+  return build_bam(c, src, "BAM bytes", accuracy_min, accuracy_max, out);
 }
 
 int pbsim_sample_profile_text(pbsim_ctx *c, char *dst, int64_t cap, int64_t *bytes) {

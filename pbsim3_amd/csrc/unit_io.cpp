@@ -638,6 +638,11 @@ bool sample_stdio(FILE *fp, long len_min, long len_max, double acc_min, double a
 // BUF_SIZE chunking is not observable here (a chunk without a line feed never ends a line; only the 4th line's bytes are kept),
 // except through NUL bytes -- strlen() ends a chunk there -- so a file that holds one goes through the stdio path, as does
 // anything that cannot be mapped.  The reference spends its sample FASTQ's parse on one core (361 MB: 0.75 s here with stdio).
+bool read_sample_fastq_stream(FILE *fp, long len_min, long len_max, double acc_min, double acc_max, SampleProfile *out,
+                              std::string *err) {
+  return sample_stdio(fp, len_min, len_max, acc_min, acc_max, out, err);
+}
+
 bool read_sample_fastq(const char *file, long len_min, long len_max, double acc_min, double acc_max, SampleProfile *out,
                        std::string *err) {
   InputBytes gz;  // a gzip FASTQ: its inflated bytes stand for the mapped file, here and in the stdio pass

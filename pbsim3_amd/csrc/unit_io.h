@@ -5,6 +5,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include <string>
 #include <vector>
@@ -81,6 +82,9 @@ bool read_sample_fastq(const char *file, long len_min, long len_max, double acc_
 // the same through fgets, chunk by chunk as the reference reads it (files with NUL bytes, pipes; the checker of the fast path)
 bool read_sample_fastq_stdio(const char *file, long len_min, long len_max, double acc_min, double acc_max, SampleProfile *out,
                              std::string *err);
+// ... over an open stream (closed here), which a caller has looked into before
+bool read_sample_fastq_stream(FILE *fp, long len_min, long len_max, double acc_min, double acc_max, SampleProfile *out,
+                              std::string *err);
 // ... and over bytes in memory instead of a file
 bool read_sample_fastq_mem(const void *bytes, size_t n, long len_min, long len_max, double acc_min, double acc_max,
                            SampleProfile *out, std::string *err);

@@ -8,7 +8,10 @@ gamma lengths, mean 9 000, clipped to 100 .. 60 000; 100 000 strings = 1.8 GB, t
     --parent-cli -- for another build's binary (the parent commit's), alternated, --rounds times;
   - with --rocprof DIR: one load_sample_fastq in a child of its own under `rocprofv3 --kernel-trace --memory-copy-trace --stats`,
     for the split: the k_sp_* kernels, the scans, the copies (--trace-child --fastq PATH is that child).
-usage: python tools/sample_profile_rate.py [--strings 100000] [--dir /dev/shm] [--rounds 3] [--parent-cli PATH] [--rocprof DIR] [--json OUT]"""
+  - with --bam: the BAM input instead -- the same strings once as an unaligned BAM (BGZF, every third record marked
+    reverse-strand) and once as a BGZF FASTQ, both inflated on the GPU: Context.load_sample of the BAM beside
+    Context.load_sample_fastq of the FASTQ, wall time per call, and the same from the inflated BAM bytes already in HBM;
+usage: python tools/sample_profile_rate.py [--bam] [--strings 100000] [--dir /dev/shm] [--rounds 3] [--parent-cli PATH] [--rocprof DIR] [--json OUT]"""
 import argparse
 import json
 import os
@@ -88,6 +91,64 @@ def library(path, dev, reps, windows_mb):
     return out
 
 
+def bam_inputs(d, n):
+    """s.bam and s.fastq.gz (both BGZF, zlib level 1) of the same n strings; returns the inflated sizes"""
+    import struct
+    import numpy as np
+    import bgzf_writer as W
+    rng = np.random.default_rng(1)
+    k = (9000.0 / 7000.0) ** 2
+    lens = np.clip(rng.gamma(k, 9000.0 / k, n), 100, 60000).astype(np.int64)
+    level = rng.integers(8, 31, n)
+    bam, fq = [b"BAM\x01" + struct.pack("<ii", 0, 0)], []
+    for i in range(n):
+        ln = int(lens[i])
+        q = np.clip(level[i] + rng.integers(-5, 6, ln), 0, 93).astype(np.uint8)
+        name = b"r%d\0" % i
+        flag = 4 | (16 if i % 3 == 0 else 0)
+        body = struct.pack("<iiBBHHHiiii", -1, -1, len(name), 0, 4680, 0, flag, ln, -1, -1, 0) + name + \
+            b"\x11" * (ln // 2) + (b"\x10" if ln % 2 else b"") + q.tobytes()
+        bam.append(struct.pack("<I", len(body)) + body)
+        fq.append(b"@r%d\n" % i + (b"T" if flag & 16 else b"A") * ln + b"\n+\n" + ((q[::-1] if flag & 16 else q) + 33).tobytes() + b"\n")
+    bam, fq = b"".join(bam), b"".join(fq)
+    with open(os.path.join(d, "s.bam"), "wb") as f:
+        f.write(W.bgzf(bam, level=1))
+    with open(os.path.join(d, "s.fastq.gz"), "wb") as f:
+        f.write(W.bgzf(fq, level=1))
+    return bam, len(fq)
+
+
+def bam_mode(a):
+    import torch
+    import pbsim3_amd as P
+    res = {}
+    with tempfile.TemporaryDirectory(dir=a.dir) as d:
+        t0 = time.time()
+        bam, fq_bytes = bam_inputs(d, a.strings)
+        res["strings"], res["bam_bytes"], res["fastq_bytes"] = a.strings, len(bam), fq_bytes
+        res["bam_file_bytes"], res["fastq_gz_file_bytes"] = (os.path.getsize(os.path.join(d, x)) for x in ("s.bam", "s.fastq.gz"))
+        print(f"{a.strings} strings: BAM {len(bam) / 1e6:.1f} MB inflated ({res['bam_file_bytes'] / 1e6:.1f} MB BGZF), FASTQ "
+              f"{fq_bytes / 1e6:.1f} MB inflated ({res['fastq_gz_file_bytes'] / 1e6:.1f} MB BGZF), written in {time.time() - t0:.0f} s", flush=True)
+        dev = torch.frombuffer(bytearray(bam), dtype=torch.uint8).cuda()
+        with P.Context(P.default_params(strategy=P.STRATEGY_WGS, method=P.METHOD_SAMPLE), 0) as ctx:
+            for key, call in (("load_sample_bam_s", lambda: ctx.load_sample(os.path.join(d, "s.bam"))),
+                              ("load_sample_fastq_bgzf_s", lambda: ctx.load_sample_fastq(os.path.join(d, "s.fastq.gz"))),
+                              ("bam_from_device_s", lambda: ctx.sample_profile_from_bam(dev))):
+                ts, kept = [], []
+                for _ in range(a.rounds):
+                    t0 = time.perf_counter()
+                    st = call()
+                    ts.append(time.perf_counter() - t0)
+                    kept.append((st.num, st.num_filtered, st.len_total_filtered))
+                res[key], res[key + "_kept"] = ts, kept[-1]
+                print(f"{key}: {['%.4f' % x for x in ts]} s; reads {kept[-1][0]}, kept {kept[-1][1]} ({kept[-1][2]} bases)", flush=True)
+        res["same_profile_numbers"] = res["load_sample_bam_s_kept"] == res["load_sample_fastq_bgzf_s_kept"] == res["bam_from_device_s_kept"]
+    print(json.dumps(res))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def cli_phases(cli, d, tag):
     out = os.path.join(d, "out_" + tag)
     os.makedirs(out, exist_ok=True)
@@ -118,7 +179,10 @@ def main():
     ap.add_argument("--rocprof", metavar="DIR", help="also run one load_sample_fastq in a child under rocprofv3, its output into DIR")
     ap.add_argument("--trace-child", action="store_true")
     ap.add_argument("--fastq", help="(--trace-child) an existing FASTQ instead of a generated one")
+    ap.add_argument("--bam", action="store_true", help="time the BAM input beside the BGZF FASTQ of the same strings, and nothing else")
     a = ap.parse_args()
+    if a.bam:
+        return bam_mode(a)
     if a.trace_child and a.fastq:
         import pbsim3_amd as P
         with P.Context(P.default_params(strategy=P.STRATEGY_WGS, method=P.METHOD_SAMPLE), 0) as ctx:
