@@ -1,7 +1,7 @@
 // bam_sort.cpp -- pbsim_truth_bam_sort: a finished truth BAM (pbsim_set_truth_bam's records behind a header, BGZF) -> the same
-// records in coordinate order, BGZF again, and the CSI index of that file.  The host's part: the member index, the header, the
-// chain walk over the scan's candidates (the one place that decides what a record is), the index; the kernels are bam_sort.hip's,
-// inflate.hip's and deflate.hip's.
+// records in coordinate order, BGZF again, and the CSI index of that file.  The host's part: the member index, the index, and
+// what to say when bam_chain.cpp's header parse or chain walk refuses the stream; the kernels are bam_scan.hip's,
+// bam_sort.hip's, inflate.hip's and deflate.hip's.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -12,10 +12,12 @@
 #include <string>
 #include <vector>
 
+#include "bam_scan.h"
 #include "bam_sort.h"
 #include "ctx.h"
 #include "engine_internal.h"
 #include "inflate_host.h"
+#include "kernels.h"
 
 namespace pbsim {
 
@@ -24,7 +26,6 @@ namespace {
 const unsigned char kEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 constexpr int kMinShift = 14;
 
-inline uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 inline void put32(std::string *o, uint32_t v) {
   for (int k = 0; k < 4; k++) o->push_back((char)(v >> (8 * k)));
 }
@@ -33,61 +34,26 @@ inline void put64(std::string *o, uint64_t v) {
 }
 
 // device memory of this call alone: the stage's buffers are as large as the file, nothing of them is kept
-struct Buf {
-  void *p = nullptr;
-  ~Buf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-  }
-  template <class T>
-  T *as() const {
-    return reinterpret_cast<T *>(p);
-  }
-};
-int alloc(Buf &b, int64_t n, const char *what) {
+int out_of_memory(const char *what, size_t want) {
+  return fail(std::string("pbsim_truth_bam_sort: out of device memory: ") + what + " needs " + std::to_string(want) +
+              " bytes (the stage holds the inflated stream, the sorted stream and their compressed pieces in HBM at once and does not chunk)");
+}
+int alloc(DevBuf &b, int64_t n, const char *what) {
   b.release();
   const size_t want = (size_t)std::max<int64_t>(n, 256);
-  if (hipMalloc(&b.p, want) != hipSuccess) {
-    b.p = nullptr;
+  if (b.ensure(want, /*exact=*/true) != hipSuccess) {
     (void)hipGetLastError();
-    return fail(std::string("pbsim_truth_bam_sort: out of device memory: ") + what + " needs " + std::to_string(want) +
-                " bytes (the stage holds the inflated stream, the sorted stream and their compressed pieces in HBM at once and does not chunk)");
+    return out_of_memory(what, want);
   }
   return PBSIM_SUCCEEDED;
 }
 
-struct Header {
-  int64_t l_text = 0, n_ref = 0, end = 0;  // end: of the reference list = the first record's offset
-  std::vector<int64_t> ref_len;
-};
-// 1: parsed; 0: `have` bytes are not enough (more of the stream exists); -1: not a BAM header (*why)
-int parse_header(const uint8_t *h, int64_t have, int64_t n, Header *out, std::string *why) {
-  auto short_of = [&](int64_t need) { return need > have; };
-  if (n < 12) return *why = "shorter than a BAM header", -1;
-  if (short_of(12)) return 0;
-  if (memcmp(h, "BAM\1", 4)) return *why = "no BAM\\1 magic", -1;
-  const int64_t l_text = (int32_t)le32(h + 4);
-  if (l_text < 0 || 12 + l_text > n) return *why = "l_text runs past the end", -1;
-  if (short_of(12 + l_text)) return 0;
-  const int64_t n_ref = (int32_t)le32(h + 8 + l_text);
-  if (n_ref < 0) return *why = "n_ref is negative", -1;
-  int64_t at = 12 + l_text;
-  out->ref_len.clear();
-  for (int64_t r = 0; r < n_ref; r++) {
-    if (at + 4 > n) return *why = "the reference list runs past the end", -1;
-    if (short_of(at + 4)) return 0;
-    const int64_t l_name = (int32_t)le32(h + at);
-    if (l_name < 1 || at + 8 + l_name > n) return *why = "the reference list runs past the end", -1;
-    if (short_of(at + 8 + l_name)) return 0;
-    out->ref_len.push_back((int32_t)le32(h + at + 4 + l_name));
-    at += 8 + l_name;
-  }
-  out->l_text = l_text;
-  out->n_ref = n_ref;
-  out->end = at;
-  return 1;
-}
+const char *const kHeaderFault[] = {"",
+                                    "shorter than a BAM header",
+                                    "no BAM\\1 magic",
+                                    "l_text runs past the end",
+                                    "n_ref is negative",
+                                    "the reference list runs past the end"};
 
 // "SO:coordinate" into the @HD line of the header text (SAMv1 1.3: @HD is the first line where there is one)
 std::string sorted_text(const std::string &t) {
@@ -150,77 +116,50 @@ int sort_bam(pbsim_ctx *c, const uint8_t *src, int64_t n_src, const pbsim_sorted
   if (!bgzf_index(src, n_src, &mem))
     return fail("pbsim_truth_bam_sort: not BGZF (every member a gzip member with a 'BC' extra field, SAMv1 4.1)");
   const int64_t N = bgzf_inflated_size(mem);
-  Buf d_in;
-  if (!alloc(d_in, N + kBsSlack, "the inflated stream")) return PBSIM_FAILED;
-  HIP_OK(hipMemsetAsync(d_in.as<uint8_t>() + N, 0, (size_t)kBsSlack, st));
+  DevBuf d_in;
+  if (!alloc(d_in, N + kBamSlack, "the inflated stream")) return PBSIM_FAILED;
+  HIP_OK(hipMemsetAsync(d_in.as<uint8_t>() + N, 0, (size_t)kBamSlack, st));
   if (!inflate_members(c, src, mem, d_in.as<uint8_t>(), true)) return PBSIM_FAILED;
   HIP_OK(hipStreamSynchronize(st));
   clk.phase("inflate", N);
   // the header: only its bytes travel back
-  Header hd;
+  BamHeader hd;
   std::vector<uint8_t> hbytes;
   for (int64_t have = std::min<int64_t>(N, 64 << 10);; have = std::min<int64_t>(N, have * 4)) {
     hbytes.resize((size_t)have);
     if (have) HIP_OK(hipMemcpy(hbytes.data(), d_in.p, (size_t)have, hipMemcpyDeviceToHost));
-    std::string why;
-    const int ok = parse_header(hbytes.data(), have, N, &hd, &why);
-    if (ok < 0) return fail("pbsim_truth_bam_sort: not a BAM file: " + why);
+    const int ok = bam_parse_header(hbytes.data(), have, N, true, &hd);
+    if (ok > 0 && hd.empty_name) hd.fault = kBamHeaderRefs;
+    if (ok < 0 || hd.fault) return fail(std::string("pbsim_truth_bam_sort: not a BAM file: ") + kHeaderFault[hd.fault]);
     if (ok > 0) break;
     if (have >= N) return fail("pbsim_truth_bam_sort: not a BAM file: the header runs past the end");
   }
-  const int64_t H = hd.end;
+  const int64_t H = hd.first_record;
   const uint8_t *stream = d_in.as<uint8_t>();
-  // ---- 2. candidates: every byte position against the fixed fields, compacted in order
-  std::vector<uint64_t> rec;  // the true records, packed (offset << 24 | block_size)
+  // ---- 2. candidates: every byte position against the fixed fields, compacted in order; then the chain, from the first record:
+  // a step must land on a candidate, the last one on the end of the stream
+  std::vector<uint64_t> rec;  // the true records, packed as kBamSortPacking
   {
-    const int64_t first_tile = H / kBsTile, n_tiles = (N + kBsTile - 1) / kBsTile - first_tile;
     std::vector<uint64_t> cand;
-    if (n_tiles > 0) {
-      Buf d_count, d_base, d_tmp, d_cand;
-      if (!alloc(d_count, (n_tiles + 1) * 8, "the scan's tile counts") || !alloc(d_base, (n_tiles + 1) * 8, "the scan's tile offsets"))
-        return PBSIM_FAILED;
-      HIP_OK(hipMemsetAsync(d_count.as<int64_t>() + n_tiles, 0, 8, st));
-      launch_bs_scan(stream, H, N, (int32_t)hd.n_ref, first_tile, n_tiles, d_count.as<int64_t>(), nullptr, nullptr, st);
-      HIP_OK(hipGetLastError());
-      size_t tb = 0;
-      HIP_OK(bs_exclusive_scan(nullptr, &tb, d_count.as<int64_t>(), d_base.as<int64_t>(), n_tiles + 1, st));
-      if (!alloc(d_tmp, (int64_t)tb, "the scan's scratch")) return PBSIM_FAILED;
-      HIP_OK(bs_exclusive_scan(d_tmp.p, &tb, d_count.as<int64_t>(), d_base.as<int64_t>(), n_tiles + 1, st));
-      int64_t n_cand = 0;
-      HIP_OK(hipMemcpyAsync(&n_cand, d_base.as<int64_t>() + n_tiles, 8, hipMemcpyDeviceToHost, st));
-      HIP_OK(hipStreamSynchronize(st));
-      if (n_cand > 0) {
-        if (!alloc(d_cand, n_cand * 8, "the candidate list")) return PBSIM_FAILED;
-        launch_bs_scan(stream, H, N, (int32_t)hd.n_ref, first_tile, n_tiles, nullptr, d_base.as<int64_t>(), d_cand.as<uint64_t>(), st);
-        HIP_OK(hipGetLastError());
-        cand.resize((size_t)n_cand);
-        HIP_OK(hipMemcpyAsync(cand.data(), d_cand.p, (size_t)n_cand * 8, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-      }
+    {
+      BamScan scan;
+      const hipError_t e = scan.run(kBamScanPlaced, stream, H, N, (int32_t)hd.n_ref, st, &cand);
+      if (e == hipErrorOutOfMemory && scan.oom_what) return out_of_memory(scan.oom_what, scan.oom_bytes);
+      HIP_OK(e);
     }
     clk.phase("scan", N - H);
-    // ---- the chain, from the first record: a step must land on a candidate, the last one on the end of the stream
-    size_t ci = 0;
-    int64_t prev = -1;
-    uint32_t prev_size = 0;
-    for (int64_t cur = H; cur < N;) {
-      while (ci < cand.size() && (int64_t)(cand[ci] >> kBsSizeBits) < cur) ci++;
-      if (ci == cand.size() || (int64_t)(cand[ci] >> kBsSizeBits) != cur) {
-        char m[512];
-        int k = snprintf(m, sizeof m,
-                         "pbsim_truth_bam_sort: the record at inflated byte offset %lld does not fit (a placed single-end record: "
-                         "0 <= refID < n_ref, pos >= 0, next_refID = next_pos = -1, tlen = 0, a block_size that covers its fields and "
-                         "ends inside the stream of %lld bytes)",
-                         (long long)cur, (long long)N);
-        if (prev >= 0)
-          snprintf(m + k, sizeof m - (size_t)k, "; the block_size %u of the record before it, at offset %lld, leads there", prev_size,
-                   (long long)prev);
-        return fail(m);
-      }
-      rec.push_back(cand[ci]);
-      prev = cur;
-      prev_size = (uint32_t)(cand[ci] & kBsSizeMask);
-      cur += 4 + (int64_t)prev_size;
+    int64_t stop = 0;
+    if (bam_walk_chain(kBamSortPacking, cand.data(), cand.size(), H, N, true, &rec, &stop) != kBamChainDone) {
+      char m[512];
+      int k = snprintf(m, sizeof m,
+                       "pbsim_truth_bam_sort: the record at inflated byte offset %lld does not fit (a placed single-end record: "
+                       "0 <= refID < n_ref, pos >= 0, next_refID = next_pos = -1, tlen = 0, a block_size that covers its fields and "
+                       "ends inside the stream of %lld bytes)",
+                       (long long)stop, (long long)N);
+      if (!rec.empty())
+        snprintf(m + k, sizeof m - (size_t)k, "; the block_size %u of the record before it, at offset %lld, leads there",
+                 (uint32_t)kBamSortPacking.size(rec.back()), (long long)kBamSortPacking.offset(rec.back()));
+      return fail(m);
     }
     clk.phase("chain");
   }
@@ -229,10 +168,10 @@ int sort_bam(pbsim_ctx *c, const uint8_t *src, int64_t n_src, const pbsim_sorted
   // ---- 3, 4. keys and the stable sort; 5. the scan of the sorted sizes and the gather
   std::vector<uint64_t> key((size_t)n_rec);
   std::vector<int64_t> rend((size_t)n_rec), dst_off((size_t)n_rec + 1, 0);
-  Buf d_out;
+  DevBuf d_out;
   if (!alloc(d_out, total + 64, "the sorted stream")) return PBSIM_FAILED;
   if (n_rec > 0) {
-    Buf d_rec, d_key, d_key2, d_idx, d_perm, d_end, d_tmp;
+    DevBuf d_rec, d_key, d_key2, d_idx, d_perm, d_end, d_tmp;
     if (!alloc(d_rec, n_rec * 8, "the record list") || !alloc(d_key, n_rec * 8, "the keys") || !alloc(d_key2, n_rec * 8, "the sorted keys") ||
         !alloc(d_idx, n_rec * 4, "the record indices") || !alloc(d_perm, n_rec * 4, "the sorted indices") ||
         !alloc(d_end, n_rec * 8, "the end coordinates"))
@@ -251,18 +190,17 @@ int sort_bam(pbsim_ctx *c, const uint8_t *src, int64_t n_src, const pbsim_sorted
     HIP_OK(hipStreamSynchronize(st));
     clk.phase("keys and sort");
     // (d_key and d_idx have done their part: the sorted sizes and offsets take their places)
-    Buf d_src, d_size, d_dst, d_ends;
+    DevBuf d_src, d_size, d_dst, d_ends;
     d_idx.release();
-    if (!alloc(d_src, n_rec * 8, "the source offsets") || !alloc(d_size, (n_rec + 1) * 8, "the sorted sizes") ||
+    if (!alloc(d_src, n_rec * 8, "the source offsets") || !alloc(d_size, n_rec * 8, "the sorted sizes") ||
         !alloc(d_dst, (n_rec + 1) * 8, "the destination offsets") || !alloc(d_ends, n_rec * 8, "the sorted end coordinates"))
       return PBSIM_FAILED;
     launch_bs_permute(d_rec.as<uint64_t>(), d_perm.as<uint32_t>(), d_end.as<int64_t>(), n_rec, d_src.as<int64_t>(), d_size.as<int64_t>(),
                       d_ends.as<int64_t>(), st);
     HIP_OK(hipGetLastError());
-    tb = 0;
-    HIP_OK(bs_exclusive_scan(nullptr, &tb, d_size.as<int64_t>(), d_dst.as<int64_t>(), n_rec + 1, st));
-    if (!alloc(d_tmp, (int64_t)tb, "the scan's scratch")) return PBSIM_FAILED;
-    HIP_OK(bs_exclusive_scan(d_tmp.p, &tb, d_size.as<int64_t>(), d_dst.as<int64_t>(), n_rec + 1, st));
+    if (!alloc(d_tmp, (n_rec / 1024 + 8) * 8, "the scan's scratch")) return PBSIM_FAILED;
+    launch_exclusive_scan_i64(d_size.as<int64_t>(), d_dst.as<int64_t>(), n_rec, d_tmp.as<int64_t>(), d_dst.as<int64_t>() + n_rec, st);
+    HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(dst_off.data(), d_dst.p, (size_t)(n_rec + 1) * 8, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(key.data(), d_key2.p, (size_t)n_rec * 8, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(rend.data(), d_ends.p, (size_t)n_rec * 8, hipMemcpyDeviceToHost, st));

@@ -1,14 +1,7 @@
 // bam_sort.hip -- the kernels of pbsim_truth_bam_sort: a finished truth BAM, inflated into HBM, becomes the same records in
 // coordinate order.
 //
-//   scan    : BAM records are chained by block_size, and a chain is serial.  Every BYTE position is tested instead, in
-//             parallel, against the fields that are constant in a placed single-end record (twelve bytes: next_refID,
-//             next_pos, tlen) and against what its sizes must satisfy.  A workgroup stages a 4 KiB tile plus a 64-byte halo in
-//             LDS; a lane reduces the 48 bytes behind its sixteen positions to two bit masks (byte == 0xFF, byte == 0) and
-//             finds the positions whose twelve constant bytes match with a handful of shifts -- the full test, on unaligned
-//             fields, runs for those few only.  Two passes (count, then write behind an exclusive scan of the counts) keep
-//             the hits in ascending order.  The hits are a SUPERSET of the record starts (a SEQ of 'N's in front of zero
-//             qualities passes): the host walks the chain over them, and that walk alone decides (bam_sort.cpp).
+//   scan    : bam_scan.hip, with the policy "placed single-end record"; the host walks the chain over its candidates.
 //   keys    : one wave per record: refID, pos, and the reference span of its CIGAR, the ops across the lanes.
 //   sort    : rocPRIM's radix sort of (refID << 32 | pos, record index): stable, so ties keep their input order.
 //   gather  : destination-driven.  A wave owns 4 KiB of the sorted stream and a lane one 16-byte vector of it at a time: the
@@ -22,8 +15,9 @@
 #include <string.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
+#include "bam_chain.h"
+#include "bam_fields.h"
 #include "bam_sort.h"
 
 namespace pbsim {
@@ -32,105 +26,16 @@ namespace {
 
 constexpr int kThreads = 256;
 
-__device__ __forceinline__ uint32_t ld16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
-__device__ __forceinline__ uint32_t ld32(const uint8_t *p) { return ld16(p) | ld16(p + 2) << 16; }
-
-// bit k = byte k of w is zero (exact: no carry runs from one byte into the next)
-__device__ __forceinline__ uint32_t zero_bytes(uint32_t w) {
-  const uint32_t m = ~(((w & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | w | 0x7F7F7F7Fu);  // 0x80 in every zero byte
-  const uint32_t x = m >> 7;
-  return (x | x >> 7 | x >> 14 | x >> 21) & 15u;
-}
-
-// the whole test of position p (the caller has seen the twelve constant bytes); the record's block_size, or 0
-__device__ __forceinline__ uint32_t bs_fits(const uint8_t *stream, int64_t p, int64_t lo, int64_t n, int32_t n_ref) {
-  if (p < lo || p + 36 > n) return 0;
-  const uint8_t *r = stream + p;
-  const uint32_t block_size = ld32(r);
-  const int32_t ref_id = (int32_t)ld32(r + 4), pos = (int32_t)ld32(r + 8), l_seq = (int32_t)ld32(r + 20);
-  const uint32_t l_read_name = r[12], n_cigar_op = ld16(r + 16);
-  if (ref_id < 0 || ref_id >= n_ref || pos < 0 || l_seq < 0) return 0;
-  if (ld32(r + 24) != 0xffffffffu || ld32(r + 28) != 0xffffffffu || ld32(r + 32) != 0u) return 0;
-  const int64_t need = 32 + (int64_t)l_read_name + 4 * (int64_t)n_cigar_op + ((int64_t)l_seq + 1) / 2 + l_seq;
-  if ((int64_t)block_size < need || block_size > kBsSizeMask) return 0;
-  if (p + 4 + (int64_t)block_size > n) return 0;
-  return block_size;
-}
-
-template <bool kWrite>
-__global__ __launch_bounds__(kThreads) void k_bs_scan(const uint8_t *stream, int64_t lo, int64_t n, int32_t n_ref, int64_t first_tile,
-                                                     int64_t *tile_count, const int64_t *tile_base, uint64_t *out) {
-  __shared__ uint4 sh[kThreads + 4];
-  __shared__ int cnt[kThreads];
-  const int i = threadIdx.x;
-  const int64_t base = (first_tile + blockIdx.x) * kBsTile;
-  const uint4 *g = reinterpret_cast<const uint4 *>(stream + base);  // (the stream's buffer is aligned, and readable kBsSlack bytes past n)
-  sh[i] = g[i];
-  if (i < 4) sh[kThreads + i] = g[kThreads + i];
-  __syncthreads();
-  // bytes 16 i + 16 .. 16 i + 63 of the tile: position j = 16 i + j' wants 0xFF in bytes j + 24 .. j + 31, 0 in j + 32 .. j + 35
-  uint64_t ff = 0, zz = 0;
-#pragma unroll
-  for (int v = 0; v < 3; v++) {
-    const uint4 x = sh[i + 1 + v];
-    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      ff |= (uint64_t)zero_bytes(~w[k]) << (16 * v + 4 * k);
-      zz |= (uint64_t)zero_bytes(w[k]) << (16 * v + 4 * k);
-    }
-  }
-  ff &= ff >> 1;
-  ff &= ff >> 2;
-  ff &= ff >> 4;  // bit k: bytes k .. k + 7 are 0xFF
-  zz &= zz >> 1;
-  zz &= zz >> 2;  // bit k: bytes k .. k + 3 are 0
-  uint32_t hits = (uint32_t)((ff >> 8) & (zz >> 16)) & 0xffffu;
-  uint32_t size[16];
-#pragma unroll
-  for (int j = 0; j < 16; j++) size[j] = 0;
-  int mine = 0;
-  if (hits) {  // rare: the unaligned fields, from HBM
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-      if (hits >> j & 1) size[j] = bs_fits(stream, base + 16 * i + j, lo, n, n_ref);
-      mine += size[j] != 0;
-    }
-  }
-  const int total = __syncthreads_count(mine != 0);  // lanes with a hit
-  if (!kWrite) {
-    if (total == 0) {
-      if (i == 0) tile_count[blockIdx.x] = 0;
-      return;
-    }
-    cnt[i] = mine;
-    __syncthreads();
-    if (i == 0) {
-      int64_t sum = 0;
-      for (int k = 0; k < kThreads; k++) sum += cnt[k];
-      tile_count[blockIdx.x] = sum;
-    }
-    return;
-  }
-  if (total == 0) return;
-  cnt[i] = mine;
-  __syncthreads();
-  if (!mine) return;
-  int64_t at = tile_base[blockIdx.x];
-  for (int k = 0; k < i; k++) at += cnt[k];
-#pragma unroll
-  for (int j = 0; j < 16; j++)
-    if (size[j]) out[at++] = (uint64_t)(base + 16 * i + j) << kBsSizeBits | size[j];
-}
+constexpr BamPacking kPk = kBamSortPacking;
 
 __global__ __launch_bounds__(kThreads) void k_bs_keys(const uint8_t *stream, const uint64_t *rec, int64_t n_rec, uint64_t *key, uint32_t *idx,
                                                      int64_t *end) {
   const int64_t r = (int64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (r >= n_rec) return;
-  const uint8_t *p = stream + (rec[r] >> kBsSizeBits);
-  const uint32_t ref_id = ld32(p + 4), pos = ld32(p + 8), l_read_name = p[12], n_cigar_op = ld16(p + 16);
-  const uint8_t *cig = p + 36 + l_read_name;
+  const uint8_t *p = stream + kPk.offset(rec[r]);
+  const uint32_t ref_id = ld32(p + kBamRefId), pos = ld32(p + kBamPos), l_read_name = p[kBamLReadName], n_cigar_op = ld16(p + kBamNCigarOp);
+  const uint8_t *cig = p + kBamFixed + l_read_name;
   int64_t span = 0;
   for (uint32_t k = lane; k < n_cigar_op; k += 64) {
     const uint32_t v = ld32(cig + 4 * (int64_t)k);
@@ -148,15 +53,11 @@ __global__ __launch_bounds__(kThreads) void k_bs_keys(const uint8_t *stream, con
 __global__ __launch_bounds__(kThreads) void k_bs_permute(const uint64_t *rec, const uint32_t *perm, const int64_t *end, int64_t n_rec,
                                                         int64_t *src_off, int64_t *size, int64_t *end_sorted) {
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i > n_rec) return;
-  if (i == n_rec) {
-    size[i] = 0;
-    return;
-  }
+  if (i >= n_rec) return;
   const uint32_t r = perm[i];
   const uint64_t x = rec[r];
-  src_off[i] = (int64_t)(x >> kBsSizeBits);
-  size[i] = 4 + (int64_t)(x & kBsSizeMask);
+  src_off[i] = kPk.offset(x);
+  size[i] = 4 + kPk.size(x);
   end_sorted[i] = end[r];
 }
 
@@ -232,13 +133,6 @@ inline unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) 
 
 }  // namespace
 
-void launch_bs_scan(const uint8_t *stream, int64_t lo, int64_t n, int32_t n_ref, int64_t first_tile, int64_t n_tiles, int64_t *tile_count,
-                    const int64_t *tile_base, uint64_t *out, hipStream_t s) {
-  if (n_tiles <= 0) return;
-  if (out) hipLaunchKernelGGL(k_bs_scan<true>, dim3((unsigned)n_tiles), dim3(kThreads), 0, s, stream, lo, n, n_ref, first_tile, tile_count, tile_base, out);
-  else hipLaunchKernelGGL(k_bs_scan<false>, dim3((unsigned)n_tiles), dim3(kThreads), 0, s, stream, lo, n, n_ref, first_tile, tile_count, tile_base, out);
-}
-
 void launch_bs_keys(const uint8_t *stream, const uint64_t *rec, int64_t n_rec, uint64_t *key, uint32_t *idx, int64_t *end, hipStream_t s) {
   if (n_rec <= 0) return;
   hipLaunchKernelGGL(k_bs_keys, dim3(blocks_of(n_rec, kThreads / 64)), dim3(kThreads), 0, s, stream, rec, n_rec, key, idx, end);
@@ -246,7 +140,8 @@ void launch_bs_keys(const uint8_t *stream, const uint64_t *rec, int64_t n_rec, u
 
 void launch_bs_permute(const uint64_t *rec, const uint32_t *perm, const int64_t *end, int64_t n_rec, int64_t *src_off, int64_t *size,
                        int64_t *end_sorted, hipStream_t s) {
-  hipLaunchKernelGGL(k_bs_permute, dim3(blocks_of(n_rec + 1, kThreads)), dim3(kThreads), 0, s, rec, perm, end, n_rec, src_off, size, end_sorted);
+  if (n_rec <= 0) return;
+  hipLaunchKernelGGL(k_bs_permute, dim3(blocks_of(n_rec, kThreads)), dim3(kThreads), 0, s, rec, perm, end, n_rec, src_off, size, end_sorted);
 }
 
 void launch_bs_gather(const uint8_t *stream, uint8_t *out, const int64_t *src_off, const int64_t *dst_off, int64_t n_rec, int64_t total,
@@ -254,10 +149,6 @@ void launch_bs_gather(const uint8_t *stream, uint8_t *out, const int64_t *src_of
   if (n_rec <= 0 || total <= 0) return;
   hipLaunchKernelGGL(k_bs_gather, dim3(blocks_of(total, kBsSpan * (kThreads / 64))), dim3(kThreads), 0, s, stream, out, src_off, dst_off, n_rec,
                      total);
-}
-
-hipError_t bs_exclusive_scan(void *temp, size_t *temp_bytes, const int64_t *in, int64_t *out, int64_t n, hipStream_t s) {
-  return rocprim::exclusive_scan(temp, *temp_bytes, in, out, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), s);
 }
 
 hipError_t bs_sort_pairs(void *temp, size_t *temp_bytes, const uint64_t *key_in, uint64_t *key_out, const uint32_t *val_in, uint32_t *val_out,

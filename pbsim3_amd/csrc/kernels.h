@@ -374,15 +374,8 @@ void launch_sp_pool(const uint8_t *buf, const uint32_t *rec_start, const int32_t
                     int64_t n_rec, uint8_t *pool, hipStream_t s);
 
 // ---- sample_bam.hip: the same profile from BAM bytes in HBM -- of the FASTQ `samtools fastq` would write from them.
-// buf[0, n) is a window of the BAM stream behind its header (16-byte aligned, readable kSbSlack bytes past n); candidates and
-// records are packed as bam_chain.h says.
-constexpr int kSbTile = 4096;
-constexpr int64_t kSbSlack = kSbTile + 128;  // the scan loads whole tiles plus a 64-byte halo; the pool reads 15 bytes past a string
-inline int64_t sb_tiles(int64_t n) { return (n + kSbTile - 1) / kSbTile; }
-// Every byte position in [lo, n) against the fields of a record (sample_bam.hip).  out == nullptr: tile_count[t] = the hits of
-// tile t; else the hits, ascending, at out[tile_base[t]..) (tile_base = the exclusive scan of tile_count)
-void launch_sb_scan(const uint8_t *buf, int64_t lo, int64_t n, int32_t n_ref, int64_t *tile_count, const int64_t *tile_base, uint64_t *out,
-                    hipStream_t s);
+// buf[0, n) is a window of the BAM stream behind its header (16-byte aligned, readable kBamSlack bytes past n, bam_scan.h);
+// records are packed as kBamSamplePacking (bam_chain.h).
 enum : int32_t { kSbCounted = 0, kSbSkipped = 1, kSbNoQual = 2 };
 // One lane per record of the chain: status[r] (flag 0x100 / 0x800: skipped; l_seq > 0 and a first quality byte 0xFF: no
 // qualities), rec_len[r] = l_seq (0 when skipped), qual_at[r] = where its qualities lie; for a counted record with a length in

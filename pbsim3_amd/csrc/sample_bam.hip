@@ -3,14 +3,7 @@
 // k_walk_sample reads -- the profile sample_profile.hip makes from the FASTQ `samtools fastq` would write.  The host side
 // (header, windows, the chain walk that decides, statistics, errors) is sample_profile.cpp and bam_chain.cpp.
 //
-//   scan   : BAM records are chained by block_size, and a chain is serial.  Every BYTE position is tested instead, in
-//            parallel (k_bs_scan's shape: a 4 KiB tile plus a halo staged in LDS, a count pass and a write pass behind an
-//            exclusive scan so the hits come out ascending).  A general record has no constant bytes, so the test is on
-//            its fields: refID, next_refID in [-1, n_ref), pos, next_pos >= -1, l_read_name >= 1 with a NUL as the name's last
-//            byte, l_seq >= 0, block_size >= 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq and <= kBamMaxBlock, the
-//            record inside the bytes.  A lane holds the 64 bytes around its sixteen positions in registers and takes the
-//            unaligned fields out of them with v_alignbyte; only the name's last byte is read from HBM, for the few positions
-//            that come so far.  The hits are a SUPERSET of the record starts (a B array that holds a record image passes).
+//   scan   : bam_scan.hip, with the policy "any record"; the host walks the chain over its candidates.
 //   sums   : one LANE per record of the chain (k_sp_sums's shape): flag 0x900 -> skipped; a first quality byte 0xFF -> no
 //            qualities; else the host's additions in READ order -- backward through memory for flag 0x10 -- of a table in LDS
 //            indexed by the byte (qprob[min(q, 93)]), sixteen-byte loads between the unaligned ends of the string.
@@ -22,104 +15,14 @@
 #include <algorithm>
 
 #include "bam_chain.h"
+#include "bam_fields.h"
 #include "kernels.h"
 
 namespace pbsim {
 
 namespace {
 
-constexpr int kThreads = 256;
-static_assert(kSbTile == kThreads * 16, "a lane tests sixteen positions");
-
-__device__ __forceinline__ uint32_t ld16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
-__device__ __forceinline__ uint32_t ld32(const uint8_t *p) { return ld16(p) | ld16(p + 2) << 16; }
-
-// the 32-bit field at byte K of the lane's 64 bytes
-template <int K>
-__device__ __forceinline__ uint32_t field(const uint32_t (&w)[16]) {
-  static_assert(K + 4 <= 64, "inside the lane's bytes");
-  if constexpr ((K & 3) == 0) return w[K >> 2];
-  else return __builtin_amdgcn_alignbyte(w[(K >> 2) + 1], w[K >> 2], (uint32_t)(K & 3));
-}
-
-// position p = the lane's byte J: the record's block_size, or 0
-template <int J>
-__device__ __forceinline__ uint32_t sb_fits(const uint32_t (&w)[16], const uint8_t *buf, int64_t p, int64_t lo, int64_t n, int32_t n_ref) {
-  const int32_t ref_id = (int32_t)field<J + 4>(w), next_ref_id = (int32_t)field<J + 24>(w);
-  if (ref_id < -1 || ref_id >= n_ref || next_ref_id < -1 || next_ref_id >= n_ref) return 0;
-  const int32_t pos = (int32_t)field<J + 8>(w), next_pos = (int32_t)field<J + 28>(w), l_seq = (int32_t)field<J + 20>(w);
-  if (pos < -1 || next_pos < -1 || l_seq < 0) return 0;
-  const uint32_t block_size = field<J>(w), x = field<J + 12>(w), y = field<J + 16>(w);
-  const uint32_t l_read_name = x & 0xffu, n_cigar_op = y & 0xffffu;
-  if (l_read_name == 0) return 0;
-  const int64_t need = 32 + (int64_t)l_read_name + 4 * (int64_t)n_cigar_op + ((int64_t)l_seq + 1) / 2 + l_seq;
-  if ((int64_t)block_size < need || (int64_t)block_size > kBamMaxBlock) return 0;
-  if (p < lo || p + 4 + (int64_t)block_size > n) return 0;
-  if (buf[p + 35 + l_read_name] != 0) return 0;  // (inside the record: need <= block_size)
-  return block_size;
-}
-
-template <int J>
-__device__ __forceinline__ void sb_fits_all(const uint32_t (&w)[16], const uint8_t *buf, int64_t p0, int64_t lo, int64_t n, int32_t n_ref,
-                                            uint32_t (&size)[16], int &mine) {
-  if constexpr (J < 16) {
-    size[J] = sb_fits<J>(w, buf, p0 + J, lo, n, n_ref);
-    mine += size[J] != 0;
-    sb_fits_all<J + 1>(w, buf, p0, lo, n, n_ref, size, mine);
-  }
-}
-
-template <bool kWrite>
-__global__ __launch_bounds__(kThreads) void k_sb_scan(const uint8_t *buf, int64_t lo, int64_t n, int32_t n_ref, int64_t *tile_count,
-                                                     const int64_t *tile_base, uint64_t *out) {
-  __shared__ uint4 sh[kThreads + 4];
-  __shared__ int cnt[kThreads];
-  const int i = threadIdx.x;
-  const int64_t base = (int64_t)blockIdx.x * kSbTile;
-  const uint4 *g = reinterpret_cast<const uint4 *>(buf + base);  // (the buffer is aligned, and readable kSbSlack bytes past n)
-  sh[i] = g[i];
-  if (i < 4) sh[kThreads + i] = g[kThreads + i];
-  __syncthreads();
-  uint32_t w[16];
-#pragma unroll
-  for (int v = 0; v < 4; v++) {
-    const uint4 x = sh[i + v];
-    w[4 * v] = x.x;
-    w[4 * v + 1] = x.y;
-    w[4 * v + 2] = x.z;
-    w[4 * v + 3] = x.w;
-  }
-  uint32_t size[16];
-#pragma unroll
-  for (int j = 0; j < 16; j++) size[j] = 0;
-  int mine = 0;
-  const int64_t p0 = base + 16 * i;
-  if (p0 < n) sb_fits_all<0>(w, buf, p0, lo, n, n_ref, size, mine);  // (the fields of position 15 end at the lane's byte 46)
-  const int total = __syncthreads_count(mine != 0);  // lanes with a hit
-  if (!kWrite) {
-    if (total == 0) {
-      if (i == 0) tile_count[blockIdx.x] = 0;
-      return;
-    }
-    cnt[i] = mine;
-    __syncthreads();
-    if (i == 0) {
-      int64_t sum = 0;
-      for (int k = 0; k < kThreads; k++) sum += cnt[k];
-      tile_count[blockIdx.x] = sum;
-    }
-    return;
-  }
-  if (total == 0) return;
-  cnt[i] = mine;
-  __syncthreads();
-  if (!mine) return;
-  int64_t at = tile_base[blockIdx.x];
-  for (int k = 0; k < i; k++) at += cnt[k];
-#pragma unroll
-  for (int j = 0; j < 16; j++)
-    if (size[j]) out[at++] = (uint64_t)(p0 + j) << kSbSizeBits | size[j];
-}
+constexpr BamPacking kPk = kBamSamplePacking;
 
 #pragma clang fp contract(off)
 __global__ __launch_bounds__(256) void k_sb_sums(const uint8_t *buf, const uint64_t *rec, int64_t n_rec, int32_t len_min, int32_t len_max,
@@ -134,12 +37,12 @@ __global__ __launch_bounds__(256) void k_sb_sums(const uint8_t *buf, const uint6
   __syncthreads();
   const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (r >= n_rec) return;
-  const int64_t at = (int64_t)(rec[r] >> kSbSizeBits);
+  const int64_t at = kPk.offset(rec[r]);
   const uint8_t *h = buf + at;
-  const uint32_t l_read_name = h[12], n_cigar_op = ld16(h + 16), flag = ld16(h + 18);
-  const int32_t len = (int32_t)ld32(h + 20);
+  const uint32_t l_read_name = h[kBamLReadName], n_cigar_op = ld16(h + kBamNCigarOp), flag = ld16(h + kBamFlag);
+  const int32_t len = (int32_t)ld32(h + kBamLSeq);
   // (the chain walk took this record from the scan: its block_size covers the qualities)
-  const int64_t start = at + 36 + (int64_t)l_read_name + 4 * (int64_t)n_cigar_op + ((int64_t)len + 1) / 2;
+  const int64_t start = at + kBamFixed + (int64_t)l_read_name + 4 * (int64_t)n_cigar_op + ((int64_t)len + 1) / 2;
   int32_t st = kSbCounted;
   if (flag & 0x900u) st = kSbSkipped;
   else if (len > 0 && buf[start] == 0xffu) st = kSbNoQual;
@@ -222,7 +125,7 @@ __global__ __launch_bounds__(256) void k_sb_pool(const uint8_t *buf, const uint6
     const int64_t words = padded[r] >> 3;
     if (words == 0) continue;
     const int64_t start = qual_at[r], len = rec_len[r];
-    const bool rev = (ld16(buf + (rec[r] >> kSbSizeBits) + 18) & 0x10u) != 0;
+    const bool rev = (ld16(buf + kPk.offset(rec[r]) + kBamFlag) & 0x10u) != 0;
     uint64_t *dst = reinterpret_cast<uint64_t *>(pool + off[r]);
     for (int64_t w = lane; w < words; w += 64) {
       // the eight source bytes of this word begin at s: behind the string's start by up to 7 bytes for the last word of a
@@ -242,14 +145,6 @@ __global__ __launch_bounds__(256) void k_sb_pool(const uint8_t *buf, const uint6
 }
 
 }  // namespace
-
-void launch_sb_scan(const uint8_t *buf, int64_t lo, int64_t n, int32_t n_ref, int64_t *tile_count, const int64_t *tile_base, uint64_t *out,
-                    hipStream_t s) {
-  const int64_t n_tiles = sb_tiles(n);
-  if (n_tiles <= 0) return;
-  if (out) hipLaunchKernelGGL(k_sb_scan<true>, dim3((unsigned)n_tiles), dim3(kThreads), 0, s, buf, lo, n, n_ref, tile_count, tile_base, out);
-  else hipLaunchKernelGGL(k_sb_scan<false>, dim3((unsigned)n_tiles), dim3(kThreads), 0, s, buf, lo, n, n_ref, tile_count, tile_base, out);
-}
 
 void launch_sb_sums(const uint8_t *buf, const uint64_t *rec, int64_t n_rec, int32_t len_min, int32_t len_max, double acc_min, double acc_max,
                     const double *qprob, uint32_t *qual_at, int32_t *rec_len, int32_t *status, double *accuracy, int64_t *padded,

@@ -23,7 +23,7 @@
 #include <thread>
 #include <vector>
 
-#include "bam_chain.h"
+#include "bam_scan.h"
 #include "ctx.h"
 #include "engine_internal.h"
 #include "inflate_host.h"
@@ -339,14 +339,15 @@ int build(pbsim_ctx *c, const Source &src, double acc_min, double acc_max, pbsim
 // ---- BAM
 
 struct BamMeta {  // device -> host per window
-  int64_t n_hits, kept_bytes;
+  int64_t kept_bytes;
 };
 
 struct BamBuilder {
   pbsim_ctx *c;
   hipStream_t st = nullptr;
-  DevBuf d_buf[2], d_tiles, d_scan_tmp, d_meta, d_qprob, d_hits, d_rec, d_qual, d_len, d_status, d_acc, d_padded, d_off, d_pool;
+  DevBuf d_buf[2], d_scan_tmp, d_meta, d_qprob, d_rec, d_qual, d_len, d_status, d_acc, d_padded, d_off, d_pool;
   HostBuf h_meta;
+  BamScan scan;
   ~BamBuilder() {  // whatever happens: nothing in flight when the buffers go
     if (st) {
       (void)hipStreamSynchronize(st);
@@ -360,7 +361,7 @@ struct BamBuilder {
     const long len_min = (long)c->p.len_min, len_max = (long)c->p.len_max;
     const bool trace = getenv("PBSIM_TRACE") != nullptr;
     // ---- the header: only as far as the first record
-    int64_t n_ref = 0, first = 0;
+    BamHeader hd;
     {
       std::vector<uint8_t> down;
       for (int64_t have = src.host ? src.n : std::min<int64_t>(src.n, 64 << 10);; have = std::min<int64_t>(src.n, have * 4)) {
@@ -370,7 +371,7 @@ struct BamBuilder {
           if (have) HIP_OK(hipMemcpy(down.data(), src.dev, (size_t)have, hipMemcpyDeviceToHost));
           h = down.data();
         }
-        const int ok = bam_parse_header(h, have, src.n, &n_ref, &first);
+        const int ok = bam_parse_header(h, have, src.n, false, &hd);
         if (ok == -2) return fail(label + ": not a BAM stream (no BAM\\1 magic)");
         if (ok < 0 || (ok == 0 && have >= src.n)) return fail(label + ": truncated BAM header");
         if (ok > 0) break;
@@ -400,44 +401,28 @@ struct BamBuilder {
     std::vector<int32_t> hl, hs;
     std::vector<double> ha;
     BamMeta *dm = d_meta.as<BamMeta>(), *hm = (BamMeta *)h_meta.p;
-    int64_t at = first;      // stream offset of the window buffer's first byte: where the next record starts
-    int64_t upto = first;    // stream bytes that have been in a window
+    int64_t at = hd.first_record;  // stream offset of the window buffer's first byte: where the next record starts
+    int64_t upto = hd.first_record;  // stream bytes that have been in a window
     int64_t carry_from = 0, carry_len = 0;  // the unfinished record in the previous window's buffer
     int64_t index = 0;       // records so far, skipped ones included
     for (int64_t k = 0; upto < src.n; k++) {
       const int b = (int)(k & 1);
       const int64_t fresh = std::min(chunk, src.n - upto), size = carry_len + fresh;
       const bool last = upto + fresh == src.n;
-      HIP_OK(d_buf[b].ensure((size_t)(size + kSbSlack)));
+      HIP_OK(d_buf[b].ensure((size_t)(size + kBamSlack)));
       uint8_t *buf = d_buf[b].as<uint8_t>();
       if (carry_len > 0)
         HIP_OK(hipMemcpyAsync(buf, d_buf[1 - b].as<uint8_t>() + carry_from, (size_t)carry_len, hipMemcpyDeviceToDevice, st));
       if (src.dev) HIP_OK(hipMemcpyAsync(buf + carry_len, src.dev + upto, (size_t)fresh, hipMemcpyDeviceToDevice, st));
       else HIP_OK(hipMemcpyAsync(buf + carry_len, src.host + upto, (size_t)fresh, hipMemcpyHostToDevice, st));
-      HIP_OK(hipMemsetAsync(buf + size, 0, (size_t)kSbSlack, st));
+      HIP_OK(hipMemsetAsync(buf + size, 0, (size_t)kBamSlack, st));
       upto += fresh;
       // ---- candidates, ascending
-      const int64_t n_tiles = sb_tiles(size);
-      HIP_OK(d_tiles.ensure((size_t)(n_tiles + 2) * 8));
-      HIP_OK(d_scan_tmp.ensure((size_t)(n_tiles / 1024 + 8) * 8));
-      launch_sb_scan(buf, 0, size, (int32_t)n_ref, d_tiles.as<int64_t>(), nullptr, nullptr, st);
-      launch_exclusive_scan_i64(d_tiles.as<int64_t>(), d_tiles.as<int64_t>(), n_tiles, d_scan_tmp.as<int64_t>(), &dm->n_hits, st);
-      HIP_OK(hipGetLastError());
-      HIP_OK(hipMemcpyAsync(hm, dm, sizeof(BamMeta), hipMemcpyDeviceToHost, st));
-      HIP_OK(hipStreamSynchronize(st));
-      const int64_t n_hits = hm->n_hits;
-      hits.resize((size_t)n_hits);
-      if (n_hits > 0) {
-        HIP_OK(d_hits.ensure((size_t)n_hits * 8));
-        launch_sb_scan(buf, 0, size, (int32_t)n_ref, nullptr, d_tiles.as<int64_t>(), d_hits.as<uint64_t>(), st);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpyAsync(hits.data(), d_hits.p, (size_t)n_hits * 8, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-      }
+      HIP_OK(scan.run(kBamScanAny, buf, 0, size, (int32_t)hd.n_ref, st, &hits));
       // ---- the chain: the records that lie whole in this window
       rec.clear();
       int64_t stop = 0;
-      const BamChainEnd end = bam_walk_chain(hits.data(), hits.size(), 0, size, last, &rec, &stop);
+      const BamChainEnd end = bam_walk_chain(kBamSamplePacking, hits.data(), hits.size(), 0, size, last, &rec, &stop);
       const int64_t n_rec = (int64_t)rec.size();
       int64_t kept_bytes = 0;
       if (n_rec > 0) {
@@ -470,8 +455,8 @@ struct BamBuilder {
         if (hs[(size_t)r] == kSbSkipped) continue;  // secondary, supplementary: not a read of `samtools fastq`
         if (hs[(size_t)r] == kSbNoQual) {
           uint8_t head[36 + 256];
-          const size_t n = (size_t)std::min<int64_t>((int64_t)sizeof head, 4 + (int64_t)(rec[(size_t)r] & kSbSizeMask));
-          HIP_OK(hipMemcpy(head, buf + (rec[(size_t)r] >> kSbSizeBits), n, hipMemcpyDeviceToHost));
+          const size_t n = (size_t)std::min<int64_t>((int64_t)sizeof head, 4 + kBamSamplePacking.size(rec[(size_t)r]));
+          HIP_OK(hipMemcpy(head, buf + kBamSamplePacking.offset(rec[(size_t)r]), n, hipMemcpyDeviceToHost));
           const size_t l_name = std::min<size_t>(head[12], n - 36);
           return fail(label + ": BAM record " + std::to_string(index) + " (" +
                       std::string((const char *)head + 36, strnlen((const char *)head + 36, l_name)) + ") has no qualities");
@@ -515,7 +500,7 @@ struct BamBuilder {
       at += stop;
       if (trace)
         fprintf(stderr, "[pbsim sample profile] BAM window %lld: %lld bytes, %lld candidates, %lld records, %lld pool bytes, carry %lld\n",
-                (long long)k, (long long)size, (long long)n_hits, (long long)n_rec, (long long)kept_bytes, (long long)carry_len);
+                (long long)k, (long long)size, (long long)hits.size(), (long long)n_rec, (long long)kept_bytes, (long long)carry_len);
     }
     {
       std::string e;

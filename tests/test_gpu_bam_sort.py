@@ -1,4 +1,4 @@
-"""`--truth-sort coordinate` (pbsim_truth_bam_sort; pbsim3_amd/csrc/bam_sort.hip, bam_sort.cpp): a finished truth BAM comes
+"""`--truth-sort coordinate` (pbsim_truth_bam_sort; pbsim3_amd/csrc/bam_scan.hip, bam_sort.hip, bam_sort.cpp): a finished truth BAM comes
 back coordinate-sorted with a CSI index.  Synthetic files built here go through Context.sort_truth_bam and must come back as
 tests/csi_model.py says, byte for byte: the header with SO:coordinate, the records in stable (refID, pos) order, the index
 of the very members the file has, and region queries through that index that find what a scan of every record finds.  Then
@@ -17,7 +17,7 @@ from cases import CASES
 
 pytestmark = pytest.mark.gpu
 
-TILE = 4096                     # bytes per workgroup of the record scan (bam_sort.h kBsTile)
+TILE = 4096                     # bytes per workgroup of the record scan (bam_scan.h kBamTile)
 SIZES = [65280, 1, 777, 4095, 32768, 3, 12345]       # uneven input members: no record start is aligned to anything
 
 
@@ -149,6 +149,44 @@ def test_a_broken_chain_is_refused_and_the_context_lives_on(ctx):
         ctx.sort_truth_bam(b"not a gzip member at all", on_index=seen.append)
     assert seen == []
     check(ctx, refs, recs)
+
+
+def test_the_largest_record_and_one_byte_more(ctx):
+    """the sort packs offset << 24 | block_size: a record with a block_size of 2^24 - 1 is sorted and indexed, the same record one
+    byte longer is refused at its own offset, and the context sorts the good file afterwards"""
+    refs = [(b"ref", 100_000)]
+    small = [sized(0, 90_000 - 7 * k, b"s%d" % k, 50 + 11 * k) for k in range(6)]
+    head = M.header(refs)
+    at = len(head) + sum(len(r) for r in small[:3])
+
+    def recs(block_size):
+        return small[:3] + [sized(0, 5000, b"largest", 4 + block_size, span=30)] + small[3:]
+
+    seen = []
+    with pytest.raises(P.PbsimError, match=r"offset %d\b" % at):
+        ctx.sort_truth_bam(framed(head + b"".join(recs(1 << 24)), [65280]), on_index=seen.append)
+    assert seen == []
+    good = recs((1 << 24) - 1)
+    assert struct.unpack_from("<I", good[3])[0] == (1 << 24) - 1
+    check(ctx, refs, good, sizes=[65280])
+
+
+@pytest.fixture(scope="module")
+def many_records():
+    """5 000 records of about 2 KB on two references, seeded: more than 2 x 2048 records and more than 2048 tiles of stream"""
+    rng = random.Random(24)
+    refs = [(b"one", 3_000_000), (b"two", 500_000)]
+    recs = [sized(k % 2, rng.randrange(refs[k % 2][1] - 100), b"m%d" % k, 1900 + rng.randrange(400), span=1 + rng.randrange(60))
+            for k in range(5000)]
+    return refs, recs
+
+
+def test_more_tiles_and_more_records_than_one_tile_of_the_exclusive_scan(ctx, many_records):
+    """both exclusive scans -- of the scan's per-tile counts and of the sorted sizes -- run over more than two of their own
+    tiles of 2048 elements"""
+    refs, recs = many_records
+    assert len(recs) > 2 * 2048 and sum(len(r) for r in recs) > 2048 * TILE
+    check(ctx, refs, recs, sizes=[65280])
 
 
 # ---------------------------------------------------------------- keys and order

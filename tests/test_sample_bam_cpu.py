@@ -1,7 +1,8 @@
 """The BAM input of the sampling method where no device is needed (pbsim_load_sample, pbsim_sample_profile_from_bam_bytes /
 _from_bam_device; pbsim3_amd/csrc/sample_profile.cpp, bam_chain.cpp): the entry points exist and check their arguments first,
 a tables-only context refuses them and stays usable, and the HIP-free host decisions -- the header parse and the chain walk
-over the scan's candidates -- run as a program of their own under ASan + UBSan (tests/asan/bam_chain_driver.cpp)."""
+over the scan's candidates, which the truth-BAM sort shares with its own packing -- run as a program of their own under
+ASan + UBSan (tests/asan/bam_chain_driver.cpp)."""
 import ctypes as C
 import os
 import shutil
@@ -16,7 +17,9 @@ import pbsim3_amd as P
 CSRC = os.path.join(harness.ROOT, "pbsim3_amd", "csrc")
 SYMBOLS = ["pbsim_load_sample", "pbsim_sample_profile_from_bam_bytes", "pbsim_sample_profile_from_bam_device"]
 BAM = B.stream([B.record("r", 4, qual=bytes([20]) * 200)])
-MAX_BLOCK = 64 << 20
+MAX_BLOCK = 64 << 20            # the sampling input's packing: 28 size bits
+SORT_MAX_BLOCK = (1 << 24) - 1  # the sort's: 24
+REF_LISTS = [[], [("chr1", 1000)], [("a", 5), ("b" * 300, 6), ("chrM", 16569)]]
 
 
 def params():
@@ -35,7 +38,7 @@ def test_symbols_and_methods_exist():
     for name in SYMBOLS:
         assert "int %s(pbsim_ctx *ctx" % name in header, name
     import pbsim3_amd.build as b
-    assert "sample_bam.hip" in b.HIP_SOURCES and "bam_chain.cpp" in b.CXX_SOURCES
+    assert "sample_bam.hip" in b.HIP_SOURCES and "bam_scan.hip" in b.HIP_SOURCES and "bam_chain.cpp" in b.CXX_SOURCES
 
 
 def test_tables_only_context_refuses_and_stays_usable(tmp_path):
@@ -102,7 +105,7 @@ def test_hip_free_translation_unit():
         assert includes and not any(w in line for line in includes for w in ("hip", "ctx.h", "kernels.h", "engine")), (name, includes)
 
 
-@pytest.mark.parametrize("refs", [[], [("chr1", 1000)], [("a", 5), ("b" * 300, 6), ("chrM", 16569)]])
+@pytest.mark.parametrize("refs", REF_LISTS)
 def test_header_parse(driver, tmp_path, refs):
     text = b"@HD\tVN:1.6\n@SQ\tSN:x\tLN:5\n" * 3
     h = B.header(refs, text)
@@ -144,9 +147,54 @@ def test_header_lengths_that_lie(driver, tmp_path):
         assert int(run(driver, "header", path, "%d:%d" % (len(data), len(data)))[0].split()[3]) == want, name
 
 
-def test_chain_walk(driver):
+@pytest.mark.parametrize("refs", REF_LISTS)
+def test_header_parse_for_the_sort(driver, tmp_path, refs):
+    """with the reference lengths wanted: l_text and every l_ref exactly, and not before the last l_ref has been seen"""
+    text = b"@HD\tVN:1.6\n@SQ\tSN:x\tLN:5\n" * 3
+    h = B.header(refs, text)
+    body = h + B.record_bytes(B.record("r", 4, qual=bytes([30]) * 10))
+    path = tmp_path / "h.bin"
+    path.write_bytes(body)
+    n = len(body)
+    good = "1 0 0 %d %d %d" % (len(text), len(refs), len(h)) + "".join(" %d" % l for _, l in refs)
+    for have, line in enumerate(run(driver, "header+", path, *["%d:%d" % (n, have) for have in range(n + 1)])):
+        assert line == "header %d:%d -> %s" % (n, have, good if have >= len(h) else "0 0 0 -7 -7 -7"), (have, line)
+
+
+def test_header_faults_of_the_sort(driver, tmp_path):
+    """one byte string per refusal of pbsim_truth_bam_sort: (return code, fault); and an l_name of 0 is reported, not refused"""
+    import struct
+    SHORT, MAGIC, TEXT, NREF, REFS = 1, 2, 3, 4, 5
+    cases = {
+        "short": (b"BAM\x01" + bytes(7), -1, SHORT),
+        "short_without_magic": (b"@r\nACGT\n+\n", -2, SHORT),
+        "no_magic": (b"@r\nACGT\n+\n!!!!\n", -2, MAGIC),
+        "negative_l_text": (b"BAM\x01" + struct.pack("<i", -1) + bytes(40), -1, TEXT),
+        "l_text_past_the_end": (b"BAM\x01" + struct.pack("<i", 37) + bytes(40), -1, TEXT),
+        "negative_n_ref": (b"BAM\x01" + struct.pack("<ii", 0, -5) + bytes(40), -1, NREF),
+        "list_past_the_end": (b"BAM\x01" + struct.pack("<ii", 0, 2) + struct.pack("<i", 2) + b"a\0" + struct.pack("<i", 9), -1, REFS),
+        "name_past_the_end": (b"BAM\x01" + struct.pack("<iii", 0, 1, 33) + bytes(36), -1, REFS),
+        "negative_l_name": (b"BAM\x01" + struct.pack("<iii", 0, 1, -2) + bytes(40), -1, REFS),
+    }
+    for name, (data, rc, fault) in cases.items():
+        path = tmp_path / name
+        path.write_bytes(data)
+        for cmd in ("header", "header+"):
+            line = run(driver, cmd, path, "%d:%d" % (len(data), len(data)))[0].split()
+            assert int(line[3]) == rc, (name, cmd, line)
+        assert int(line[4]) == fault and line[5:] == ["0", "-7", "-7", "-7"], (name, line)
+    data = b"BAM\x01" + struct.pack("<ii", 0, 2) + struct.pack("<ii", 0, 7) + struct.pack("<i", 2) + b"a\0" + struct.pack("<i", 9) + bytes(5)
+    path = tmp_path / "empty_name"
+    path.write_bytes(data)
+    assert run(driver, "header+", path, "%d:%d" % (len(data), len(data)))[0].endswith("-> 1 0 1 0 2 %d 7 9" % (len(data) - 5))
+    assert run(driver, "header", path, "%d:%d" % (len(data), len(data)))[0].endswith("-> 1 2 %d" % (len(data) - 5))
+
+
+def chain_scenarios(driver, bits):
+    max_block = {28: MAX_BLOCK, 24: SORT_MAX_BLOCK}[bits]
+
     def chain(frm, end, last, hits):
-        return run(driver, "chain", frm, end, int(last), *["%d:%d" % h for h in hits])[0]
+        return run(driver, "chain", bits, frm, end, int(last), *["%d:%d" % h for h in hits])[0]
 
     # three records of 100, 40 and 60 bytes (block_size + 4) behind offset 10
     true = [(10, 96), (110, 36), (150, 56)]
@@ -169,9 +217,21 @@ def test_chain_walk(driver):
     # a candidate that overruns the bytes (the scan gives none) is not followed
     assert chain(10, 190, True, true) == "chain -> malformed 150 2 10:96 110:36"
     assert chain(0, 0, True, []) == "chain -> done 0 0"
-    # the cap: a record may be as large as kBamMaxBlock, a carry never needs to grow beyond one such record
-    assert chain(0, 4 + MAX_BLOCK, False, [(0, MAX_BLOCK)]) == "chain -> done %d 1 0:%d" % (4 + MAX_BLOCK, MAX_BLOCK)
-    assert chain(0, 4 + MAX_BLOCK + 1, True, [(0, MAX_BLOCK + 1)]) == "chain -> malformed 0 0"
-    assert chain(0, 4 + MAX_BLOCK - 1, False, []) == "chain -> carry 0 0"
-    assert chain(0, 4 + MAX_BLOCK, False, []) == "chain -> malformed 0 0"
-    assert chain(100, 100 + 4 + MAX_BLOCK, False, [(0, 96)]) == "chain -> malformed 100 0"
+    # the cap: a record may be as large as the packing's max_block, a carry never needs to grow beyond one such record
+    assert chain(0, 4 + max_block, False, [(0, max_block)]) == "chain -> done %d 1 0:%d" % (4 + max_block, max_block)
+    assert chain(10, 14 + max_block, True, [(10, max_block)]) == "chain -> done %d 1 10:%d" % (14 + max_block, max_block)
+    if bits == 28:      # (the sort's packing has no bits for a larger size: its cap is the mask)
+        assert chain(0, 4 + MAX_BLOCK + 1, True, [(0, MAX_BLOCK + 1)]) == "chain -> malformed 0 0"
+    assert chain(0, 4 + max_block - 1, False, []) == "chain -> carry 0 0"
+    assert chain(0, 4 + max_block, False, []) == "chain -> malformed 0 0"
+    assert chain(100, 100 + 4 + max_block, False, [(0, 96)]) == "chain -> malformed 100 0"
+    assert chain(100, 100 + 4 + (1 << bits), True, []) == "chain -> malformed 100 0"
+
+
+def test_chain_walk(driver):
+    chain_scenarios(driver, 28)
+
+
+def test_chain_walk_with_the_sorts_packing(driver):
+    """offset << 24 | block_size: a record of 2^24 - 1 bytes is followed, 4 + 2^24 bytes without a candidate are malformed"""
+    chain_scenarios(driver, 24)
