@@ -359,6 +359,55 @@ typedef struct pbsim_sorted_bam_sink {
   int (*on_index)(void *user, const char *bytes, int64_t n);               /* the .csi file, once, whole */
 } pbsim_sorted_bam_sink;
 int pbsim_truth_bam_sort(pbsim_ctx *ctx, const void *bam, int64_t n, const pbsim_sorted_bam_sink *sink, int64_t stats[4]);
+/* A mapper's BAM scored against the truth on the GPU: how many simulated reads were mapped back to where they came from, by
+ * MAPQ (what `paftools mapeval` tells of a PAF).  truth[0..n_truth), n_truth >= 1: files of pbsim_set_truth_bam's records, in
+ * task order or sorted (the records pbsim_truth_bam_sort accepts); query[0..n): any BAM, in any order, with secondary,
+ * supplementary, unmapped and paired records.  Each file is BGZF (inflated on the GPU), one plain gzip stream (inflated by
+ * zlib on the host) or an uncompressed BAM stream.
+ * References are matched by name, never by refID.  ref_name (NULL: none) replaces the name of a truth file's reference and is
+ * legal only where the file has exactly one (a wgs truth file calls its reference "ref": ref_name is the FASTA record the
+ * mapper saw).  A query reference that no truth file names matches nothing.  Reads are matched by read name, the bytes in
+ * front of the NUL, over all truth files; a name that occurs twice in the truth (a file given twice, files that repeat a name) is
+ * refused with the name and both files.
+ * A query record with flag & 0x100 is secondary, else with flag & 0x800 supplementary, else primary.  A primary whose name
+ * the truth does not have is unknown.  Of the known primaries of one name the one at the smallest inflated offset is the
+ * first, the others are duplicates.  A first primary with flag & 4 or refID < 0 is unmapped; every other one is scored.  The
+ * interval of a record is [pos, pos + max(1, span)), span the sum of its CIGAR's M, D, N, = and X lengths (the <q>S<span>N
+ * placeholder of a CG-tagged record gives its span so; the tag is not read).  A scored record is correct when its reference
+ * has the truth's name, its flag & 16 is the truth's and, with inter = min(te, qe) - max(ts, qs) and union = max(te, qe) -
+ * min(ts, qs) in 64-bit integers, inter > 0 and inter * 1000 >= overlap_permille * union; else it is wrong.
+ * counts: truth records, query records, primary, secondary, supplementary, unknown, duplicate, unmapped, scored, correct,
+ * wrong, missing (truth reads without a first primary).  hist[2 q], hist[2 q + 1]: the scored records of MAPQ q and the wrong
+ * ones among them.  on_verdicts (sink or the callback may be NULL) is called once with one byte per truth record, in truth
+ * file order then record order: 0 missing, 1 unmapped, 2 wrong, 3 correct; a return of 0 aborts the call.
+ * opts (NULL: the defaults): overlap_permille 1 .. 1000 (0: the default, 100); hash_bits 0 or 64: read names are looked up by
+ * all 64 bits of their hash; 1 .. 63: by that many bits only -- for tests, which so drive every lookup through collisions: the
+ * results must not differ, since a lookup always compares the name bytes (the duplicate check then costs the square of a run).
+ * tests/mapeval_model.py states the rule in plain Python.  The stage holds every inflated stream in HBM at once and does not
+ * chunk: a file that does not fit fails with the bytes the refused allocation needed.  A malformed record fails with its
+ * inflated offset, a query of more than 2^36 inflated bytes is refused, a tables-only context fails as pbsim_inflate_buffer
+ * does.  After any failure the context stays usable and on_verdicts has not been called. */
+typedef struct pbsim_eval_truth {
+  const void *bytes;
+  int64_t n;
+  const char *ref_name; /* NULL: the file's own reference names */
+} pbsim_eval_truth;
+typedef struct pbsim_eval_opts {
+  int32_t overlap_permille;
+  int32_t hash_bits;
+} pbsim_eval_opts;
+typedef struct pbsim_eval_sink {
+  void *user;
+  int (*on_verdicts)(void *user, const unsigned char *bytes, int64_t n);
+} pbsim_eval_sink;
+int pbsim_truth_bam_eval(pbsim_ctx *ctx, const pbsim_eval_truth *truth, int n_truth, const void *query, int64_t n,
+                         const pbsim_eval_opts *opts, const pbsim_eval_sink *sink, int64_t counts[12], int64_t hist[512]);
+/* The report text of counts and hist, no device needed: one line "# truth_records=N query_records=N primary=N secondary=N
+ * supplementary=N unknown=N duplicate=N unmapped=N scored=N correct=N wrong=N missing=N", then for each MAPQ from 255 down
+ * that has scored records "Q\t<mapq>\t<n>\t<wrong>\t<cum n>\t<cum wrong>\t<cum wrong * 1000000 / cum n>\t<cum n * 1000000 /
+ * truth records>" (sums from 255 down to this MAPQ, integer division).  Returns the text's length, and writes it (no NUL)
+ * where buf holds cap >= that many bytes; -1: bad argument. */
+int64_t pbsim_eval_report(const int64_t counts[12], const int64_t hist[512], char *buf, int64_t cap);
 
 /* ---- batch primitives (used by the drivers above, bench.py, multi-GPU) ------
  * pbsim_batch_walk     header draw + bucketing + HMM walk of reads

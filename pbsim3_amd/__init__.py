@@ -138,6 +138,24 @@ class SortedBamSink(C.Structure):
     _fields_ = [("user", C.c_void_p), ("on_bam", SORTED_BAM_CB), ("on_index", SORTED_INDEX_CB)]
 
 
+class EvalTruth(C.Structure):
+    _fields_ = [("bytes", C.c_char_p), ("n", C.c_int64), ("ref_name", C.c_char_p)]
+
+
+class EvalOpts(C.Structure):
+    _fields_ = [("overlap_permille", C.c_int32), ("hash_bits", C.c_int32)]
+
+
+EVAL_VERDICTS_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
+
+
+class EvalSink(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("on_verdicts", EVAL_VERDICTS_CB)]
+
+
+EVAL_COUNTS = ["truth_records", "query_records", "primary", "secondary", "supplementary", "unknown", "duplicate", "unmapped",
+               "scored", "correct", "wrong", "missing"]
+
 # every symbol include/pbsim3_amd.h declares: (name, restype, argtypes)
 API = [
     ("pbsim_job_add_record", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
@@ -221,6 +239,9 @@ API = [
     ("pbsim_inflate_bound", C.c_int64, [C.c_void_p, C.c_int64]),
     ("pbsim_inflate_buffer", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_truth_bam_sort", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(SortedBamSink), C.POINTER(C.c_int64)]),
+    ("pbsim_truth_bam_eval", C.c_int, [C.c_void_p, C.POINTER(EvalTruth), C.c_int, C.c_char_p, C.c_int64, C.POINTER(EvalOpts),
+                                       C.POINTER(EvalSink), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("pbsim_eval_report", C.c_int64, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p, C.c_int64]),
     ("pbsim_batch_walk", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_slot_count", C.c_int, []),
     ("pbsim_select_slot", C.c_int, [C.c_void_p, C.c_int]),
@@ -292,6 +313,20 @@ def load(build_if_missing=True):
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def eval_report(counts, hist) -> bytes:
+    """The report text of Context.eval_bam's counts (the dict, or the twelve values in order) and hist ([256][2]):
+    pbsim_eval_report, no device needed."""
+    vals = [counts[k] for k in EVAL_COUNTS] if isinstance(counts, dict) else list(counts)
+    c = (C.c_int64 * 12)(*[int(v) for v in vals])
+    h = (C.c_int64 * 512)(*[int(v) for row in hist for v in row])
+    n = load().pbsim_eval_report(c, h, None, 0)
+    if n < 0:
+        raise PbsimError("pbsim_eval_report: bad argument")
+    buf = C.create_string_buffer(max(n, 1))
+    load().pbsim_eval_report(c, h, buf, n)
+    return buf.raw[:n]
 
 
 def inflate_bound(data: bytes) -> int:
@@ -790,6 +825,41 @@ class Context:
         stats = (C.c_int64 * 4)()
         _check(self.lib.pbsim_truth_bam_sort(self.h, bytes(data), len(data), C.byref(sink), stats))
         return b"".join(parts), b"".join(index), tuple(stats)
+
+    def eval_bam(self, truth, query, ref_names=None, overlap=0.1, verdicts=False, hash_bits=0):
+        """A mapper's BAM scored against the truth (pbsim_truth_bam_eval; the rule: include/pbsim3_amd.h).  truth: the bytes
+        of one truth BAM or a list of them; query: the bytes of the mapper's BAM; ref_names: per truth file None or the name
+        (str / bytes) its only reference has in the query; overlap: the least intersection / union of a correct mapping,
+        in (0, 1]; hash_bits: see the header (tests only).  Returns (counts, hist, report) -- a dict, a numpy [256, 2] array of
+        (scored, wrong) by MAPQ, the report text -- and with `verdicts` a fourth item: one uint8 per truth record, 0 missing,
+        1 unmapped, 2 wrong, 3 correct."""
+        import numpy as np
+        files = [truth] if isinstance(truth, (bytes, bytearray, memoryview)) else list(truth)
+        names = list(ref_names) if ref_names is not None else [None] * len(files)
+        if len(names) != len(files):
+            raise ValueError("ref_names: one entry per truth file (%d given for %d files)" % (len(names), len(files)))
+        if not 0 < overlap <= 1:
+            raise ValueError("overlap must be in (0, 1]")
+        keep = [bytes(f) for f in files]
+        arr = (EvalTruth * max(len(keep), 1))()
+        for k, (f, nm) in enumerate(zip(keep, names)):
+            arr[k] = EvalTruth(f, len(f), None if nm is None else (nm.encode() if isinstance(nm, str) else bytes(nm)))
+        opts = EvalOpts(max(1, int(round(overlap * 1000))), int(hash_bits))
+        got = []
+
+        def on_verdicts(user, ptr, n):
+            got.append(np.frombuffer(C.string_at(ptr, n), dtype=np.uint8).copy() if n else np.zeros(0, np.uint8))
+            return 1
+        sink = EvalSink(None, EVAL_VERDICTS_CB(on_verdicts))
+        counts = (C.c_int64 * 12)()
+        hist = (C.c_int64 * 512)()
+        query = bytes(query)
+        _check(self.lib.pbsim_truth_bam_eval(self.h, arr, len(keep), query, len(query), C.byref(opts), C.byref(sink) if verdicts else None,
+                                             counts, hist))
+        cd = dict(zip(EVAL_COUNTS, (int(v) for v in counts)))
+        hd = np.array(list(hist), dtype=np.int64).reshape(256, 2)
+        out = (cd, hd, eval_report(cd, hd))
+        return out + (got[0],) if verdicts else out
 
     def set_transcripts(self, ids, plus, minus, seqs):
         """ids: list[str]; plus/minus: expression counts; seqs: list[bytes]."""

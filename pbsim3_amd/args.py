@@ -98,3 +98,50 @@ def truth_sort(a):
     if truth_format(a) != "bam":
         raise ValueError("--truth-sort coordinate sorts the .aln.bam file: it needs --truth-format bam")
     return how
+
+
+def eval_bam(argv):
+    """`pbsim --eval-bam MAPPED.bam --truth-bam FILE [--truth-bam FILE ...] [--truth-ref-names a,b,..] [--eval-overlap 0.1]
+    [--eval-out FILE]` -> dict(query, truth=[...], ref_names=None or [...], overlap, out=None or FILE): the stand-alone mode
+    that scores a mapper's BAM against truth BAMs (pbsim_truth_bam_eval).  --truth-bam repeats, so argv is walked and not
+    zipped into a dict.  What pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
+    takes = ("--eval-bam", "--truth-bam", "--truth-ref-names", "--eval-overlap", "--eval-out", "--device")
+    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
+    got = dict(query=None, truth=[], ref_names=None, overlap=0.1, out=None)
+    if any(a.split("=")[0] in ranks for a in argv):
+        raise ValueError("--eval-bam runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a not in takes:
+            raise ValueError("(%s): --eval-bam takes --truth-bam, --truth-ref-names, --eval-overlap, --eval-out and --device, and no other option." % a)
+        if i + 1 >= len(argv):
+            raise ValueError("(%s): the option needs a value." % a)
+        v = argv[i + 1]
+        i += 2
+        if a == "--eval-bam":
+            got["query"] = v
+        elif a == "--truth-bam":
+            got["truth"].append(v)
+        elif a == "--truth-ref-names":
+            got["ref_names"] = v.split(",")
+        elif a == "--eval-out":
+            got["out"] = v
+        elif a == "--eval-overlap":
+            try:
+                got["overlap"] = float(v)
+            except ValueError:
+                got["overlap"] = -1.0
+            if not 0.0 < got["overlap"] <= 1.0:
+                raise ValueError("(eval-overlap: %s): the least intersection / union of a correct mapping, in (0, 1]." % v)
+    if not got["query"]:
+        raise ValueError("--eval-bam MAPPED.bam: name the mapper's BAM file.")
+    if not got["truth"]:
+        raise ValueError("--eval-bam needs the truth: --truth-bam FILE [--truth-bam FILE ...] (the .aln.bam files of --truth-format bam).")
+    if got["ref_names"] is not None:
+        if len(got["ref_names"]) != len(got["truth"]):
+            raise ValueError("(truth-ref-names): %d names for %d --truth-bam files: the k-th name goes to the k-th file."
+                             % (len(got["ref_names"]), len(got["truth"])))
+        if "" in got["ref_names"]:
+            raise ValueError("(truth-ref-names): an empty name.")
+    return got

@@ -15,6 +15,7 @@
 #include <fcntl.h>
 #include <unistd.h>
 #include <getopt.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -337,6 +338,8 @@ void print_help() {
           "  --truth-format maf|bam (maf): bam writes the truth alignments as <prefix>[_NNNN].aln.bam instead of .maf.gz\n"
           "  --truth-sort coordinate (with --truth-format bam): each finished .aln.bam is sorted by coordinate on the GPU\n"
           "  and indexed (<name>.aln.bam.csi); pbsim --sort-truth-bam FILE [FILE ...] does the same for files made earlier\n"
+          "  pbsim --eval-bam MAPPED.bam --truth-bam FILE [--truth-bam FILE ...] [--truth-ref-names a,b,..] [--eval-overlap (0.1)]\n"
+          "  [--eval-out FILE]: no simulation; a mapper's BAM is scored against the .aln.bam files on the GPU, by MAPQ\n"
           "  --genome, --transcript, --template and --sample may be gzip-compressed (recognised by content): BGZF is\n"
           "  inflated on the GPU, other gzip by zlib on the host; the whole inflated file is held in host memory\n\n");
 }
@@ -977,11 +980,110 @@ void sort_truth_files(pbsim_ctx *ctx, const std::vector<std::string> &names, boo
   }
 }
 
+// `pbsim --eval-bam MAPPED.bam --truth-bam FILE ...`: a mapper's BAM scored against finished truth BAMs (pbsim_truth_bam_eval),
+// the report to stdout or --eval-out.  What can be refused from the command line alone is refused before a GPU is touched.
+struct MappedFile {
+  void *map = MAP_FAILED;
+  size_t n = 0;
+  ~MappedFile() {
+    if (map != MAP_FAILED) munmap(map, n);
+  }
+  bool open_file(const std::string &name) {
+    const int fd = open(name.c_str(), O_RDONLY);
+    struct stat sb;
+    if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size <= 0) {
+      if (fd >= 0) close(fd);
+      return false;
+    }
+    n = (size_t)sb.st_size;
+    map = mmap(NULL, n, PROT_READ, MAP_PRIVATE, fd, 0);
+    close(fd);
+    if (map == MAP_FAILED) return false;
+    (void)madvise(map, n, MADV_SEQUENTIAL);
+    return true;
+  }
+};
+
+int eval_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
+  if (comm && comm->world > 1) die(": --eval-bam runs on one GPU.");
+  std::string query, names_arg, out_name;
+  std::vector<std::string> truth;
+  bool have_names = false;
+  double overlap = 0.1;
+  for (int i = 1; i < argc; i++) {
+    const std::string a = argv[i];
+    const bool takes = a == "--eval-bam" || a == "--truth-bam" || a == "--truth-ref-names" || a == "--eval-overlap" || a == "--eval-out" ||
+                       a == "--device";
+    if (!takes)
+      die(" (%s): --eval-bam takes --truth-bam, --truth-ref-names, --eval-overlap, --eval-out and --device, and no other option.", argv[i]);
+    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
+    const char *v = argv[++i];
+    if (a == "--eval-bam") query = v;
+    else if (a == "--truth-bam") truth.push_back(v);
+    else if (a == "--truth-ref-names") names_arg = v, have_names = true;
+    else if (a == "--eval-out") out_name = v;
+    else if (a == "--device") device = device >= 0 ? device : atoi(v);
+    else {
+      char *e = NULL;
+      overlap = strtod(v, &e);
+      if (e == v || *e || !(overlap > 0.0 && overlap <= 1.0)) die(" (eval-overlap: %s): the least intersection / union of a correct mapping, in (0, 1].", v);
+    }
+  }
+  if (query.empty()) die(": --eval-bam MAPPED.bam: name the mapper's BAM file.");
+  if (truth.empty()) die(": --eval-bam needs the truth: --truth-bam FILE [--truth-bam FILE ...] (the .aln.bam files of --truth-format bam).");
+  std::vector<std::string> names;
+  if (have_names) {
+    for (size_t at = 0;;) {
+      const size_t comma = names_arg.find(',', at);
+      names.push_back(names_arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
+      if (comma == std::string::npos) break;
+      at = comma + 1;
+    }
+    char got[32], want[32];
+    snprintf(got, sizeof got, "%zu", names.size());
+    snprintf(want, sizeof want, "%zu", truth.size());
+    if (names.size() != truth.size()) die(" (truth-ref-names): %s names for %s --truth-bam files: the k-th name goes to the k-th file.", got, want);
+    for (const std::string &n : names)
+      if (n.empty()) die(" (truth-ref-names: %s): an empty name.", names_arg.c_str());
+  }
+  std::vector<MappedFile> files(truth.size() + 1);
+  for (size_t f = 0; f <= truth.size(); f++) {
+    const std::string &name = f < truth.size() ? truth[f] : query;
+    if (!files[f].open_file(name)) die(": Cannot open file: %s", name.c_str());
+  }
+  pbsim_params p;
+  pbsim_params_default(&p);
+  p.strategy = PBSIM_STRATEGY_WGS;
+  p.method = PBSIM_METHOD_ERR;
+  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
+  if (!ctx) check(0);
+  std::vector<pbsim_eval_truth> tr(truth.size());
+  for (size_t f = 0; f < truth.size(); f++) tr[f] = pbsim_eval_truth{files[f].map, (int64_t)files[f].n, have_names ? names[f].c_str() : NULL};
+  pbsim_eval_opts opts = {(int32_t)std::min(1000L, std::max(1L, lround(overlap * 1000))), 0};
+  int64_t counts[12], hist[512];
+  if (!pbsim_truth_bam_eval(ctx, tr.data(), (int)tr.size(), files.back().map, (int64_t)files.back().n, &opts, NULL, counts, hist)) {
+    fprintf(stderr, "ERROR: %s\n", pbsim_last_error());
+    for (size_t f = 0; f < truth.size(); f++) fprintf(stderr, "ERROR: truth file %zu is %s\n", f, truth[f].c_str());
+    quit(-1);
+  }
+  std::string text((size_t)pbsim_eval_report(counts, hist, NULL, 0), '\0');
+  pbsim_eval_report(counts, hist, &text[0], (int64_t)text.size());
+  FILE *fp = out_name.empty() ? stdout : fopen(out_name.c_str(), "wb");
+  if (!fp) die(": Cannot open output file: %s", out_name.c_str());
+  const bool wrote = fwrite(text.data(), 1, text.size(), fp) == text.size();
+  if ((fp == stdout ? fflush(fp) : fclose(fp)) != 0 || !wrote) die(": write error on %s", out_name.empty() ? "the standard output" : out_name.c_str());
+  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
+  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int device) {
   struct timeval tv0;
   gettimeofday(&tv0, NULL);
+  for (int i = 1; i < argc; i++)
+    if (!strcmp(argv[i], "--eval-bam")) return eval_bam_main(argc, argv, comm, device);
   if (argc >= 2 && !strcmp(argv[1], "--sort-truth-bam")) {
     // the standalone mode: no simulation, the named files sorted and indexed in place on one GPU
     if (comm && comm->world > 1) die(": --sort-truth-bam runs on one GPU.");

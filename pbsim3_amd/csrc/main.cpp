@@ -15,6 +15,7 @@
 //                                     rendezvous file of the launch's own under /dev/shm (or $TMPDIR); exit status = the first
 //                                     child's that is not 0
 //   pbsim --sort-truth-bam FILE ..   no simulation: finished truth BAMs sorted by coordinate and indexed in place (cli.cpp)
+//   pbsim --eval-bam MAPPED.bam --truth-bam FILE ..   no simulation: a mapper's BAM scored against truth BAMs (cli.cpp)
 // Every rank runs the same pbsim_cli_main(argv): the job is deterministic in the values the ranks exchange, so they stay
 // in lockstep; rank 0 prints the report and creates the files, every rank writes its own byte ranges.
 #include <hip/hip_runtime.h>
@@ -81,6 +82,19 @@ int main(int argc, char **argv) {
     if (truth_sort && (devices.size() > 1 || n_processes > 0 || proc_world > 0 || proc_rank >= 0 || !rendezvous.empty())) {
       fprintf(stderr, "ERROR: --truth-sort runs on one GPU: run the job without it (several ranks write the same bytes as one) and sort "
                       "the finished files with: pbsim --sort-truth-bam <prefix>[_NNNN].aln.bam\n");
+      return 255;
+    }
+  }
+  {
+    // --eval-bam is a mode of one GPU: the options that start several ranks are refused beside it
+    bool eval_bam = false, ranks = false;
+    for (int i = 1; i < argc; i++) {
+      if (!strcmp(argv[i], "--eval-bam")) eval_bam = true;
+      for (const char *o : {"--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest"})
+        if (!strcmp(argv[i], o) || (!strncmp(argv[i], o, strlen(o)) && argv[i][strlen(o)] == '=')) ranks = true;
+    }
+    if (eval_bam && ranks) {
+      fprintf(stderr, "ERROR: --eval-bam runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.\n");
       return 255;
     }
   }
