@@ -408,6 +408,61 @@ int pbsim_truth_bam_eval(pbsim_ctx *ctx, const pbsim_eval_truth *truth, int n_tr
  * truth records>" (sums from 255 down to this MAPQ, integer division).  Returns the text's length, and writes it (no NUL)
  * where buf holds cap >= that many bytes; -1: bad argument. */
 int64_t pbsim_eval_report(const int64_t counts[12], const int64_t hist[512], char *buf, int64_t cap);
+/* The depth of coverage of a BAM on the GPU: how many records cover each reference position (what `samtools depth -a`,
+ * `bedtools genomecov -bga` or `mosdepth` tell).  bam[0..n) is a truth BAM, sorted or not, or a mapper's BAM: BGZF (inflated
+ * on the GPU), one plain gzip stream (zlib on the host) or an uncompressed BAM stream; any record pbsim_truth_bam_eval takes
+ * as a query record is taken here.
+ * A record is skipped, and counted, in this order: skipped_flag if flag & exclude_flags (default 0x704: unmapped, secondary,
+ * QC-fail, duplicate; supplementary records count); else skipped_unplaced if refID < 0 or pos < 0; else skipped_mapq if
+ * mapq < min_mapq.  Nothing more of a skipped record is looked at.  Every other record is counted.
+ * The CIGAR of a counted record is its CIGAR field -- except where n_cigar_op == 2, op 0 is S with length l_seq, op 1 is N and
+ * the record has a CG tag of type B,I: then it is the array in that tag (SAMv1 4.2.2; truth records of more than 65535 runs
+ * are written so, and the placeholder taken literally covers nothing).  The tag is looked for in such a record only, by
+ * walking its aux fields by type (A c C s S i I f Z H B); an aux field that runs past the record or has an unknown type
+ * fails the call with the record's inflated offset, and so does a CIGAR op code above 8 in a counted record.
+ * The reference position starts at pos and advances over M D N = X.  M, = and X cover; D covers when count_deletions is not 0
+ * (the default: the truth of an error-laden long read has a deletion every few dozen bases); N never covers; I S H P
+ * neither advance nor cover.  Positions at or beyond the reference's l_ref are not counted, and a record that loses at least
+ * one covered position so is counted in clipped.  A record that covers nothing is counted and adds no depth.
+ * depth[ref][p] is the number of counted records that cover p, an int32: a file of 2^31 records or more is refused.  All of it
+ * is integer arithmetic: the result is a function of the input alone, whatever the order of the records.
+ * The text, through on_text in offset order, in pieces of at most piece_bytes (a piece may end inside a line), the references
+ * in header order, none for a reference with l_ref == 0, name the bytes in front of the first NUL:
+ *   format 0, bedgraph: the maximal runs of equal depth over [0, l_ref), zero runs too: "name\tstart\tend\tdepth\n";
+ *   format 1, window (window >= 1): for k = 0, 1, ..: [k window, min((k + 1) window, l_ref)): "name\tstart\tend\tsum\tmean_milli\n",
+ *   sum the 64-bit sum of the depths, mean_milli = sum * 1000 / (end - start), integer division.
+ * counts: records, counted, skipped_flag, skipped_unplaced, skipped_mapq, clipped.  hist[d]: over all references the positions
+ * of depth d, hist[255] those of depth >= 255.  on_refs, once and before any text: per reference l_ref, covered positions
+ * (depth >= 1), the 64-bit sum of depths, the largest depth.  on_depth, after the text and only where it is not NULL: a host
+ * copy of each reference's depths, in header order.  sink and each callback may be NULL; a callback that returns 0 aborts
+ * the call.  tests/depth_model.py states the rule in plain Python.
+ * The stage holds the inflated stream and the depth array -- 4 bytes per reference position, 12 GB for a 3 Gbp header -- in HBM
+ * at once and does not chunk: what does not fit fails with the bytes the refused allocation needed.  format outside 0 and 1,
+ * window < 1 with format 1, min_mapq outside 0 .. 255 and a negative piece_bytes fail before any device work; a malformed
+ * record fails with its inflated offset, a file of 2^36 inflated bytes or more is refused, a tables-only context fails as
+ * pbsim_inflate_buffer does.  After any failure the context stays usable. */
+typedef struct pbsim_depth_opts { /* NULL: {0x704, 0, 1, 0, 0, 0} */
+  int32_t exclude_flags, min_mapq, count_deletions;
+  int32_t format;      /* 0 bedgraph, 1 window */
+  int64_t window;      /* format 1: >= 1 */
+  int64_t piece_bytes; /* 0: the default; else the most text one on_text call carries (tests drive many pieces with it) */
+} pbsim_depth_opts;
+typedef struct pbsim_depth_sink {
+  void *user;
+  int (*on_text)(void *user, const char *bytes, int64_t n, int64_t offset); /* in offset order; may be NULL */
+  int (*on_refs)(void *user, int32_t n_ref, const char *const *names,
+                 const int64_t *rows /* n_ref x 4: l_ref, covered, sum, max */); /* once, before any on_text; may be NULL */
+  int (*on_depth)(void *user, int32_t ref, const int32_t *depth, int64_t l_ref); /* host copy, per reference in order, after
+                                                                                     the text; may be NULL: then nothing is copied */
+} pbsim_depth_sink;
+int pbsim_bam_depth(pbsim_ctx *ctx, const void *bam, int64_t n, const pbsim_depth_opts *opts,
+                    const pbsim_depth_sink *sink, int64_t counts[6], int64_t hist[256]);
+/* The report text, no device needed: one line "# records=N counted=N skipped_flag=N skipped_unplaced=N skipped_mapq=N
+ * clipped=N", then per reference with l_ref > 0 "R\t<name>\t<l_ref>\t<covered>\t<sum>\t<max>\t<sum * 1000 / l_ref>" (integer
+ * division), then for each d with hist[d] > 0, ascending, "H\t<d>\t<positions>".  names[r]: NUL-terminated.  Returns the text's
+ * length, and writes it (no NUL) where buf holds cap >= that many bytes; -1: bad argument. */
+int64_t pbsim_depth_report(const int64_t counts[6], int32_t n_ref, const char *const *names, const int64_t *rows,
+                           const int64_t hist[256], char *buf, int64_t cap);
 
 /* ---- batch primitives (used by the drivers above, bench.py, multi-GPU) ------
  * pbsim_batch_walk     header draw + bucketing + HMM walk of reads

@@ -156,6 +156,24 @@ class EvalSink(C.Structure):
 EVAL_COUNTS = ["truth_records", "query_records", "primary", "secondary", "supplementary", "unknown", "duplicate", "unmapped",
                "scored", "correct", "wrong", "missing"]
 
+
+class DepthOpts(C.Structure):
+    _fields_ = [("exclude_flags", C.c_int32), ("min_mapq", C.c_int32), ("count_deletions", C.c_int32), ("format", C.c_int32),
+                ("window", C.c_int64), ("piece_bytes", C.c_int64)]
+
+
+DEPTH_TEXT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64)
+DEPTH_REFS_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64))
+DEPTH_ARRAY_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64)
+
+
+class DepthSink(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("on_text", DEPTH_TEXT_CB), ("on_refs", DEPTH_REFS_CB), ("on_depth", DEPTH_ARRAY_CB)]
+
+
+DEPTH_COUNTS = ["records", "counted", "skipped_flag", "skipped_unplaced", "skipped_mapq", "clipped"]
+DEPTH_FORMATS = {"bedgraph": 0, "window": 1}
+
 # every symbol include/pbsim3_amd.h declares: (name, restype, argtypes)
 API = [
     ("pbsim_job_add_record", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
@@ -242,6 +260,10 @@ API = [
     ("pbsim_truth_bam_eval", C.c_int, [C.c_void_p, C.POINTER(EvalTruth), C.c_int, C.c_char_p, C.c_int64, C.POINTER(EvalOpts),
                                        C.POINTER(EvalSink), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("pbsim_eval_report", C.c_int64, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p, C.c_int64]),
+    ("pbsim_bam_depth", C.c_int, [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(DepthOpts), C.POINTER(DepthSink), C.POINTER(C.c_int64),
+                                  C.POINTER(C.c_int64)]),
+    ("pbsim_depth_report", C.c_int64, [C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                       C.c_char_p, C.c_int64]),
     ("pbsim_batch_walk", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_slot_count", C.c_int, []),
     ("pbsim_select_slot", C.c_int, [C.c_void_p, C.c_int]),
@@ -326,6 +348,23 @@ def eval_report(counts, hist) -> bytes:
         raise PbsimError("pbsim_eval_report: bad argument")
     buf = C.create_string_buffer(max(n, 1))
     load().pbsim_eval_report(c, h, buf, n)
+    return buf.raw[:n]
+
+
+def depth_report(counts, refs, hist) -> bytes:
+    """The report text of Context.bam_depth's counts (the dict, or the six values in order), refs (a list of (name, l_ref,
+    covered, sum, max)) and hist (256 values): pbsim_depth_report, no device needed."""
+    vals = [counts[k] for k in DEPTH_COUNTS] if isinstance(counts, dict) else list(counts)
+    refs = list(refs)
+    c = (C.c_int64 * 6)(*[int(v) for v in vals])
+    h = (C.c_int64 * 256)(*[int(v) for v in hist])
+    names = (C.c_char_p * max(len(refs), 1))(*[r[0].encode() if isinstance(r[0], str) else bytes(r[0]) for r in refs])
+    rows = (C.c_int64 * max(4 * len(refs), 1))(*[int(v) for r in refs for v in r[1:5]])
+    n = load().pbsim_depth_report(c, len(refs), names, rows, h, None, 0)
+    if n < 0:
+        raise PbsimError("pbsim_depth_report: bad argument")
+    buf = C.create_string_buffer(max(n, 1))
+    load().pbsim_depth_report(c, len(refs), names, rows, h, buf, n)
     return buf.raw[:n]
 
 
@@ -860,6 +899,41 @@ class Context:
         hd = np.array(list(hist), dtype=np.int64).reshape(256, 2)
         out = (cd, hd, eval_report(cd, hd))
         return out + (got[0],) if verdicts else out
+
+    def bam_depth(self, data, fmt="bedgraph", window=0, min_mapq=0, exclude_flags=0x704, deletions=True, arrays=False, piece_bytes=0):
+        """The depth of coverage of a BAM (pbsim_bam_depth; the rule: include/pbsim3_amd.h).  data: the bytes of a truth BAM
+        or a mapper's BAM; fmt: "bedgraph" (runs of equal depth) or "window" (sums over windows of `window` positions).  Returns
+        (text, counts, refs, hist, report): the text's bytes, a dict, a list of (name, l_ref, covered, sum, max), a numpy
+        int64[256] and the report text -- and with `arrays` a sixth item, a list of numpy int32 arrays, one per reference."""
+        import numpy as np
+        if fmt not in DEPTH_FORMATS:
+            raise ValueError("fmt must be bedgraph or window")
+        parts, at, refs, depth = [], [0], [], []
+
+        def on_text(user, ptr, n, offset):
+            if offset != at[0]:      # (the pieces come in offset order)
+                return 0
+            parts.append(C.string_at(ptr, n))
+            at[0] += n
+            return 1
+
+        def on_refs(user, n_ref, names, rows):
+            refs.extend((names[r],) + tuple(int(rows[4 * r + k]) for k in range(4)) for r in range(n_ref))
+            return 1
+
+        def on_depth(user, ref, ptr, l_ref):
+            depth.append(np.frombuffer(C.string_at(ptr, 4 * l_ref), dtype=np.int32).copy() if l_ref else np.zeros(0, np.int32))
+            return 1
+        sink = DepthSink(None, DEPTH_TEXT_CB(on_text), DEPTH_REFS_CB(on_refs), DEPTH_ARRAY_CB(on_depth) if arrays else DEPTH_ARRAY_CB())
+        opts = DepthOpts(int(exclude_flags), int(min_mapq), 1 if deletions else 0, DEPTH_FORMATS[fmt], int(window), int(piece_bytes))
+        counts = (C.c_int64 * 6)()
+        hist = (C.c_int64 * 256)()
+        data = bytes(data)
+        _check(self.lib.pbsim_bam_depth(self.h, data, len(data), C.byref(opts), C.byref(sink), counts, hist))
+        cd = dict(zip(DEPTH_COUNTS, (int(v) for v in counts)))
+        hd = np.array(list(hist), dtype=np.int64)
+        out = (b"".join(parts), cd, refs, hd, depth_report(cd, refs, hd))
+        return out + (depth,) if arrays else out
 
     def set_transcripts(self, ids, plus, minus, seqs):
         """ids: list[str]; plus/minus: expression counts; seqs: list[bytes]."""

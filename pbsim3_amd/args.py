@@ -145,3 +145,72 @@ def eval_bam(argv):
         if "" in got["ref_names"]:
             raise ValueError("(truth-ref-names): an empty name.")
     return got
+
+
+def _whole(v, base=10):
+    """a whole number written with digits only (what the command line takes), or None"""
+    body = v[2:] if base == 16 else v
+    digits = "0123456789abcdefABCDEF" if base == 16 else "0123456789"
+    if not body or any(ch not in digits for ch in body):
+        return None
+    return int(body, base)
+
+
+def depth_bam(argv):
+    """`pbsim --depth-bam FILE --depth-out FILE [--depth-format bedgraph|window] [--depth-window N] [--depth-min-mapq Q]
+    [--depth-exclude-flags F] [--depth-no-deletions]` -> dict(bam, out, format, window, min_mapq, exclude_flags, deletions): the
+    stand-alone mode that writes the depth of coverage of a BAM (pbsim_bam_depth).  F is decimal or 0x hexadecimal.  What
+    pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
+    takes = ("--depth-bam", "--depth-out", "--depth-format", "--depth-window", "--depth-min-mapq", "--depth-exclude-flags", "--device")
+    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
+    got = dict(bam=None, out=None, format="bedgraph", window=0, min_mapq=0, exclude_flags=0x704, deletions=True)
+    if any(a.split("=")[0] in ranks for a in argv):
+        raise ValueError("--depth-bam runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
+    have_window = False
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a == "--depth-no-deletions":
+            got["deletions"] = False
+            i += 1
+            continue
+        if a not in takes:
+            raise ValueError("(%s): --depth-bam takes --depth-out, --depth-format, --depth-window, --depth-min-mapq, --depth-exclude-flags, "
+                             "--depth-no-deletions and --device, and no other option." % a)
+        if i + 1 >= len(argv):
+            raise ValueError("(%s): the option needs a value." % a)
+        v = argv[i + 1]
+        i += 2
+        if a == "--depth-bam":
+            got["bam"] = v
+        elif a == "--depth-out":
+            got["out"] = v
+        elif a == "--depth-format":
+            if v not in ("bedgraph", "window"):
+                raise ValueError("(depth-format: %s): bedgraph or window." % v)
+            got["format"] = v
+        elif a == "--depth-window":
+            have_window = True
+            n = _whole(v)
+            if n is None or not 1 <= n < 2 ** 63:
+                raise ValueError("(depth-window: %s): a whole number of at least 1." % v)
+            got["window"] = n
+        elif a == "--depth-min-mapq":
+            n = _whole(v)
+            if n is None or n > 255:
+                raise ValueError("(depth-min-mapq: %s): a whole number, 0 .. 255." % v)
+            got["min_mapq"] = n
+        elif a == "--depth-exclude-flags":
+            n = _whole(v, 16 if v[:2] in ("0x", "0X") else 10)
+            if n is None or n > 65535:
+                raise ValueError("(depth-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535." % v)
+            got["exclude_flags"] = n
+    if not got["bam"]:
+        raise ValueError("--depth-bam FILE: name the BAM file.")
+    if not got["out"]:
+        raise ValueError("--depth-bam needs --depth-out FILE: the bedGraph or window text goes there (the report goes to the standard output).")
+    if got["format"] == "window" and not have_window:
+        raise ValueError("--depth-format window needs --depth-window N.")
+    if got["format"] != "window" and have_window:
+        raise ValueError("--depth-window N goes with --depth-format window.")
+    return got

@@ -1,12 +1,10 @@
 // bam_eval.cpp -- pbsim_truth_bam_eval: a mapper's BAM scored against the truth BAMs (the rule: include/pbsim3_amd.h,
-// tests/mapeval_model.py).  The host's part: the containers, the headers, what to say when bam_chain.cpp's header parse or chain
-// walk refuses a stream, the references by name (bam_eval_rule.cpp) and the counts; the kernels are inflate.hip's,
-// bam_scan.hip's, bam_sort.hip's sort and bam_eval.hip's.
+// tests/mapeval_model.py).  The host's part: the streams into HBM and their records (bam_stream.cpp), the references by name
+// (bam_eval_rule.cpp) and the counts; the kernels are inflate.hip's, bam_scan.hip's, bam_sort.hip's sort and bam_eval.hip's.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <zlib.h>
 
 #include <algorithm>
 #include <string>
@@ -16,8 +14,8 @@
 #include "bam_fields.h"
 #include "bam_scan.h"
 #include "bam_sort.h"
+#include "bam_stream.h"
 #include "ctx.h"
-#include "inflate_host.h"
 
 namespace pbsim {
 
@@ -25,179 +23,11 @@ namespace {
 
 const char kWho[] = "pbsim_truth_bam_eval: ";
 
-int out_of_memory(const char *what, size_t want) {
-  return fail(std::string(kWho) + "out of device memory: " + what + " needs " + std::to_string(want) +
-              " bytes (the stage holds every inflated stream and its records' keys in HBM at once and does not chunk)");
-}
-int alloc(DevBuf &b, int64_t n, const char *what) {
-  b.release();
-  const size_t want = (size_t)std::max<int64_t>(n, 256);
-  if (b.ensure(want, /*exact=*/true) != hipSuccess) {
-    (void)hipGetLastError();
-    return out_of_memory(what, want);
-  }
-  return PBSIM_SUCCEEDED;
-}
+const BamStage kStage = {kWho, "the stage holds every inflated stream and its records' keys in HBM at once and does not chunk"};
 
-const char *const kHeaderFault[] = {"",
-                                    "shorter than a BAM header",
-                                    "no BAM\\1 magic",
-                                    "l_text runs past the end",
-                                    "n_ref is negative",
-                                    "the reference list runs past the end"};
+int alloc(DevBuf &b, int64_t n, const char *what) { return bam_stage_alloc(kStage, b, n, what); }
 
-// The phases on the stream's own clock (PBSIM_TRACE): an event where each ends.  What the host does between two events -- the
-// chain walk, the tables -- falls into the phase it belongs to, since the stream is idle meanwhile.
-struct Phases {
-  bool on = getenv("PBSIM_TRACE") != nullptr;
-  hipStream_t st;
-  std::vector<hipEvent_t> ev;
-  std::vector<std::string> name;
-  explicit Phases(hipStream_t s) : st(s) { mark(""); }
-  ~Phases() {
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-  }
-  void mark(const std::string &what) {
-    if (!on) return;
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return;
-    (void)hipEventRecord(e, st);
-    ev.push_back(e);
-    name.push_back(what);
-  }
-  void print(int64_t inflated, int64_t n_truth, int64_t n_query) {
-    if (!on || ev.empty()) return;
-    (void)hipEventSynchronize(ev.back());
-    float total = 0;
-    for (size_t k = 1; k < ev.size(); k++) {
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, ev[k - 1], ev[k]);
-      total += ms;
-      fprintf(stderr, "[pbsim eval] %9.2f ms  %s\n", ms, name[k].c_str());
-    }
-    fprintf(stderr, "[pbsim eval] %9.2f ms  total: %.1f MB inflated, %lld truth records, %lld query records\n", total, inflated / 1e6,
-            (long long)n_truth, (long long)n_query);
-  }
-};
-
-struct Stream {
-  std::string what;  // "truth file 0", "the query"
-  DevBuf d;
-  int64_t N = 0, H = 0;
-  BamHeader hd;
-  std::vector<std::string> ref_names;
-  std::vector<uint64_t> rec;
-  const uint8_t *bytes() const { return (const uint8_t *)d.p; }
-};
-
-// one gzip stream (concatenated members are one stream) through zlib
-bool gunzip(const uint8_t *src, int64_t n, std::vector<uint8_t> *out, std::string *err) {
-  z_stream z;
-  memset(&z, 0, sizeof z);
-  if (inflateInit2(&z, 16 + MAX_WBITS) != Z_OK) {
-    *err = "zlib: inflateInit2 failed";
-    return false;
-  }
-  out->clear();
-  std::vector<uint8_t> piece((size_t)4 << 20);
-  int64_t at = 0;
-  for (;;) {
-    const int64_t take = std::min<int64_t>(n - at, (int64_t)1 << 30);
-    z.next_in = const_cast<Bytef *>(src + at);
-    z.avail_in = (uInt)take;
-    z.next_out = piece.data();
-    z.avail_out = (uInt)piece.size();
-    const int rc = inflate(&z, Z_NO_FLUSH);
-    at += take - (int64_t)z.avail_in;
-    out->insert(out->end(), piece.data(), piece.data() + (piece.size() - z.avail_out));
-    if (rc == Z_STREAM_END) {
-      if (at >= n) break;
-      if (inflateReset(&z) == Z_OK) continue;  // the next member
-    } else if (rc == Z_OK && (at < n || z.avail_out == 0)) {
-      continue;  // more input to give, or more output to take
-    }
-    // no progress is possible: the data is damaged, or it breaks off
-    *err = std::string("gzip data does not inflate: ") + (z.msg ? z.msg : "it breaks off");
-    inflateEnd(&z);
-    return false;
-  }
-  inflateEnd(&z);
-  return true;
-}
-
-// the container: BGZF is inflated on the GPU, one plain gzip stream by zlib on the host, "BAM\1" is the stream itself
-int inflate_stream(pbsim_ctx *c, const uint8_t *src, int64_t n, Stream *s) {
-  hipStream_t st = c->stream;
-  const std::string who = kWho + s->what + ": ";
-  std::vector<BgzfMember> mem;
-  std::vector<uint8_t> host;
-  const uint8_t *plain = nullptr;
-  if (n >= 4 && memcmp(src, "BAM\1", 4) == 0) {
-    plain = src;
-    s->N = n;
-  } else if (n >= 2 && src[0] == 0x1f && src[1] == 0x8b) {
-    if (bgzf_index(src, n, &mem)) {
-      s->N = bgzf_inflated_size(mem);
-    } else {
-      std::string err;
-      if (!gunzip(src, n, &host, &err)) return fail(who + err);
-      plain = host.data();
-      s->N = (int64_t)host.size();
-    }
-  } else {
-    return fail(who + "neither BGZF, gzip nor an uncompressed BAM stream");
-  }
-  if (!alloc(s->d, s->N + kBamSlack, "an inflated stream")) return PBSIM_FAILED;
-  uint8_t *d = s->d.as<uint8_t>();
-  HIP_OK(hipMemsetAsync(d + s->N, 0, (size_t)kBamSlack, st));
-  if (plain) {
-    if (s->N > 0) HIP_OK(hipMemcpyAsync(d, plain, (size_t)s->N, hipMemcpyHostToDevice, st));
-  } else if (!inflate_members(c, src, mem, d, true)) {
-    return fail(who + g_err);
-  }
-  HIP_OK(hipStreamSynchronize(st));  // (`host` goes with this frame)
-  return PBSIM_SUCCEEDED;
-}
-
-// the header, then the records: the scan's candidates and the chain over them
-int locate(pbsim_ctx *c, Stream *s, BamScan *scan, BamScanPolicy policy, BamPacking pk) {
-  hipStream_t st = c->stream;
-  const std::string who = kWho + s->what + ": ";
-  const int64_t N = s->N;
-  if (pk.size_bits > 24 && N >= ((int64_t)1 << (64 - pk.size_bits)))
-    return fail(who + std::to_string(N) + " inflated bytes: a query of 2^36 bytes or more is not taken (its records are packed as offset << 28 | block_size)");
-  std::vector<uint8_t> hbytes;
-  for (int64_t have = std::min<int64_t>(N, 64 << 10);; have = std::min<int64_t>(N, have * 4)) {
-    hbytes.resize((size_t)have);
-    if (have) HIP_OK(hipMemcpy(hbytes.data(), s->d.p, (size_t)have, hipMemcpyDeviceToHost));
-    const int ok = bam_parse_header(hbytes.data(), have, N, true, &s->hd);
-    if (ok < 0 || s->hd.fault) return fail(who + "not a BAM file: " + kHeaderFault[s->hd.fault]);
-    if (ok > 0) break;
-    if (have >= N) return fail(who + "not a BAM file: the header runs past the end");
-  }
-  bam_ref_names(hbytes.data(), s->hd, &s->ref_names);
-  s->H = s->hd.first_record;
-  std::vector<uint64_t> cand;
-  const hipError_t e = scan->run(policy, s->bytes(), s->H, N, (int32_t)s->hd.n_ref, st, &cand);
-  if (e == hipErrorOutOfMemory && scan->oom_what) return out_of_memory(scan->oom_what, scan->oom_bytes);
-  HIP_OK(e);
-  int64_t stop = 0;
-  s->rec.clear();
-  if (bam_walk_chain(pk, cand.data(), cand.size(), s->H, N, true, &s->rec, &stop) != kBamChainDone) {
-    char m[640];
-    int k = snprintf(m, sizeof m, "the record at inflated byte offset %lld does not fit (%s, l_seq >= 0, a block_size that covers its fields and ends "
-                                  "inside the stream of %lld bytes)",
-                     (long long)stop,
-                     policy == kBamScanPlaced ? "a placed single-end record of a truth BAM: 0 <= refID < n_ref, pos >= 0, next_refID = next_pos = -1, tlen = 0"
-                                              : "refID and next_refID in [-1, n_ref), pos and next_pos >= -1, a read name that ends with a NUL",
-                     (long long)N);
-    if (!s->rec.empty())
-      snprintf(m + k, sizeof m - (size_t)k, "; the block_size %u of the record before it, at offset %lld, leads there", (uint32_t)pk.size(s->rec.back()),
-               (long long)pk.offset(s->rec.back()));
-    return fail(who + m);
-  }
-  return PBSIM_SUCCEEDED;
-}
+typedef BamStream Stream;
 
 // the read name of the record at `offset` of a stream
 int name_at(const Stream &s, int64_t offset, std::string *name) {
@@ -212,27 +42,27 @@ int name_at(const Stream &s, int64_t offset, std::string *name) {
 int eval_bam(pbsim_ctx *c, const pbsim_eval_truth *truth, int n_truth_files, const uint8_t *query, int64_t n_query_bytes, int32_t permille,
              int hash_bits, const pbsim_eval_sink *sink, int64_t counts[kEvalCounts], int64_t hist[512]) {
   hipStream_t st = c->stream;
-  Phases ph(st);
+  BamPhases ph(st, "eval");
   // ---- 1. every stream into HBM
   std::vector<Stream> tr((size_t)n_truth_files);
   Stream qu;
   qu.what = "the query";
   for (int f = 0; f < n_truth_files; f++) {
     tr[(size_t)f].what = "truth file " + std::to_string(f);
-    if (!inflate_stream(c, (const uint8_t *)truth[f].bytes, truth[f].n, &tr[(size_t)f])) return PBSIM_FAILED;
+    if (!bam_inflate_stream(c, kStage, (const uint8_t *)truth[f].bytes, truth[f].n, &tr[(size_t)f])) return PBSIM_FAILED;
   }
-  if (!inflate_stream(c, query, n_query_bytes, &qu)) return PBSIM_FAILED;
+  if (!bam_inflate_stream(c, kStage, query, n_query_bytes, &qu)) return PBSIM_FAILED;
   ph.mark("inflate");
   // ---- 2. the records of each
   int64_t inflated = qu.N;
   {
     BamScan scan;
     for (Stream &s : tr) {
-      if (!locate(c, &s, &scan, kBamScanPlaced, kBamSortPacking)) return PBSIM_FAILED;
+      if (!bam_locate(c, kStage, &s, &scan, kBamScanPlaced, kBamSortPacking)) return PBSIM_FAILED;
       inflated += s.N;
       ph.mark("scan + chain, " + s.what);
     }
-    if (!locate(c, &qu, &scan, kBamScanAny, kBamSamplePacking)) return PBSIM_FAILED;
+    if (!bam_locate(c, kStage, &qu, &scan, kBamScanAny, kBamSamplePacking)) return PBSIM_FAILED;
     ph.mark("scan + chain, " + qu.what);
   }
   std::vector<int64_t> first_record;  // of each truth file, among all truth records
@@ -339,7 +169,11 @@ int eval_bam(pbsim_ctx *c, const pbsim_eval_truth *truth, int n_truth_files, con
   }
   HIP_OK(hipStreamSynchronize(st));
   ph.mark("join + verdict");
-  ph.print(inflated, n_t, n_q);
+  {
+    char sum[160];
+    snprintf(sum, sizeof sum, "%.1f MB inflated, %lld truth records, %lld query records", inflated / 1e6, (long long)n_t, (long long)n_q);
+    ph.print(sum);
+  }
   const uint64_t *cls = h_small.data() + kCls, *res = h_small.data() + kRes;  // cls: primary, secondary, supplementary, unknown, known
   counts[kEvalTruth] = n_t;
   counts[kEvalQuery] = n_q;

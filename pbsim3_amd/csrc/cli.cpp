@@ -12,7 +12,10 @@
 //
 // wgs (errhmm / qshmm) runs as ONE job over all records (pbsim_job_run): the records are resident in HBM, and on several
 // ranks every rank pwrite()s its own byte ranges of the final files.  Rank 0 alone prints and creates files.
+#include <ctype.h>
+#include <errno.h>
 #include <fcntl.h>
+#include <limits.h>
 #include <unistd.h>
 #include <getopt.h>
 #include <math.h>
@@ -340,6 +343,9 @@ void print_help() {
           "  and indexed (<name>.aln.bam.csi); pbsim --sort-truth-bam FILE [FILE ...] does the same for files made earlier\n"
           "  pbsim --eval-bam MAPPED.bam --truth-bam FILE [--truth-bam FILE ...] [--truth-ref-names a,b,..] [--eval-overlap (0.1)]\n"
           "  [--eval-out FILE]: no simulation; a mapper's BAM is scored against the .aln.bam files on the GPU, by MAPQ\n"
+          "  pbsim --depth-bam FILE --depth-out FILE [--depth-format bedgraph|window (bedgraph)] [--depth-window N]\n"
+          "  [--depth-min-mapq Q (0)] [--depth-exclude-flags F (0x704)] [--depth-no-deletions]: no simulation; the depth of coverage\n"
+          "  of a truth BAM or a mapper's BAM on the GPU: bedGraph runs or fixed windows to --depth-out, a summary to stdout\n"
           "  --genome, --transcript, --template and --sample may be gzip-compressed (recognised by content): BGZF is\n"
           "  inflated on the GPU, other gzip by zlib on the host; the whole inflated file is held in host memory\n\n");
 }
@@ -1077,6 +1083,106 @@ int eval_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
   return 0;
 }
 
+// `pbsim --depth-bam FILE --depth-out FILE ...`: the depth of coverage of a BAM (pbsim_bam_depth), the text to --depth-out, the
+// report to stdout.  What can be refused from the command line alone is refused before a GPU is touched.
+bool whole_number(const char *v, int base, long long lo, long long hi, long long *out) {
+  char *e = NULL;
+  errno = 0;
+  const long long x = strtoll(v, &e, base);
+  if (e == v || *e || errno || x < lo || x > hi || !(isdigit((unsigned char)v[0]))) return false;
+  *out = x;
+  return true;
+}
+
+int depth_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
+  if (comm && comm->world > 1) die(": --depth-bam runs on one GPU.");
+  std::string in_name, out_name, format = "bedgraph";
+  long long window = 0, min_mapq = 0, exclude = 0x704;
+  bool have_window = false, deletions = true;
+  for (int i = 1; i < argc; i++) {
+    const std::string a = argv[i];
+    if (a == "--depth-no-deletions") {
+      deletions = false;
+      continue;
+    }
+    const bool takes = a == "--depth-bam" || a == "--depth-out" || a == "--depth-format" || a == "--depth-window" || a == "--depth-min-mapq" ||
+                       a == "--depth-exclude-flags" || a == "--device";
+    if (!takes)
+      die(" (%s): --depth-bam takes --depth-out, --depth-format, --depth-window, --depth-min-mapq, --depth-exclude-flags, --depth-no-deletions "
+          "and --device, and no other option.",
+          argv[i]);
+    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
+    const char *v = argv[++i];
+    if (a == "--depth-bam") in_name = v;
+    else if (a == "--depth-out") out_name = v;
+    else if (a == "--device") device = device >= 0 ? device : atoi(v);
+    else if (a == "--depth-format") {
+      format = v;
+      if (format != "bedgraph" && format != "window") die(" (depth-format: %s): bedgraph or window.", v);
+    } else if (a == "--depth-window") {
+      have_window = true;
+      if (!whole_number(v, 10, 1, LLONG_MAX, &window)) die(" (depth-window: %s): a whole number of at least 1.", v);
+    } else if (a == "--depth-min-mapq") {
+      if (!whole_number(v, 10, 0, 255, &min_mapq)) die(" (depth-min-mapq: %s): a whole number, 0 .. 255.", v);
+    } else {
+      const bool hex = v[0] == '0' && (v[1] == 'x' || v[1] == 'X');
+      if (!whole_number(v, hex ? 16 : 10, 0, 65535, &exclude)) die(" (depth-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535.", v);
+    }
+  }
+  if (in_name.empty()) die(": --depth-bam FILE: name the BAM file.");
+  if (out_name.empty()) die(": --depth-bam needs --depth-out FILE: the bedGraph or window text goes there (the report goes to the standard output).");
+  if (format == "window" && !have_window) die(": --depth-format window needs --depth-window N.");
+  if (format != "window" && have_window) die(": --depth-window N goes with --depth-format window.");
+  MappedFile file;
+  if (!file.open_file(in_name)) die(": Cannot open file: %s", in_name.c_str());
+  pbsim_params p;
+  pbsim_params_default(&p);
+  p.strategy = PBSIM_STRATEGY_WGS;
+  p.method = PBSIM_METHOD_ERR;
+  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
+  if (!ctx) check(0);
+  struct Result {
+    FILE *fp = NULL;
+    bool write_failed = false;
+    std::vector<std::string> names;
+    std::vector<int64_t> rows;
+  } res;
+  res.fp = fopen(out_name.c_str(), "wb");
+  if (!res.fp) die(": Cannot open output file: %s", out_name.c_str());
+  pbsim_depth_opts opts = {(int32_t)exclude, (int32_t)min_mapq, deletions ? 1 : 0, format == "window" ? 1 : 0, (int64_t)window, 0};
+  pbsim_depth_sink sink = {&res,
+                           [](void *u, const char *z, int64_t k, int64_t) {
+                             Result *x = (Result *)u;
+                             if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
+                             return x->write_failed ? 0 : 1;
+                           },
+                           [](void *u, int32_t n_ref, const char *const *names, const int64_t *rows) {
+                             Result *x = (Result *)u;
+                             x->names.assign(names, names + n_ref);
+                             x->rows.assign(rows, rows + 4 * (size_t)n_ref);
+                             return 1;
+                           },
+                           NULL};
+  int64_t counts[6], hist[256];
+  const bool ok = pbsim_bam_depth(ctx, file.map, (int64_t)file.n, &opts, &sink, counts, hist) != 0;
+  if (fclose(res.fp) != 0) res.write_failed = true;
+  if (!ok || res.write_failed) {
+    fprintf(stderr, "ERROR: %s\n", res.write_failed ? ("write error on " + out_name).c_str() : pbsim_last_error());
+    unlink(out_name.c_str());
+    quit(-1);
+  }
+  std::vector<const char *> name_ptr;
+  for (const std::string &nm : res.names) name_ptr.push_back(nm.c_str());
+  const int32_t n_ref = (int32_t)name_ptr.size();
+  std::string text((size_t)pbsim_depth_report(counts, n_ref, name_ptr.data(), res.rows.data(), hist, NULL, 0), '\0');
+  pbsim_depth_report(counts, n_ref, name_ptr.data(), res.rows.data(), hist, &text[0], (int64_t)text.size());
+  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
+  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
+  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
+  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int device) {
@@ -1084,6 +1190,8 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
   gettimeofday(&tv0, NULL);
   for (int i = 1; i < argc; i++)
     if (!strcmp(argv[i], "--eval-bam")) return eval_bam_main(argc, argv, comm, device);
+  for (int i = 1; i < argc; i++)
+    if (!strcmp(argv[i], "--depth-bam")) return depth_bam_main(argc, argv, comm, device);
   if (argc >= 2 && !strcmp(argv[1], "--sort-truth-bam")) {
     // the standalone mode: no simulation, the named files sorted and indexed in place on one GPU
     if (comm && comm->world > 1) die(": --sort-truth-bam runs on one GPU.");
