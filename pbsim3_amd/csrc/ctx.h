@@ -128,6 +128,10 @@ struct DfLane {
   int pre_count = 0;                   // pieces df_begin launched
   hipStream_t lane_stream = nullptr;   // the lane's own kernel stream (`stream` is where the call's kernels are being launched)
   hipEvent_t ev_pre = nullptr;         // behind a prelaunch on another stream
+  // the job pipeline's hand-off (pbsim::deflate_handoff): the head was launched by the lane thread of the round in front, on
+  // the shared lane stream; `hand_open` until a call on this lane has waited for those kernels (or deflate_settle has)
+  hipEvent_t ev_hand = nullptr;        // behind the handed-off kernels
+  bool hand_open = false;
   hipEvent_t ev_df[kDfBuffers] = {}, ev_cp[kDfBuffers] = {};
   hipEvent_t ev_k0[kDfBuffers] = {}, ev_k1[kDfBuffers] = {};  // timing: around k_deflate_chunks of the piece in dense buffer b
   // Pinned arena that holds ALL compressed pieces of one batch (job.cpp, several ranks): a rank learns where its bytes go in
@@ -453,9 +457,19 @@ int stats_merge(StatsAcc *st, const pbsim_params &p, const pbsim_comm *comm, int
 // emission: the delivery that follows (deflate_pieces on the same buffers) finds them under way.  The pieces go through the
 // lanes' own staging, not a caller's arena.  Harmless when the delivery never comes.
 int deflate_prelaunch(pbsim_ctx *c, Slot &sl, bool want_read, bool want_maf);
+// `tail_hook` (optional) is called on the calling thread once the call has launched its LAST piece -- from then on the lane's
+// kernel stream has nothing left to do for this call -- and, while it returns false ("nothing to do yet"), again after every
+// later copy the call enqueues.
 int deflate_pieces(pbsim_ctx *c, DfLane &lane, const uint8_t *d_text, int64_t n,
                    const std::function<int(const char *, int64_t)> &consume,
-                   const std::function<char *(int64_t)> *place = nullptr);
+                   const std::function<char *(int64_t)> *place = nullptr, const std::function<bool()> *tail_hook = nullptr);
+// The job pipeline's hand-off: what a call on `next` (a bulk slot's lane `lane_index`) runs before its first copy -- the table
+// fit and the first pieces -- enqueued NOW on the shared lane stream, behind `text_ready` and behind whatever that stream
+// holds.  The call that follows for the same text finds it in place.  Harmless when that call never comes, but then
+// deflate_settle() before the text or the lane's buffers are handed on.
+int deflate_handoff(pbsim_ctx *c, DfLane &next, int lane_index, const uint8_t *d_text, int64_t n, bool own_staging,
+                    hipEvent_t text_ready);
+int deflate_settle(DfLane &lane);  // waits for handed-off kernels no call has waited for and voids them
 int ensure_deflate_ready(pbsim_ctx *c);  // CRC / shift tables of deflate.hip resident (call before using lanes from threads)
 int ensure_crc_tables(pbsim_ctx *c);  // deflate.hip's slice-by-4 CRC-32 and pow128 tables resident (d_df_tables; inflate uses them too)
 // upper-case + homopolymer pass of a record (k_hp_*) enqueued on `stream`; flags receives the census (DeviceFlags)

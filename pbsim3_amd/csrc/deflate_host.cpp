@@ -42,8 +42,9 @@ int ensure_deflate_tables(pbsim_ctx *c) {
 // an arena that keeps a whole batch) instead of the lane's double-buffered staging.
 // What a call needs before its first copy: buffers, streams, the code table and the kernels of its first pieces (df_begin).
 // This part can run AHEAD of the call (deflate_prelaunch, on the slot's own stream): the unit driver does that for a batch whose
-// bytes it delivers (units.cpp).  For the job pipeline's rounds it was measured and not taken (round 5,
-// profiles/r05_prelaunch_ab.txt): the kernels take the GPU from the round that is being delivered.
+// bytes it delivers (units.cpp).  For the job pipeline's rounds that was measured and not taken (round 5,
+// profiles/r05_prelaunch_ab.txt): the kernels take the GPU from the round that is being delivered.  There the head is
+// launched by the lane of the round in front, at its tail (deflate_handoff, the tail hook of deflate_stream).
 struct DfGeom {
   int64_t piece, max_ch, n_pieces;
   int ahead, nbuf;
@@ -172,7 +173,7 @@ int df_begin(pbsim_ctx *c, DfLane &sl, const uint8_t *d_text, int64_t n, bool ow
 
 template <class F>
 int deflate_stream(pbsim_ctx *c, DfLane &sl, const uint8_t *d_text, int64_t n, F &&consume,
-                   const std::function<char *(int64_t)> *place = nullptr) {
+                   const std::function<char *(int64_t)> *place = nullptr, const std::function<bool()> *tail_hook = nullptr) {
   if (n <= 0) return PBSIM_SUCCEEDED;
   // The kernels of a piece, its copy and the host's consume() are three stages that must not wait for each other's round trips:
   // the lane's stream always holds the NEXT pieces' kernels (piece k + ahead is launched before piece k's total is read back),
@@ -181,8 +182,15 @@ int deflate_stream(pbsim_ctx *c, DfLane &sl, const uint8_t *d_text, int64_t n, F
   // copying: 1.5 ms of kernels + a host round trip per 1.46 ms of copy.)
   const bool prelaunched = sl.pre_valid && sl.pre_text == d_text && sl.pre_n == n && sl.pre_own_staging == (place == nullptr);
   sl.pre_valid = false;
+  // (a head handed off for another text -- the round it was launched for was cut short -- : its kernels still write the
+  // lane's buffers)
+  const bool handed = prelaunched && sl.hand_open;
+  if (!prelaunched && !pbsim::deflate_settle(sl)) return PBSIM_FAILED;
   if (!prelaunched && !df_begin(c, sl, d_text, n, place == nullptr, nullptr)) return PBSIM_FAILED;
   sl.pre_valid = false;
+  if (handed && getenv("PBSIM_TRACE"))
+    fprintf(stderr, "[deflate] lane call of %.1f MB found its head handed off (%d pieces launched behind the call in front)\n", n / 1e6,
+            sl.pre_count);
   if (sl.pre_elsewhere) {  // the first pieces were launched on the slot's stream: the rest follows them on the lane's
     sl.stream = sl.lane_stream;
     HIP_OK(hipStreamWaitEvent(sl.stream, sl.ev_pre, 0));
@@ -195,6 +203,12 @@ int deflate_stream(pbsim_ctx *c, DfLane &sl, const uint8_t *d_text, int64_t n, F
   const bool trace = getenv("PBSIM_DEFLATE_TRACE") != nullptr;  // where a call's wall time goes: kernels | link | consumer
   const auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_kernel = 0, t_copy = 0, t_consume = 0, t_begin = now();
+  double t_first_copy = 0, t_last_copy = 0;  // trace: host time of the first copy's enqueue and of the last copy's completion
+  // the tail hook is due once the last piece has been launched, and stays due while it finds nothing to do
+  bool hook_due = false;
+  auto offer_tail = [&]() {
+    if (tail_hook && hook_due && (*tail_hook)()) hook_due = false;
+  };
   int64_t out_bytes = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;  // trace: begin / end of every copy on the copy stream
   bool used[kDfBuffers] = {false};
@@ -204,6 +218,8 @@ int deflate_stream(pbsim_ctx *c, DfLane &sl, const uint8_t *d_text, int64_t n, F
   };
   for (int64_t j = sl.pre_count; j < std::min<int64_t>(ahead, n_pieces); j++)  // (what a prelaunch left of the head start)
     if (!launch(j)) return PBSIM_FAILED;
+  hook_due = n_pieces <= ahead;
+  offer_tail();
   const char *prev_ptr = nullptr;  // piece k - 1: copy possibly still in flight
   int64_t prev_bytes = 0;
   int prev_buf = 0;
@@ -235,6 +251,7 @@ int deflate_stream(pbsim_ctx *c, DfLane &sl, const uint8_t *d_text, int64_t n, F
       tev.emplace_back(e0, e1);
       HIP_OK(hipEventRecord(e0, sl.copy_stream));
     }
+    if (k == 0) t_first_copy = now();
     HIP_OK(hipMemcpyAsync(dst, sl.d_df_dense[b].p, (size_t)total, hipMemcpyDeviceToHost, sl.copy_stream));
     if (trace) HIP_OK(hipEventRecord(tev.back().second, sl.copy_stream));
     HIP_OK(hipEventRecord(sl.ev_cp[b], sl.copy_stream));
@@ -253,15 +270,19 @@ int deflate_stream(pbsim_ctx *c, DfLane &sl, const uint8_t *d_text, int64_t n, F
     // piece k's staging set is free (its total has arrived), the dense buffer of piece k - 1 once its copy is through (a
     // stream wait inside launch): keep the kernels one piece ahead
     if (k + ahead < n_pieces && !launch(k + ahead)) return PBSIM_FAILED;
+    if (k + ahead == n_pieces - 1) hook_due = true;
+    offer_tail();
   }
   if (prev_bytes) {
     const double t1 = now();
     HIP_OK(hipEventSynchronize(sl.ev_cp[prev_buf]));
     const double t2 = now();
+    t_last_copy = t2;
     if (!consume(prev_ptr, prev_bytes)) return PBSIM_FAILED;
     t_copy += t2 - t1;
     t_consume += now() - t2;
   }
+  sl.hand_open = false;  // (every piece's kernels have been waited for, the handed-off ones included)
   if (trace) {
     double t_link = 0, t_span = 0;
     float ms = 0;
@@ -275,8 +296,10 @@ int deflate_stream(pbsim_ctx *c, DfLane &sl, const uint8_t *d_text, int64_t n, F
     }
     fprintf(stderr,
             "[deflate] %.1f MB -> %.1f MB in %.1f ms: waited %.1f ms for kernels, %.1f ms for copies, %.1f ms in the consumer; copies: "
-            "%.1f ms on the engine within a span of %.1f ms (%.1f GB/s while copying)\n",
-            n / 1e6, out_bytes / 1e6, now() - t_begin, t_kernel, t_copy, t_consume, t_link, t_span, t_link > 0 ? out_bytes / t_link / 1e6 : 0.0);
+            "%.1f ms on the engine within a span of %.1f ms (%.1f GB/s while copying); first copy enqueued at %.3f, last copy "
+            "complete at %.3f ms%s%s\n",
+            n / 1e6, out_bytes / 1e6, now() - t_begin, t_kernel, t_copy, t_consume, t_link, t_span, t_link > 0 ? out_bytes / t_link / 1e6 : 0.0,
+            t_first_copy, t_last_copy, sl.own_streams ? " (chain lane)" : "", handed ? " (head handed off)" : "");
   }
   if (d_prof) {
     unsigned long long t[16];
@@ -308,8 +331,29 @@ int deflate_to_host(pbsim_ctx *c, DfLane &sl, const uint8_t *d_text, int64_t n, 
 
 extern "C++" int pbsim::deflate_pieces(pbsim_ctx *c, DfLane &lane, const uint8_t *d_text, int64_t n,
                                        const std::function<int(const char *, int64_t)> &consume,
-                                       const std::function<char *(int64_t)> *place) {
-  return deflate_stream(c, lane, d_text, n, consume, place);
+                                       const std::function<char *(int64_t)> *place, const std::function<bool()> *tail_hook) {
+  return deflate_stream(c, lane, d_text, n, consume, place, tail_hook);
+}
+extern "C++" int pbsim::deflate_handoff(pbsim_ctx *c, DfLane &next, int lane_index, const uint8_t *d_text, int64_t n,
+                                        bool own_staging, hipEvent_t text_ready) {
+  hipStream_t st = c->df_streams[lane_index][0];
+  if (!st || next.own_streams || next.hand_open || n <= 0) return fail("deflate_handoff: bad argument");
+  if (!next.ev_hand) HIP_OK(hipEventCreateWithFlags(&next.ev_hand, hipEventDisableTiming));
+  HIP_OK(hipStreamWaitEvent(st, text_ready, 0));
+  // (df_begin with no stream of the caller's launches on the lane's shared stream: behind the pieces of the call in front)
+  const int ok = df_begin(c, next, d_text, n, own_staging, nullptr);
+  if (!ok) next.pre_valid = false;
+  // whatever df_begin got launched is waited for through this event, by the call that follows or by deflate_settle
+  next.hand_open = true;
+  HIP_OK(hipEventRecord(next.ev_hand, st));
+  return ok;
+}
+extern "C++" int pbsim::deflate_settle(DfLane &lane) {
+  if (!lane.hand_open) return PBSIM_SUCCEEDED;
+  lane.pre_valid = false;
+  HIP_OK(hipEventSynchronize(lane.ev_hand));
+  lane.hand_open = false;
+  return PBSIM_SUCCEEDED;
 }
 extern "C++" int pbsim::ensure_deflate_ready(pbsim_ctx *c) {
   // (called by a job before its delivery threads start: the lanes' shared streams exist from here on -- the

@@ -316,6 +316,8 @@ void pbsim_destroy(pbsim_ctx *c) {
         if (L.ev_k0[i]) (void)hipEventDestroy(L.ev_k0[i]);
         if (L.ev_k1[i]) (void)hipEventDestroy(L.ev_k1[i]);
       }
+      (void)deflate_settle(L);
+      if (L.ev_hand) (void)hipEventDestroy(L.ev_hand);
       for (hipStream_t &st : L.own)
         if (st) (void)hipStreamDestroy(st);
     }
@@ -373,6 +375,8 @@ int pbsim_release_pools(pbsim_ctx *c) {
   for (Slot &sl : c->slots) {
     if (sl.b_enqueued) return fail("pbsim_release_pools: a batch is in flight");
     if (sl.stream) HIP_OK(hipStreamSynchronize(sl.stream));
+    for (DfLane &L : sl.df)
+      if (!deflate_settle(L)) return PBSIM_FAILED;
   }
   HIP_OK(hipDeviceSynchronize());
   for (Slot &sl : c->slots) {

@@ -38,6 +38,7 @@
 #include <thread>
 
 #include "ctx.h"
+#include "handoff.h"
 
 using namespace pbsim;
 
@@ -393,6 +394,7 @@ struct Job {
   void drop_round(const Round &r) {
     c->cur = r.slot;
     (void)hipStreamSynchronize(c->s().stream);
+    (void)settle_slot(r.slot);
     c->s().b_enqueued = false;
   }
   void drop_rounds_of(int rec) {
@@ -422,6 +424,55 @@ struct Job {
         c->s().b_enqueued = false;
         r.tail_slot = -1;
       }
+  }
+
+  // ---- the lanes' hand-off: while a round's bytes move, the main loop publishes the NEXT round as soon as its
+  // text emission is enqueued; each lane of the round in front, at its tail -- its last piece launched, its kernel stream
+  // idle for the four copies still to go --, launches the head of the next round's compression on that stream
+  // (deflate_handoff).  The next round's lane calls then find their first pieces compressed and start with a copy.
+  // Only with the two lanes side by side (pbsim_set_deflate bit 2: one after the other, lane 0's tail is lane 1's start), only
+  // the bulk rounds' slots (the tail chains' lanes have streams of their own).  PBSIM_JOB_HANDOFF=0 turns it off.
+  Handoff handoff;
+  bool handoff_on = false;
+  bool lookahead = false;  // run(): a second round in flight beside a short one (PBSIM_JOB_LOOKAHEAD=0 turns it off)
+  int64_t n_handed = 0, n_handed_void = 0;  // lane heads launched at a tail | of those, never delivered
+  void publish_next(int slot) {
+    const Slot &sl = c->slots[slot];
+    if (!handoff_on || sl.b_info.n_final <= 0) return;
+    HandoffNext d;
+    d.slot = slot;
+    d.text[0] = sink->on_read_text ? sl.d_read_text.p : nullptr;
+    d.text[1] = sink->on_maf_text ? sl.d_maf_text.p : nullptr;
+    d.bytes[0] = sl.b_info.read_text_bytes;
+    d.bytes[1] = sl.b_info.maf_text_bytes;
+    d.ev_text = sl.ev_text;
+    handoff.publish(d);
+  }
+  // nobody launches anything for the published round from here on; which lanes did (bit per lane)
+  unsigned withdraw_next() {
+    if (!handoff_on) return 0;
+    const unsigned took = handoff.withdraw();
+    n_handed += (took & 1) + (took >> 1);
+    return took;
+  }
+  // the slot's text or its lanes' buffers are about to be handed on: heads that no call has waited for are waited for here
+  int settle_slot(int slot) {
+    for (DfLane &L : c->slots[slot].df) {
+      if (L.hand_open) n_handed_void++;
+      if (!deflate_settle(L)) return PBSIM_FAILED;
+    }
+    return PBSIM_SUCCEEDED;
+  }
+  // a lane's tail hook (on the lane's thread).  false: no next round is up yet -- the lane asks again after its next copy.
+  std::function<bool()> tail_hook(int which) {
+    return [this, which]() -> bool {
+      return handoff.take(which, [&](const HandoffNext &d) {
+        if (!d.text[which] || d.bytes[which] <= 0) return;
+        // (a failure here is not the job's: the call that follows starts from scratch and meets it itself)
+        (void)deflate_handoff(c, c->slots[d.slot].df[which], which, (const uint8_t *)d.text[which], d.bytes[which], !multi,
+                              (hipEvent_t)d.ev_text);
+      });
+    };
   }
 
   size_t arena_max = 0;  // bytes of pinned memory one lane's arena may hold
@@ -487,11 +538,12 @@ struct Job {
       const int64_t base = is_read ? read_at : maf_at;
       const uint8_t *d = is_read ? sl.d_read_text.as<uint8_t>() : sl.d_maf_text.as<uint8_t>();
       if (!cb || n == 0) return PBSIM_SUCCEEDED;
+      const std::function<bool()> hook = tail_hook(which);
       return deflate_pieces(c, sl.df[which], d, n, [&](const char *z, int64_t k) {
         if (!call_sink(which, unit, z, k, base + *sent)) return fail(is_read ? "sink aborted (read text)" : "sink aborted (MAF text)");
         *sent += k;
         return PBSIM_SUCCEEDED;
-      });
+      }, nullptr, handoff_on ? &hook : nullptr);
     });
   }
   // several ranks: a rank learns where its bytes go only after every rank has compressed its block, so the whole batch is
@@ -512,7 +564,8 @@ struct Job {
         if (!p) oom = true;
         return p;
       };
-      if (!deflate_pieces(c, L, d, n, [](const char *, int64_t) { return PBSIM_SUCCEEDED; }, &place))
+      const std::function<bool()> hook = tail_hook(which);
+      if (!deflate_pieces(c, L, d, n, [](const char *, int64_t) { return PBSIM_SUCCEEDED; }, &place, handoff_on ? &hook : nullptr))
         return oom ? fail("out of pinned host memory for a compressed batch (PBSIM_PINNED_ARENA_MB bounds a lane's arena)") : PBSIM_FAILED;
       int64_t tot = 0;
       for (const auto &sg : L.arena_segs) tot += sg.second;
@@ -873,6 +926,7 @@ struct Job {
     if (!collect(rec)) return PBSIM_FAILED;  // (an announced record: resident and prepared by now, or waited for here)
     const int s = acquire_slot();
     c->cur = s;
+    if (!settle_slot(s)) return PBSIM_FAILED;  // (a head launched for a round of this slot that was never delivered)
     const double tb = now_us();
     if (trace) fprintf(stderr, "[pbsim job r%d] begin rec %d first=%lld n_per=%lld\n", rank, rec + 1, (long long)R.spec_read, (long long)n_per);
     if (!walk_begin(c, R.ref, R.spec_read + (int64_t)rank * n_per, n_per, -1)) return PBSIM_FAILED;
@@ -882,7 +936,7 @@ struct Job {
     // longest read.  A wrong guess costs time only (process_round: a clear round that does touch the quota emits its text again
     // behind the cut, an unclear one that does not pays one exchange more); PBSIM_JOB_CLEAR=0 / 1 forces it (tests).
     const double after = R.spec_total + (double)W * (double)n_per * mean;
-    static const char *force_clear = getenv("PBSIM_JOB_CLEAR");
+    const char *force_clear = getenv("PBSIM_JOB_CLEAR");
     const bool clear = force_clear ? atoi(force_clear) != 0
                                    : (double)R.quota - after > 0.04 * (double)W * (double)n_per * mean + 2.0 * (double)std::min<int64_t>(c->p.len_max, R.ref.len);
     fifo.push_back(Round{rec, s, R.spec_read, n_per, mean, clear});
@@ -911,6 +965,10 @@ struct Job {
     fifo.pop_front();
     Rec &R = recs[(size_t)rd.rec];
     c->cur = rd.slot;
+    struct Withdraw {  // whichever way this round ends, its descriptor does not stay up
+      Job *j;
+      ~Withdraw() { (void)j->withdraw_next(); }
+    } withdraw_at_exit{this};
     const double t0 = now_us();
     int64_t pass0 = 0, code = 0;
     std::string my_err;
@@ -939,6 +997,7 @@ struct Job {
         const double tf = now_us();
         fin_ok = finalize_uncut(c, &bi) && finalize_text(c, &bi);
         if (!fin_ok) my_err = g_err;
+        else publish_next(rd.slot);  // (before the wait for the previous round's bytes: its lanes take it at their tails)
         t_fin += now_us() - tf;
       }
       msg[3] = fin_ok ? 0 : 1;
@@ -998,8 +1057,11 @@ struct Job {
     } else {
       // a failure here travels in the exchange's status word: every rank leaves the job at the same collective
       const double tf = now_us();
-      fin_ok = (untouched ? finalize_uncut(c, &bi) : finalize_cut(c, before, &bi)) && finalize_text(c, &bi);
+      // (a clear round that missed: its text is written again -- a head launched for the first emission reads that text)
+      fin_ok = (!withdraw_next() || settle_slot(rd.slot)) && (untouched ? finalize_uncut(c, &bi) : finalize_cut(c, before, &bi)) &&
+               finalize_text(c, &bi);
       if (!fin_ok) my_err = g_err;
+      else publish_next(rd.slot);
       if (untouched) c->s().b_info.len_total_after = bi.len_total_after = before + pass0;
       t_fin += now_us() - tf;
       if (rd.clear) n_clear_missed++;
@@ -1030,6 +1092,11 @@ struct Job {
     // ---- delivery: the previous round's sizes have been exchanged (its bytes were on their way while this round's text was
     // emitted); this round's bytes start moving
     if (!c_applied && !complete_pending(true)) return PBSIM_FAILED;  // (nothing was pending)
+    const unsigned handed = withdraw_next();  // (this round's own lanes must not find their own descriptor)
+    if (trace && handoff_on)
+      fprintf(stderr, "[pbsim job r%d] t=%.1f ms rec %d hand-off: %s%s%s\n", rank, (now_us() - t_start) / 1e3, rd.rec + 1,
+              handed == 0 ? "no lane took the round" : (handed == 3 ? "both lanes' heads launched" : "one lane's head launched"),
+              handed ? " behind the round in front" : "", handed && !mine ? " (void: the block is behind the cut)" : "");
     pending.reset(new Delivery);
     ++rec_rounds_open[(size_t)rd.rec];
     pending->slot = rd.slot;
@@ -1101,7 +1168,17 @@ struct Job {
       // interleave == k > 1: of the first k open records the one that is furthest behind, so that k records advance side by
       // side (a caller that writes a file pair per record then has 2k files to write at a time, pbsim_job_set_interleave).
       const int open_max = std::max(2, interleave);
-      while (bulk_in_flight() < depth) {
+      // A delivered job keeps ONE round in flight (job_run_impl) -- but a round of a quarter of a full one or less (the job's
+      // first, a record's last: 49 533 reads behind four rounds of 444 704) is delivered in less time than the next round is
+      // walked: 8 ms of bytes, then a link that waits ~25 ms for the 28 ms walk that was begun only when the short round came
+      // back (profiles/handoff_idle_parent.txt: the one boundary of 33 ms per job).  The next round is begun BESIDE a short
+      // round.  The same on every rank: n_per and the cap are agreed values.
+      auto depth_now = [&]() {
+        if (!lookahead || depth != 1 || fifo.size() != 1) return depth;
+        const Round &r = fifo.front();
+        return 4 * r.n_per <= recs[(size_t)r.rec].cap ? 2 : 1;
+      };
+      while (bulk_in_flight() < depth_now()) {
         int cand = -1;
         const int hi = std::min(n, merged + open_max);
         double best = 2.0;
@@ -1617,7 +1694,8 @@ static int job_run_impl(pbsim_ctx *c, const pbsim_comm *comm, const pbsim_record
       const double scratch_per_base = (double)regions * sf * 1.12 * 1.08 + 0.1;
       // (rounds in flight + one whose delivery is pending + one with the worker; nothing is held back when the text stays put)
       const bool delivering_text = J.sink && (J.sink->on_read_text || J.sink->on_maf_text);
-      const double slots_used = (double)J.depth + (delivering_text ? 2.0 : 1.0);
+      // (+ the round begun beside a short one, Job::run)
+      const double slots_used = (double)J.depth + (delivering_text ? 3.0 : 1.0);
       const char *ff = getenv("PBSIM_JOB_FIT");  // experiment knob: share of the free HBM the slots may take
       const double fit = (ff ? atof(ff) : 0.75) * (double)(free_b + held + held_text) / (slots_used * (text_per_base + scratch_per_base));
       target = std::min(target, std::max(fit, 1.0e8));
@@ -1699,6 +1777,13 @@ static int job_run_impl(pbsim_ctx *c, const pbsim_comm *comm, const pbsim_record
   const int keep_lds = c->walk_lds_kb;
   if (J.deflated()) c->walk_lds_kb = std::max(c->walk_lds_kb, 81);
   c->defer_text_sync = true;  // the round loop does not wait for a round's text emission; the delivery thread does
+  {
+    const char *ho = getenv("PBSIM_JOB_HANDOFF");
+    J.handoff_on = J.deflated() && c->deflate_parallel && !(ho && atoi(ho) == 0);
+    const char *la = getenv("PBSIM_JOB_LOOKAHEAD");
+    J.lookahead = delivers && !(la && atoi(la) == 0);
+  }
+  if (J.trace) fprintf(stderr, "[pbsim job r%d] entered at %.3f ms, round loop at %.3f ms\n", J.rank, J.t_start / 1e3, now_us() / 1e3);
   int ok = J.run();
   c->defer_text_sync = false;
   c->walk_lds_kb = keep_lds;
@@ -1716,8 +1801,16 @@ static int job_run_impl(pbsim_ctx *c, const pbsim_comm *comm, const pbsim_record
     J.tail_worker.finish();
     g_err = keep;
   }
+  // (both workers have finished: no lane thread is left.  Heads handed off for rounds that were never delivered end here at
+  // the latest -- the slots' text and the lanes' buffers belong to the caller again.)
+  (void)J.withdraw_next();
+  for (int s = 0; s < kMaxSlots; s++)
+    if (!J.settle_slot(s) && ok) ok = PBSIM_FAILED;
   for (Slot &sl : c->slots)
     for (DfLane &L : sl.df) L.arena_trim();
+  if (J.trace)
+    fprintf(stderr, "[pbsim job r%d] returns at %.3f ms; hand-off %s: %lld lane heads launched at a tail, %lld of them never delivered\n",
+            J.rank, now_us() / 1e3, J.handoff_on ? "on" : "off", (long long)J.n_handed, (long long)J.n_handed_void);
   {
     const double wall = now_us() - J.t_start;
     double *b = c->job_breakdown;
