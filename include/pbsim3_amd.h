@@ -463,6 +463,71 @@ int pbsim_bam_depth(pbsim_ctx *ctx, const void *bam, int64_t n, const pbsim_dept
  * length, and writes it (no NUL) where buf holds cap >= that many bytes; -1: bad argument. */
 int64_t pbsim_depth_report(const int64_t counts[6], int32_t n_ref, const char *const *names, const int64_t *rows,
                            const int64_t hist[256], char *buf, int64_t cap);
+/* A summary of the reads of one or more BAM files on the GPU: lengths, error rates, qualities (what `samtools stats`, NanoStat
+ * or cramino tell) -- of a real run, the numbers --length-mean / --length-sd / --length-min / --length-max, --accuracy-mean,
+ * --difference-ratio and the sampling method's --accuracy-min / --accuracy-max ask for; of a simulated run, whether the reads
+ * came out that way.  files[0..n_files), n_files >= 1: each is BGZF (inflated on the GPU), one plain gzip stream (zlib on the
+ * host) or an uncompressed BAM stream, an unaligned BAM, a truth BAM or a mapper's BAM.  The files are taken one after the
+ * other and summed into one result (a wgs job writes one truth file per FASTA record); headers are not compared; a file's
+ * stream is freed when its pass is done.  Every quantity is an integer: the result is a function of the input alone.
+ * Classes of a record, tested in this order: skipped_flag if flag & exclude_flags (default 0x900: each read counts once;
+ * nothing more of such a record is looked at); else unaligned if flag & 4, refID < 0, pos < 0 or n_cigar_op == 0 (length and
+ * quality only); else skipped_mapq if mapq < min_mapq (skipped wholly); else aligned.  counted = unaligned + aligned.
+ * Length, over counted records with l_seq >= 1 (a counted record with l_seq == 0 adds to no_seq and takes no part in length or
+ * quality): len_row = n, bases, min, max, mean_milli = bases * 1000 / n, sd = isqrt((n * sumsq - bases^2) / n^2), median = the
+ * element (n - 1) / 2 of the ascending lengths, N10 .. N90: Nx the length of the first record, in descending order, at which
+ * running sum * 100 >= x * bases.  All divisions are integer divisions; with n == 0 every field is 0.
+ * Alignment, over aligned records.  The CIGAR is resolved as pbsim_bam_depth resolves it (the <l_seq>S<span>N placeholder is
+ * replaced by the CG:B,I array).  m = the M, = and X lengths, ins the I, del the D lengths, ins_events / del_events the ops of
+ * that kind with length >= 1, soft, hard; cols = m + ins + del.  NM is the first aux field named NM of type c C s S i I, found
+ * by walking the aux fields by type until what is wanted (NM; the CG array where the CIGAR is the placeholder) has been found;
+ * a record without one, or with a negative value, adds to no_nm; one with nm < ins + del, nm - ins - del > m or cols == 0 adds to
+ * nm_bad; every other aligned record is scored, sub = nm - ins - del, identity_ppm = (cols - nm) * 1000000 / cols,
+ * hist_identity[identity_ppm / 1000] += 1.  An aux field that runs past the record or has an unknown type, met on that walk,
+ * or a CIGAR op code above 8, in an aligned record, fails the call with the record's inflated offset.
+ * Quality, over counted records with l_seq >= 1: a first quality byte 0xFF adds to no_qual, and the record takes no part.
+ * Else per base q' = min(q, 127), hist_q[q'] += 1; per read esum = the sum of E[q'], E[q] = round(2^32 10^(-q/10)),
+ * acc_ppm = 1000000 - esum * 1000000 / (l_seq << 32), hist_qacc[acc_ppm / 1000] += 1: the sampling method's accuracy
+ * 1 - mean(10^(-Q/10)) in fixed point, so that it does not depend on the order of the additions (it is not the double the
+ * sampling profile computes).
+ * counts: records, skipped_flag, unaligned, skipped_mapq, aligned, no_seq, no_qual, no_nm, nm_bad, scored.  totals, the first
+ * nine over scored records: cols, sub, ins, del, ins_events, del_events, soft, hard, identity_sum; then the sum of acc_ppm, the
+ * number of reads it is over, and the sum of q' over all their bases.
+ * The per-read text, only where sink->on_text is not NULL (nothing of it is computed otherwise), in offset order, in pieces of
+ * at most piece_bytes (a piece may end inside a line), one line per counted record, in file order and then record order:
+ *   name\tclass\tlength\tcols\tnm\tins\tdel\tsoft\tidentity_ppm\tmean_q_milli\tacc_ppm\n
+ * name the read name's bytes in front of the first NUL, class A (aligned) or U, length l_seq; cols, ins, del, soft of an aligned
+ * record, nm where it has a value that is not negative, identity_ppm where it is scored, mean_q_milli = the sum of q' * 1000 /
+ * l_seq and acc_ppm where it has qualities; a field its record does not define is "*".  The first callback comes when every
+ * file has been read: after a failure no callback has seen partial text.
+ * tests/stats_model.py states the rule in plain Python.  exclude_flags outside 0 .. 65535, min_mapq outside 0 .. 255 and a
+ * negative piece_bytes fail before any device work; a file of 2^36 inflated bytes or more and 2^31 records or more in total are
+ * refused; an allocation that does not fit fails with the bytes it needed; a tables-only context fails as pbsim_inflate_buffer
+ * does.  After any failure the context stays usable. */
+typedef struct pbsim_stats_file {
+  const void *bam;
+  int64_t n;
+} pbsim_stats_file;
+typedef struct pbsim_stats_opts { /* NULL: {0x900, 0, 0} */
+  int32_t exclude_flags, min_mapq;
+  int64_t piece_bytes; /* 0: the default; else the most text one on_text call carries */
+} pbsim_stats_opts;
+typedef struct pbsim_stats_sink {
+  void *user;
+  int (*on_text)(void *user, const char *bytes, int64_t n, int64_t offset); /* in offset order; may be NULL */
+} pbsim_stats_sink;
+int pbsim_bam_stats(pbsim_ctx *ctx, const pbsim_stats_file *files, int n_files, const pbsim_stats_opts *opts,
+                    const pbsim_stats_sink *sink, int64_t counts[10], int64_t len_row[16], int64_t totals[12],
+                    int64_t hist_q[128], int64_t hist_identity[1001], int64_t hist_qacc[1001]);
+/* The report text, no device needed: "# records=N skipped_flag=N unaligned=N skipped_mapq=N aligned=N no_seq=N no_qual=N no_nm=N
+ * nm_bad=N scored=N"; "L" and the sixteen values of len_row; "E\t<sub>\t<ins>\t<del>\t<cols>", their three rates in ppm of
+ * cols, the sub : ins : del split in permille of sub + ins + del, and identity_sum / scored; "Q\t<acc_sum / acc_reads>\t<q_sum
+ * * 1000 / the bases of hist_q>" (integer divisions; 0 where the divisor is 0); then "HQ\t<q>\t<bases>", "HI\t<bin>\t<reads>" and
+ * "HA\t<bin>\t<reads>" for the bins that are not empty, ascending.  Returns the text's length, and writes it (no NUL) where buf
+ * holds cap >= that many bytes; -1: bad argument. */
+int64_t pbsim_stats_report(const int64_t counts[10], const int64_t len_row[16], const int64_t totals[12],
+                           const int64_t hist_q[128], const int64_t hist_identity[1001], const int64_t hist_qacc[1001],
+                           char *buf, int64_t cap);
 
 /* ---- batch primitives (used by the drivers above, bench.py, multi-GPU) ------
  * pbsim_batch_walk     header draw + bucketing + HMM walk of reads

@@ -174,6 +174,26 @@ class DepthSink(C.Structure):
 DEPTH_COUNTS = ["records", "counted", "skipped_flag", "skipped_unplaced", "skipped_mapq", "clipped"]
 DEPTH_FORMATS = {"bedgraph": 0, "window": 1}
 
+
+class StatsFile(C.Structure):
+    _fields_ = [("bam", C.c_void_p), ("n", C.c_int64)]
+
+
+class StatsOpts(C.Structure):
+    _fields_ = [("exclude_flags", C.c_int32), ("min_mapq", C.c_int32), ("piece_bytes", C.c_int64)]
+
+
+STATS_TEXT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64)
+
+
+class StatsSink(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("on_text", STATS_TEXT_CB)]
+
+
+STATS_COUNTS = ["records", "skipped_flag", "unaligned", "skipped_mapq", "aligned", "no_seq", "no_qual", "no_nm", "nm_bad", "scored"]
+STATS_LEN_ROW = ["n", "bases", "min", "max", "mean_milli", "sd", "median"] + ["N%d" % x for x in range(10, 100, 10)]
+STATS_TOTALS = ["cols", "sub", "ins", "del", "ins_events", "del_events", "soft", "hard", "identity_sum", "acc_sum", "acc_reads", "q_sum"]
+
 # every symbol include/pbsim3_amd.h declares: (name, restype, argtypes)
 API = [
     ("pbsim_job_add_record", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
@@ -264,6 +284,8 @@ API = [
                                   C.POINTER(C.c_int64)]),
     ("pbsim_depth_report", C.c_int64, [C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                        C.c_char_p, C.c_int64]),
+    ("pbsim_bam_stats", C.c_int, [C.c_void_p, C.POINTER(StatsFile), C.c_int, C.POINTER(StatsOpts), C.POINTER(StatsSink)] + [C.POINTER(C.c_int64)] * 6),
+    ("pbsim_stats_report", C.c_int64, [C.POINTER(C.c_int64)] * 6 + [C.c_char_p, C.c_int64]),
     ("pbsim_batch_walk", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_slot_count", C.c_int, []),
     ("pbsim_select_slot", C.c_int, [C.c_void_p, C.c_int]),
@@ -365,6 +387,24 @@ def depth_report(counts, refs, hist) -> bytes:
         raise PbsimError("pbsim_depth_report: bad argument")
     buf = C.create_string_buffer(max(n, 1))
     load().pbsim_depth_report(c, len(refs), names, rows, h, buf, n)
+    return buf.raw[:n]
+
+
+def stats_report(counts, len_row, totals, hist_q, hist_identity, hist_qacc) -> bytes:
+    """The report text of Context.bam_stats's counts, len_row and totals (the dicts, or the values in order) and its three
+    histograms (128, 1001 and 1001 values): pbsim_stats_report, no device needed."""
+    def vals(x, names):
+        return [int(x[k]) for k in names] if isinstance(x, dict) else [int(v) for v in x]
+    parts = [vals(counts, STATS_COUNTS), vals(len_row, STATS_LEN_ROW), vals(totals, STATS_TOTALS), [int(v) for v in hist_q],
+             [int(v) for v in hist_identity], [int(v) for v in hist_qacc]]
+    if [len(p) for p in parts] != [10, 16, 12, 128, 1001, 1001]:
+        raise ValueError("stats_report: 10 counts, 16 length values, 12 totals and histograms of 128, 1001 and 1001 bins")
+    arrs = [(C.c_int64 * len(p))(*p) for p in parts]
+    n = load().pbsim_stats_report(*arrs, None, 0)
+    if n < 0:
+        raise PbsimError("pbsim_stats_report: bad argument")
+    buf = C.create_string_buffer(max(n, 1))
+    load().pbsim_stats_report(*arrs, buf, n)
     return buf.raw[:n]
 
 
@@ -934,6 +974,35 @@ class Context:
         hd = np.array(list(hist), dtype=np.int64)
         out = (b"".join(parts), cd, refs, hd, depth_report(cd, refs, hd))
         return out + (depth,) if arrays else out
+
+    def bam_stats(self, files, min_mapq=0, exclude_flags=0x900, text=False, piece_bytes=0):
+        """A summary of the reads of BAM files (pbsim_bam_stats; the rule: include/pbsim3_amd.h).  files: the bytes of one
+        file, or a list of them, summed into one result.  Returns (counts, len_row, totals, hist_q, hist_identity, hist_qacc,
+        report): three dicts, three numpy int64 arrays (128, 1001 and 1001 bins) and the report text -- and with `text` an
+        eighth item, the per-read lines."""
+        import numpy as np
+        if isinstance(files, (bytes, bytearray, memoryview)):
+            files = [files]
+        files = [bytes(f) for f in files]
+        arr = (StatsFile * max(len(files), 1))(*[StatsFile(C.cast(C.c_char_p(f), C.c_void_p), len(f)) for f in files])
+        parts, at = [], [0]
+
+        def on_text(user, ptr, n, offset):
+            if offset != at[0]:      # (the pieces come in offset order)
+                return 0
+            parts.append(C.string_at(ptr, n))
+            at[0] += n
+            return 1
+        sink = StatsSink(None, STATS_TEXT_CB(on_text) if text else STATS_TEXT_CB())
+        opts = StatsOpts(int(exclude_flags), int(min_mapq), int(piece_bytes))
+        out = [(C.c_int64 * k)() for k in (10, 16, 12, 128, 1001, 1001)]
+        _check(self.lib.pbsim_bam_stats(self.h, arr, len(files), C.byref(opts), C.byref(sink), *out))
+        cd = dict(zip(STATS_COUNTS, (int(v) for v in out[0])))
+        ld = dict(zip(STATS_LEN_ROW, (int(v) for v in out[1])))
+        td = dict(zip(STATS_TOTALS, (int(v) for v in out[2])))
+        hists = tuple(np.array(list(h), dtype=np.int64) for h in out[3:])
+        res = (cd, ld, td) + hists + (stats_report(cd, ld, td, *hists),)
+        return res + (b"".join(parts),) if text else res
 
     def set_transcripts(self, ids, plus, minus, seqs):
         """ids: list[str]; plus/minus: expression counts; seqs: list[bytes]."""

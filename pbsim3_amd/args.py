@@ -214,3 +214,40 @@ def depth_bam(argv):
     if got["format"] != "window" and have_window:
         raise ValueError("--depth-window N goes with --depth-format window.")
     return got
+
+
+def stats_bam(argv):
+    """`pbsim --stats-bam FILE [--stats-bam FILE ...] [--stats-out FILE] [--stats-min-mapq Q] [--stats-exclude-flags F]` ->
+    dict(bams, out, min_mapq, exclude_flags): the stand-alone mode that summarises the reads of BAM files (pbsim_bam_stats).  F
+    is decimal or 0x hexadecimal.  What pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
+    takes = ("--stats-bam", "--stats-out", "--stats-min-mapq", "--stats-exclude-flags", "--device")
+    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
+    got = dict(bams=[], out=None, min_mapq=0, exclude_flags=0x900)
+    if any(a.split("=")[0] in ranks for a in argv):
+        raise ValueError("--stats-bam runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a not in takes:
+            raise ValueError("(%s): --stats-bam takes --stats-out, --stats-min-mapq, --stats-exclude-flags and --device, and no other option." % a)
+        if i + 1 >= len(argv):
+            raise ValueError("(%s): the option needs a value." % a)
+        v = argv[i + 1]
+        i += 2
+        if a == "--stats-bam":
+            got["bams"].append(v)
+        elif a == "--stats-out":
+            got["out"] = v
+        elif a == "--stats-min-mapq":
+            n = _whole(v)
+            if n is None or n > 255:
+                raise ValueError("(stats-min-mapq: %s): a whole number, 0 .. 255." % v)
+            got["min_mapq"] = n
+        elif a == "--stats-exclude-flags":
+            n = _whole(v, 16 if v[:2] in ("0x", "0X") else 10)
+            if n is None or n > 65535:
+                raise ValueError("(stats-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535." % v)
+            got["exclude_flags"] = n
+    if not got["bams"]:
+        raise ValueError("--stats-bam FILE: name the BAM file.")
+    return got

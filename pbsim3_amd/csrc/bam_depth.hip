@@ -23,6 +23,7 @@
 
 #include <rocprim/device/device_scan.hpp>
 
+#include "bam_aux.h"
 #include "bam_depth.h"
 #include "bam_fields.h"
 
@@ -44,49 +45,6 @@ __device__ __forceinline__ int op_class(uint32_t v, bool deletions) {
   if (op == 0 || op == 7 || op == 8) return 1;
   if (op == 2) return deletions ? 1 : 2;
   return op == 3 ? 2 : 0;
-}
-
-// The array of the record's CG tag of type B,I (SAMv1 4.2.2) among the aux fields [a, end).  1: found (*ops, *n); 0: the
-// record has none; -1: a field runs past the record or has an unknown type.
-__device__ int find_cg(const uint8_t *a, const uint8_t *end, const uint8_t **ops, uint32_t *n) {
-  while (a < end) {
-    if (end - a < 3) return -1;
-    const bool cg = a[0] == 'C' && a[1] == 'G';
-    const uint8_t t = a[2];
-    a += 3;
-    int64_t size;
-    if (t == 'A' || t == 'c' || t == 'C') {
-      size = 1;
-    } else if (t == 's' || t == 'S') {
-      size = 2;
-    } else if (t == 'i' || t == 'I' || t == 'f') {
-      size = 4;
-    } else if (t == 'Z' || t == 'H') {
-      const uint8_t *z = a;
-      while (z < end && *z) z++;
-      if (z >= end) return -1;
-      size = z + 1 - a;
-    } else if (t == 'B') {
-      if (end - a < 5) return -1;
-      const uint8_t sub = a[0];
-      const int64_t count = ld32(a + 1);
-      const int64_t each = sub == 'c' || sub == 'C' ? 1 : sub == 's' || sub == 'S' ? 2 : sub == 'i' || sub == 'I' || sub == 'f' ? 4 : 0;
-      if (each == 0) return -1;
-      a += 5;
-      size = count * each;
-      if (size > end - a) return -1;
-      if (cg && sub == 'I') {
-        *ops = a;
-        *n = (uint32_t)count;
-        return 1;
-      }
-    } else {
-      return -1;
-    }
-    if (size > end - a) return -1;
-    a += size;
-  }
-  return 0;
 }
 
 __global__ __launch_bounds__(kThreads) void k_depth_events(const uint8_t *stream, const uint64_t *rec, int64_t n_rec, int size_bits, DepthRefs refs,
@@ -130,7 +88,10 @@ __global__ __launch_bounds__(kThreads) void k_depth_events(const uint8_t *stream
         const uint32_t op0 = ld32(cig), op1 = ld32(cig + 4);
         if ((op0 & 15u) == 4 && (op0 >> 4) == l_seq && (op1 & 15u) == 3) {
           const uint8_t *aux = cig + 8 + ((int64_t)l_seq + 1) / 2 + (int64_t)l_seq;
-          if (aux > end || find_cg(aux, end, &cig, &n_ops) < 0) bad = true;
+          BamAux ax;
+          const int got = aux > end ? -1 : bam_aux_walk(aux, end, kAuxCg, &ax);
+          if (got < 0) bad = true;
+          else if (got & kAuxCg) cig = ax.cg, n_ops = ax.n_cg;
         }
       }
     }

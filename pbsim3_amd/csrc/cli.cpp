@@ -346,6 +346,9 @@ void print_help() {
           "  pbsim --depth-bam FILE --depth-out FILE [--depth-format bedgraph|window (bedgraph)] [--depth-window N]\n"
           "  [--depth-min-mapq Q (0)] [--depth-exclude-flags F (0x704)] [--depth-no-deletions]: no simulation; the depth of coverage\n"
           "  of a truth BAM or a mapper's BAM on the GPU: bedGraph runs or fixed windows to --depth-out, a summary to stdout\n"
+          "  pbsim --stats-bam FILE [--stats-bam FILE ...] [--stats-out FILE] [--stats-min-mapq Q (0)] [--stats-exclude-flags F (0x900)]:\n"
+          "  no simulation; the reads of BAM files summarised on the GPU: lengths, error rates from CIGAR and NM, qualities;\n"
+          "  the report to stdout, one line per read to --stats-out\n"
           "  --genome, --transcript, --template and --sample may be gzip-compressed (recognised by content): BGZF is\n"
           "  inflated on the GPU, other gzip by zlib on the host; the whole inflated file is held in host memory\n\n");
 }
@@ -1183,6 +1186,75 @@ int depth_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
   return 0;
 }
 
+// `pbsim --stats-bam FILE [--stats-bam FILE ...] ...`: a summary of the reads of BAM files (pbsim_bam_stats), the report to
+// stdout, the per-read text to --stats-out.  What can be refused from the command line alone is refused before a GPU is touched.
+int stats_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
+  if (comm && comm->world > 1) die(": --stats-bam runs on one GPU.");
+  std::vector<std::string> in_names;
+  std::string out_name;
+  long long min_mapq = 0, exclude = 0x900;
+  for (int i = 1; i < argc; i++) {
+    const std::string a = argv[i];
+    const bool takes = a == "--stats-bam" || a == "--stats-out" || a == "--stats-min-mapq" || a == "--stats-exclude-flags" || a == "--device";
+    if (!takes) die(" (%s): --stats-bam takes --stats-out, --stats-min-mapq, --stats-exclude-flags and --device, and no other option.", argv[i]);
+    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
+    const char *v = argv[++i];
+    if (a == "--stats-bam") in_names.push_back(v);
+    else if (a == "--stats-out") out_name = v;
+    else if (a == "--device") device = device >= 0 ? device : atoi(v);
+    else if (a == "--stats-min-mapq") {
+      if (!whole_number(v, 10, 0, 255, &min_mapq)) die(" (stats-min-mapq: %s): a whole number, 0 .. 255.", v);
+    } else {
+      const bool hex = v[0] == '0' && (v[1] == 'x' || v[1] == 'X');
+      if (!whole_number(v, hex ? 16 : 10, 0, 65535, &exclude)) die(" (stats-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535.", v);
+    }
+  }
+  if (in_names.empty()) die(": --stats-bam FILE: name the BAM file.");
+  std::vector<MappedFile> files(in_names.size());
+  for (size_t f = 0; f < files.size(); f++)
+    if (!files[f].open_file(in_names[f])) die(": Cannot open file: %s", in_names[f].c_str());
+  pbsim_params p;
+  pbsim_params_default(&p);
+  p.strategy = PBSIM_STRATEGY_WGS;
+  p.method = PBSIM_METHOD_ERR;
+  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
+  if (!ctx) check(0);
+  struct Result {
+    FILE *fp = NULL;
+    bool write_failed = false;
+  } res;
+  if (!out_name.empty()) {
+    res.fp = fopen(out_name.c_str(), "wb");
+    if (!res.fp) die(": Cannot open output file: %s", out_name.c_str());
+  }
+  std::vector<pbsim_stats_file> in(files.size());
+  for (size_t f = 0; f < files.size(); f++) in[f] = pbsim_stats_file{files[f].map, (int64_t)files[f].n};
+  pbsim_stats_opts opts = {(int32_t)exclude, (int32_t)min_mapq, 0};
+  pbsim_stats_sink sink = {&res, [](void *u, const char *z, int64_t k, int64_t) {
+                             Result *x = (Result *)u;
+                             if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
+                             return x->write_failed ? 0 : 1;
+                           }};
+  if (!res.fp) sink.on_text = NULL;
+  int64_t counts[10], len_row[16], totals[12], hist_q[128], hist_identity[1001], hist_qacc[1001];
+  const bool ok = pbsim_bam_stats(ctx, in.data(), (int)in.size(), &opts, &sink, counts, len_row, totals, hist_q, hist_identity, hist_qacc) != 0;
+  if (res.fp && fclose(res.fp) != 0) res.write_failed = true;
+  if (!ok || res.write_failed) {
+    fprintf(stderr, "ERROR: %s\n", res.write_failed ? ("write error on " + out_name).c_str() : pbsim_last_error());
+    if (in_names.size() > 1)
+      for (size_t f = 0; f < in_names.size(); f++) fprintf(stderr, "ERROR: file %zu is %s\n", f, in_names[f].c_str());
+    if (!out_name.empty()) unlink(out_name.c_str());
+    quit(-1);
+  }
+  std::string text((size_t)pbsim_stats_report(counts, len_row, totals, hist_q, hist_identity, hist_qacc, NULL, 0), '\0');
+  pbsim_stats_report(counts, len_row, totals, hist_q, hist_identity, hist_qacc, &text[0], (int64_t)text.size());
+  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
+  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
+  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
+  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int device) {
@@ -1192,6 +1264,8 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
     if (!strcmp(argv[i], "--eval-bam")) return eval_bam_main(argc, argv, comm, device);
   for (int i = 1; i < argc; i++)
     if (!strcmp(argv[i], "--depth-bam")) return depth_bam_main(argc, argv, comm, device);
+  for (int i = 1; i < argc; i++)
+    if (!strcmp(argv[i], "--stats-bam")) return stats_bam_main(argc, argv, comm, device);
   if (argc >= 2 && !strcmp(argv[1], "--sort-truth-bam")) {
     // the standalone mode: no simulation, the named files sorted and indexed in place on one GPU
     if (comm && comm->world > 1) die(": --sort-truth-bam runs on one GPU.");
