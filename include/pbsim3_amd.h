@@ -528,6 +528,98 @@ int pbsim_bam_stats(pbsim_ctx *ctx, const pbsim_stats_file *files, int n_files, 
 int64_t pbsim_stats_report(const int64_t counts[10], const int64_t len_row[16], const int64_t totals[12],
                            const int64_t hist_q[128], const int64_t hist_identity[1001], const int64_t hist_qacc[1001],
                            char *buf, int64_t cap);
+/* The error profile of the aligned reads of one or more BAM files against the genome they were aligned to, on the GPU: the
+ * substitution matrix, the indel length spectrum, deletions by homopolymer class with the --hp-del-bias they suggest, the
+ * reported qualities against the errors found, and NM checked against the genome (what `samtools stats -r`, alfred or NanoOK
+ * tell).  No MD tag, no = / X ops and no NM tag are needed: the genome lies in HBM beside the records.
+ * The genome: refs[0..n_refs), n_refs >= 1, each {name, lines, bytes}: name NUL-terminated and compared as bytes, two equal
+ * names are refused; lines[0..bytes) are the record's sequence lines, line feeds allowed and dropped.  Each record is prepared
+ * as the simulator prepares its reference (tests/ref_prep_model.py): a-z upper-cased, and one class byte per base, the length of
+ * its homopolymer run up to 11 (beyond: 11 odd, 10 even), N class 1; a run never joins the next record's.  The whole genome
+ * stays in HBM, 2 bytes per base, while the files pass one after another.
+ * files[0..n_files), n_files >= 1, each {bam, n, ref_name}: BGZF (inflated on the GPU), one plain gzip stream or an uncompressed
+ * BAM stream.  A file's reference is looked up in the genome by its name -- by ref_name where that is not NULL, which is refused
+ * for a file that has not exactly one reference (a wgs truth file calls its reference "ref").  Found with an l_ref that is not
+ * the record's number of bases, the call fails and names both.
+ * Every quantity is an integer: the result is a function of the input alone, whatever the order of records or files.
+ * Class of a record, tested in this order: skipped_flag if flag & exclude_flags (default 0x900); unaligned if flag & 4, refID
+ * outside 0 .. n_ref - 1, pos < 0 or n_cigar_op == 0; skipped_mapq if mapq < min_mapq; skipped_ref if the genome lacks its
+ * reference; else aligned.  Nothing more of a record of the first four classes is looked at.  The CIGAR of an aligned record is
+ * resolved as pbsim_bam_depth resolves it (the <l_seq>S<span>N placeholder is replaced by the CG:B,I array) and NM is found as
+ * pbsim_bam_stats finds it; an aux field that runs past the record or has an unknown type, met on that walk, or a CIGAR op code
+ * above 8, fails the call with the record's inflated offset.  An aligned record is no_seq if l_seq == 0; else misfit if the
+ * CIGAR's query length (M I S = X) is not l_seq or pos + its span (M D N = X) > l_ref; else scored.  Only a scored record's
+ * bases, qualities and reference bases are read.
+ * Columns of a scored record.  r, the reference class: A C G T -> 0 .. 3, every other byte 4.  b, the read class, from the
+ * 4-bit code: 1 2 4 8 -> 0 .. 3; 0 (=) -> r, and 4 in an inserted base, which has no r; every other code 4.  An M, = or X
+ * column adds to pair[5 r + b] and is ambiguous if r or b is 4, else a match if r == b, else a sub.  With v the reference
+ * base's class byte, hp_cols[v] counts the M = X and D columns, hp_sub[v] the sub columns, hp_del[v] the D columns.  An I op of
+ * length >= 1 adds to ins_events and ins_len[min(length, 63)], each of its bases to ins and ins_base[b]; a D op of length >= 1
+ * to del_events and del_len[min(length, 63)], each of its bases to del and del_base[r].  S adds to soft, H to hard, N only
+ * advances, P and ops of length 0 do nothing.  Where the record has qualities (the first byte is not 0xFF), with q' = min(q,
+ * 127): qcal[q'][0] counts the M = X columns that are not ambiguous, qcal[q'][1] the sub columns, qcal[q'][2] the inserted bases.
+ * Per scored record: cols = m + ins + del; with cols >= 1 identity_ppm = match * 1000000 / cols (integer division),
+ * hist_identity[identity_ppm / 1000] += 1; nm_derived = sub + ins + del; no_nm if it has no NM or a negative one, else
+ * nm_unchecked if ambiguous > 0, else nm_agree if NM == nm_derived, else nm_differ.
+ * counts: records, skipped_flag, unaligned, skipped_mapq, skipped_ref, aligned, no_seq, misfit, scored, no_nm, nm_unchecked,
+ * nm_agree, nm_differ, with_qual.  totals, over scored records: cols, match, sub, ambiguous, ins, del, ins_events, del_events,
+ * soft, hard, identity_sum.
+ * The fit, over the classes v = 1 .. 10: x = v - 1, c = hp_cols[v], d = hp_del[v]; W = sum c, Sx = sum c x, Sxx = sum c x^2,
+ * Sy = sum d, Sxy = sum d x; Num = W Sxy - Sx Sy, Den = Sxx Sy - Sx Sxy.  fit_ok = 1 only where Sy > 0 and Den > 0; then
+ * fit_bias_milli = 1000 + floor(9000 Num / Den), floored toward minus infinity and held to +-2^62, and fit_suggest_milli is
+ * that value held to 1000 .. 10000; else all three are 0.  It is the weighted least-squares line of the deletion rate on the
+ * class, slope over intercept: the simulator's deletion rate is proportional to 1 + (bias - 1) (v - 1) / 9 (pbsim.cpp:673-697).
+ * The per-read text, only where sink->on_text is not NULL, in offset order, in pieces of at most piece_bytes (a piece may end
+ * inside a line), one line per aligned record, in file order and then record order:
+ *   name\tclass\tlength\tcols\tmatch\tsub\tambiguous\tins\tdel\tsoft\tnm_tag\tnm_derived\tidentity_ppm\n
+ * class S (scored), N (no_seq) or F (misfit); length l_seq; cols, ins, del, soft from the CIGAR; nm_tag where NM is there and
+ * not negative; match, sub, ambiguous and nm_derived of a scored record; identity_ppm where it has cols >= 1; a field its record
+ * does not define is "*".  The first callback comes when every file has been read.
+ * tests/errors_model.py states the rule in plain Python.  exclude_flags outside 0 .. 65535, min_mapq outside 0 .. 255, a
+ * negative piece_bytes, a missing name and two equal names fail before any device work; a file of 2^36 inflated bytes or more
+ * and 2^32 - 1 records or more in one file are refused; the stage holds the genome, one file's inflated stream and 93 bytes per
+ * record (101 with the text) in HBM at once and does not chunk: an allocation that does not fit fails with the bytes it needed; a tables-only
+ * context fails as pbsim_inflate_buffer does.  After any failure the context stays usable. */
+typedef struct pbsim_errors_ref {
+  const char *name;
+  const void *lines;
+  int64_t bytes;
+} pbsim_errors_ref;
+typedef struct pbsim_errors_file {
+  const void *bam;
+  int64_t n;
+  const char *ref_name; /* NULL: the file's own reference names */
+} pbsim_errors_file;
+typedef struct pbsim_errors_opts { /* NULL: {0x900, 0, 0} */
+  int32_t exclude_flags, min_mapq;
+  int64_t piece_bytes; /* 0: the default; else the most text one on_text call carries */
+} pbsim_errors_opts;
+typedef struct pbsim_errors_sink {
+  void *user;
+  int (*on_text)(void *user, const char *bytes, int64_t n, int64_t offset); /* in offset order; may be NULL */
+} pbsim_errors_sink;
+typedef struct pbsim_errors_result {
+  int64_t counts[14];
+  int64_t totals[11];
+  int64_t pair[25];
+  int64_t hp_cols[12], hp_sub[12], hp_del[12];
+  int64_t ins_len[64], del_len[64];
+  int64_t ins_base[5], del_base[5];
+  int64_t qcal[128][3];
+  int64_t hist_identity[1001];
+  int64_t fit_ok, fit_bias_milli, fit_suggest_milli;
+} pbsim_errors_result;
+int pbsim_bam_errors(pbsim_ctx *ctx, const pbsim_errors_ref *refs, int n_refs, const pbsim_errors_file *files, int n_files,
+                     const pbsim_errors_opts *opts, const pbsim_errors_sink *sink, pbsim_errors_result *result);
+/* The report text, no device needed (the three fit fields are not read: the fit is made again from hp_cols and hp_del):
+ * "# records=N skipped_flag=N .. with_qual=N", the counts by their names; "E" and the first ten totals, then sub, ins and del in
+ * ppm of cols and identity_sum / the reads of hist_identity; five lines "M\t<A C G T N>" with the row of pair; "HP\t<v>\t<cols>\t
+ * <sub>\t<del>\t<del * 1000000 / cols>" per class with cols > 0; "B\t<fit_ok>\t<fit_bias_milli>\t<fit_suggest_milli>"; "IL\t<bin>\t
+ * <events>" and "DL\t<bin>\t<events>" for the bins that are not empty; "IB" and "DB" with the five values of ins_base and
+ * del_base; "QC\t<q>\t<cols>\t<sub>\t<ins>\t<empirical Q milli>" per q with a value that is not 0, the last floor(-10000 log10(sub
+ * / cols)) in double arithmetic, "*" where cols or sub is 0; "HI\t<bin>\t<reads>".  Integer divisions; 0 where the divisor is 0.
+ * Returns the text's length, and writes it (no NUL) where buf holds cap >= that many bytes; -1: bad argument. */
+int64_t pbsim_errors_report(const pbsim_errors_result *result, char *buf, int64_t cap);
 
 /* ---- batch primitives (used by the drivers above, bench.py, multi-GPU) ------
  * pbsim_batch_walk     header draw + bucketing + HMM walk of reads

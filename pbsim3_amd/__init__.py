@@ -194,6 +194,39 @@ STATS_COUNTS = ["records", "skipped_flag", "unaligned", "skipped_mapq", "aligned
 STATS_LEN_ROW = ["n", "bases", "min", "max", "mean_milli", "sd", "median"] + ["N%d" % x for x in range(10, 100, 10)]
 STATS_TOTALS = ["cols", "sub", "ins", "del", "ins_events", "del_events", "soft", "hard", "identity_sum", "acc_sum", "acc_reads", "q_sum"]
 
+
+class ErrorsRef(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("lines", C.c_void_p), ("bytes", C.c_int64)]
+
+
+class ErrorsFile(C.Structure):
+    _fields_ = [("bam", C.c_void_p), ("n", C.c_int64), ("ref_name", C.c_char_p)]
+
+
+class ErrorsOpts(C.Structure):
+    _fields_ = [("exclude_flags", C.c_int32), ("min_mapq", C.c_int32), ("piece_bytes", C.c_int64)]
+
+
+ERRORS_TEXT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64)
+
+
+class ErrorsSink(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("on_text", ERRORS_TEXT_CB)]
+
+
+ERRORS_COUNTS = ["records", "skipped_flag", "unaligned", "skipped_mapq", "skipped_ref", "aligned", "no_seq", "misfit", "scored", "no_nm",
+                 "nm_unchecked", "nm_agree", "nm_differ", "with_qual"]
+ERRORS_TOTALS = ["cols", "match", "sub", "ambiguous", "ins", "del", "ins_events", "del_events", "soft", "hard", "identity_sum"]
+# the arrays of pbsim_errors_result behind counts and totals, in the struct's order (qcal: [128][3] laid flat)
+ERRORS_ARRAYS = [("pair", 25), ("hp_cols", 12), ("hp_sub", 12), ("hp_del", 12), ("ins_len", 64), ("del_len", 64), ("ins_base", 5),
+                 ("del_base", 5), ("qcal", 384), ("hist_identity", 1001)]
+ERRORS_FIT = ["fit_ok", "fit_bias_milli", "fit_suggest_milli"]
+
+
+class ErrorsResult(C.Structure):
+    _fields_ = [("counts", C.c_int64 * 14), ("totals", C.c_int64 * 11)] + [(name, C.c_int64 * n) for name, n in ERRORS_ARRAYS] + \
+               [(name, C.c_int64) for name in ERRORS_FIT]
+
 # every symbol include/pbsim3_amd.h declares: (name, restype, argtypes)
 API = [
     ("pbsim_job_add_record", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
@@ -286,6 +319,9 @@ API = [
                                        C.c_char_p, C.c_int64]),
     ("pbsim_bam_stats", C.c_int, [C.c_void_p, C.POINTER(StatsFile), C.c_int, C.POINTER(StatsOpts), C.POINTER(StatsSink)] + [C.POINTER(C.c_int64)] * 6),
     ("pbsim_stats_report", C.c_int64, [C.POINTER(C.c_int64)] * 6 + [C.c_char_p, C.c_int64]),
+    ("pbsim_bam_errors", C.c_int, [C.c_void_p, C.POINTER(ErrorsRef), C.c_int, C.POINTER(ErrorsFile), C.c_int, C.POINTER(ErrorsOpts),
+                                   C.POINTER(ErrorsSink), C.POINTER(ErrorsResult)]),
+    ("pbsim_errors_report", C.c_int64, [C.POINTER(ErrorsResult), C.c_char_p, C.c_int64]),
     ("pbsim_batch_walk", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_slot_count", C.c_int, []),
     ("pbsim_select_slot", C.c_int, [C.c_void_p, C.c_int]),
@@ -405,6 +441,36 @@ def stats_report(counts, len_row, totals, hist_q, hist_identity, hist_qacc) -> b
         raise PbsimError("pbsim_stats_report: bad argument")
     buf = C.create_string_buffer(max(n, 1))
     load().pbsim_stats_report(*arrs, buf, n)
+    return buf.raw[:n]
+
+
+def _errors_dict(res) -> dict:
+    """an ErrorsResult as a dict: counts and totals as dicts by name, the arrays as lists, the fit's three values"""
+    out = dict(counts=dict(zip(ERRORS_COUNTS, (int(v) for v in res.counts))), totals=dict(zip(ERRORS_TOTALS, (int(v) for v in res.totals))))
+    for name, _ in ERRORS_ARRAYS:
+        out[name] = [int(v) for v in getattr(res, name)]
+    for name in ERRORS_FIT:
+        out[name] = int(getattr(res, name))
+    return out
+
+
+def errors_report(result) -> bytes:
+    """The report text of Context.bam_errors's result (the dict; counts and totals as dicts by name or as the values in order; the
+    fit's values are not read): pbsim_errors_report, no device needed."""
+    def vals(x, names):
+        return [int(x[k]) for k in names] if isinstance(x, dict) else [int(v) for v in x]
+    parts = [("counts", vals(result["counts"], ERRORS_COUNTS)), ("totals", vals(result["totals"], ERRORS_TOTALS))] + \
+            [(name, [int(v) for v in result[name]]) for name, _ in ERRORS_ARRAYS]
+    res = ErrorsResult()
+    for name, v in parts:
+        if len(v) != len(getattr(res, name)):
+            raise ValueError("errors_report: %s has %d values, not %d" % (name, len(v), len(getattr(res, name))))
+        setattr(res, name, type(getattr(res, name))(*v))
+    n = load().pbsim_errors_report(C.byref(res), None, 0)
+    if n < 0:
+        raise PbsimError("pbsim_errors_report: bad argument")
+    buf = C.create_string_buffer(max(n, 1))
+    load().pbsim_errors_report(C.byref(res), buf, n)
     return buf.raw[:n]
 
 
@@ -1003,6 +1069,39 @@ class Context:
         hists = tuple(np.array(list(h), dtype=np.int64) for h in out[3:])
         res = (cd, ld, td) + hists + (stats_report(cd, ld, td, *hists),)
         return res + (b"".join(parts),) if text else res
+
+    def bam_errors(self, files, genome, ref_names=None, text=False, min_mapq=0, exclude_flags=0x900, piece_bytes=0):
+        """The error profile of the aligned reads of BAM files against their genome (pbsim_bam_errors; the rule:
+        include/pbsim3_amd.h).  files: the bytes of one file, or a list of them, summed into one result; genome: a list of (name,
+        sequence lines) with names as str or bytes, line feeds allowed in the lines; ref_names: per file None or the name its only
+        reference has in the genome.  Returns (result, report): a dict -- counts and totals as dicts by name, the arrays pair,
+        hp_cols, hp_sub, hp_del, ins_len, del_len, ins_base, del_base, qcal (128 x 3, flat) and hist_identity as lists, fit_ok,
+        fit_bias_milli, fit_suggest_milli -- and the report text; with `text` a third item, the per-read lines."""
+        if isinstance(files, (bytes, bytearray, memoryview)):
+            files = [files]
+        files = [bytes(f) for f in files]
+        names = list(ref_names) if ref_names is not None else [None] * len(files)
+        if len(names) != len(files):
+            raise ValueError("ref_names: one entry per file (%d given for %d files)" % (len(names), len(files)))
+        names = [None if nm is None else (nm.encode() if isinstance(nm, str) else bytes(nm)) for nm in names]
+        genome = [((nm.encode() if isinstance(nm, str) else bytes(nm)), bytes(lines)) for nm, lines in genome]
+        refs = (ErrorsRef * max(len(genome), 1))(*[ErrorsRef(nm, C.cast(C.c_char_p(lines), C.c_void_p), len(lines)) for nm, lines in genome])
+        arr = (ErrorsFile * max(len(files), 1))(*[ErrorsFile(C.cast(C.c_char_p(f), C.c_void_p), len(f), nm) for f, nm in zip(files, names)])
+        parts, at = [], [0]
+
+        def on_text(user, ptr, n, offset):
+            if offset != at[0]:      # (the pieces come in offset order)
+                return 0
+            parts.append(C.string_at(ptr, n))
+            at[0] += n
+            return 1
+        sink = ErrorsSink(None, ERRORS_TEXT_CB(on_text) if text else ERRORS_TEXT_CB())
+        opts = ErrorsOpts(int(exclude_flags), int(min_mapq), int(piece_bytes))
+        res = ErrorsResult()
+        _check(self.lib.pbsim_bam_errors(self.h, refs, len(genome), arr, len(files), C.byref(opts), C.byref(sink), C.byref(res)))
+        out = _errors_dict(res)
+        got = (out, errors_report(out))
+        return got + (b"".join(parts),) if text else got
 
     def set_transcripts(self, ids, plus, minus, seqs):
         """ids: list[str]; plus/minus: expression counts; seqs: list[bytes]."""

@@ -251,3 +251,54 @@ def stats_bam(argv):
     if not got["bams"]:
         raise ValueError("--stats-bam FILE: name the BAM file.")
     return got
+
+
+def errors_bam(argv):
+    """`pbsim --errors-bam FILE [--errors-bam FILE ...] --errors-genome FASTA [--errors-ref-names a,b,..] [--errors-out FILE]
+    [--errors-min-mapq Q] [--errors-exclude-flags F]` -> dict(bams, genome, ref_names, out, min_mapq, exclude_flags): the stand-alone
+    mode that profiles the errors of aligned reads against their genome (pbsim_bam_errors).  F is decimal or 0x hexadecimal.  What
+    pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
+    takes = ("--errors-bam", "--errors-genome", "--errors-ref-names", "--errors-out", "--errors-min-mapq", "--errors-exclude-flags", "--device")
+    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
+    got = dict(bams=[], genome=None, ref_names=None, out=None, min_mapq=0, exclude_flags=0x900)
+    if any(a.split("=")[0] in ranks for a in argv):
+        raise ValueError("--errors-bam runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a not in takes:
+            raise ValueError("(%s): --errors-bam takes --errors-genome, --errors-ref-names, --errors-out, --errors-min-mapq, --errors-exclude-flags "
+                             "and --device, and no other option." % a)
+        if i + 1 >= len(argv):
+            raise ValueError("(%s): the option needs a value." % a)
+        v = argv[i + 1]
+        i += 2
+        if a == "--errors-bam":
+            got["bams"].append(v)
+        elif a == "--errors-genome":
+            got["genome"] = v
+        elif a == "--errors-ref-names":
+            got["ref_names"] = v.split(",")
+        elif a == "--errors-out":
+            got["out"] = v
+        elif a == "--errors-min-mapq":
+            n = _whole(v)
+            if n is None or n > 255:
+                raise ValueError("(errors-min-mapq: %s): a whole number, 0 .. 255." % v)
+            got["min_mapq"] = n
+        elif a == "--errors-exclude-flags":
+            n = _whole(v, 16 if v[:2] in ("0x", "0X") else 10)
+            if n is None or n > 65535:
+                raise ValueError("(errors-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535." % v)
+            got["exclude_flags"] = n
+    if not got["bams"]:
+        raise ValueError("--errors-bam FILE: name the BAM file.")
+    if not got["genome"]:
+        raise ValueError("--errors-bam needs --errors-genome FASTA: the genome the reads were aligned to.")
+    if got["ref_names"] is not None:
+        if len(got["ref_names"]) != len(got["bams"]):
+            raise ValueError("(errors-ref-names): %d names for %d --errors-bam files: the k-th name goes to the k-th file."
+                             % (len(got["ref_names"]), len(got["bams"])))
+        if "" in got["ref_names"]:
+            raise ValueError("(errors-ref-names): an empty name.")
+    return got

@@ -349,6 +349,10 @@ void print_help() {
           "  pbsim --stats-bam FILE [--stats-bam FILE ...] [--stats-out FILE] [--stats-min-mapq Q (0)] [--stats-exclude-flags F (0x900)]:\n"
           "  no simulation; the reads of BAM files summarised on the GPU: lengths, error rates from CIGAR and NM, qualities;\n"
           "  the report to stdout, one line per read to --stats-out\n"
+          "  pbsim --errors-bam FILE [--errors-bam FILE ...] --errors-genome FASTA [--errors-ref-names a,b,..] [--errors-out FILE]\n"
+          "  [--errors-min-mapq Q (0)] [--errors-exclude-flags F (0x900)]: no simulation; the aligned reads of BAM files against\n"
+          "  their genome on the GPU: substitution matrix, indel lengths, deletions by homopolymer class and the --hp-del-bias they\n"
+          "  suggest, qualities against the errors found, NM checked; the report to stdout, one line per read to --errors-out\n"
           "  --genome, --transcript, --template and --sample may be gzip-compressed (recognised by content): BGZF is\n"
           "  inflated on the GPU, other gzip by zlib on the host; the whole inflated file is held in host memory\n\n");
 }
@@ -1255,6 +1259,112 @@ int stats_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
   return 0;
 }
 
+// `pbsim --errors-bam FILE [--errors-bam FILE ...] --errors-genome FASTA ...`: the error profile of aligned reads against their
+// genome (pbsim_bam_errors), the report to stdout, the per-read text to --errors-out.  What can be refused from the command line
+// alone is refused before a GPU is touched.
+int errors_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
+  if (comm && comm->world > 1) die(": --errors-bam runs on one GPU.");
+  std::vector<std::string> in_names, names;
+  std::string out_name, genome_name, names_arg;
+  bool have_names = false;
+  long long min_mapq = 0, exclude = 0x900;
+  for (int i = 1; i < argc; i++) {
+    const std::string a = argv[i];
+    const bool takes = a == "--errors-bam" || a == "--errors-genome" || a == "--errors-ref-names" || a == "--errors-out" || a == "--errors-min-mapq" ||
+                       a == "--errors-exclude-flags" || a == "--device";
+    if (!takes)
+      die(" (%s): --errors-bam takes --errors-genome, --errors-ref-names, --errors-out, --errors-min-mapq, --errors-exclude-flags and --device, "
+          "and no other option.",
+          argv[i]);
+    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
+    const char *v = argv[++i];
+    if (a == "--errors-bam") in_names.push_back(v);
+    else if (a == "--errors-genome") genome_name = v;
+    else if (a == "--errors-ref-names") names_arg = v, have_names = true;
+    else if (a == "--errors-out") out_name = v;
+    else if (a == "--device") device = device >= 0 ? device : atoi(v);
+    else if (a == "--errors-min-mapq") {
+      if (!whole_number(v, 10, 0, 255, &min_mapq)) die(" (errors-min-mapq: %s): a whole number, 0 .. 255.", v);
+    } else {
+      const bool hex = v[0] == '0' && (v[1] == 'x' || v[1] == 'X');
+      if (!whole_number(v, hex ? 16 : 10, 0, 65535, &exclude)) die(" (errors-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535.", v);
+    }
+  }
+  if (in_names.empty()) die(": --errors-bam FILE: name the BAM file.");
+  if (genome_name.empty()) die(": --errors-bam needs --errors-genome FASTA: the genome the reads were aligned to.");
+  if (have_names) {
+    for (size_t at = 0;;) {
+      const size_t comma = names_arg.find(',', at);
+      names.push_back(names_arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
+      if (comma == std::string::npos) break;
+      at = comma + 1;
+    }
+    char got[32], want[32];
+    snprintf(got, sizeof got, "%zu", names.size());
+    snprintf(want, sizeof want, "%zu", in_names.size());
+    if (names.size() != in_names.size()) die(" (errors-ref-names): %s names for %s --errors-bam files: the k-th name goes to the k-th file.", got, want);
+    for (const std::string &n : names)
+      if (n.empty()) die(" (errors-ref-names): an empty name.");
+  }
+  std::vector<MappedFile> files(in_names.size());
+  for (size_t f = 0; f < files.size(); f++)
+    if (!files[f].open_file(in_names[f])) die(": Cannot open file: %s", in_names[f].c_str());
+  // the genome: each record's sequence lines as they lie in the file, its name the id up to the first white space
+  pbsim::FastaMap fm;
+  {
+    pbsim::GenomeInfo gm;
+    bool fallback = false;
+    std::string err;
+    if (!pbsim::map_genome(genome_name.c_str(), &fm, &gm, false, &fallback, &err))
+      die(": --errors-genome %s: %s", genome_name.c_str(),
+          fallback ? "not a FASTA file that can be mapped (a regular file that begins with '>' and holds no NUL byte)" : err.c_str());
+  }
+  std::vector<std::string> ref_names;
+  for (const pbsim::FastaRecord &r : fm.recs) ref_names.push_back(r.id.substr(0, r.id.find_first_of(" \t\r\n\v\f")));
+  std::vector<pbsim_errors_ref> refs;
+  for (size_t r = 0; r < fm.recs.size(); r++) refs.push_back(pbsim_errors_ref{ref_names[r].c_str(), fm.recs[r].lines, fm.recs[r].bytes});
+  pbsim_params p;
+  pbsim_params_default(&p);
+  p.strategy = PBSIM_STRATEGY_WGS;
+  p.method = PBSIM_METHOD_ERR;
+  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
+  if (!ctx) check(0);
+  struct Result {
+    FILE *fp = NULL;
+    bool write_failed = false;
+  } res;
+  if (!out_name.empty()) {
+    res.fp = fopen(out_name.c_str(), "wb");
+    if (!res.fp) die(": Cannot open output file: %s", out_name.c_str());
+  }
+  std::vector<pbsim_errors_file> in(files.size());
+  for (size_t f = 0; f < files.size(); f++) in[f] = pbsim_errors_file{files[f].map, (int64_t)files[f].n, have_names ? names[f].c_str() : NULL};
+  pbsim_errors_opts opts = {(int32_t)exclude, (int32_t)min_mapq, 0};
+  pbsim_errors_sink sink = {&res, [](void *u, const char *z, int64_t k, int64_t) {
+                              Result *x = (Result *)u;
+                              if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
+                              return x->write_failed ? 0 : 1;
+                            }};
+  if (!res.fp) sink.on_text = NULL;
+  std::vector<pbsim_errors_result> result(1);
+  const bool ok = pbsim_bam_errors(ctx, refs.data(), (int)refs.size(), in.data(), (int)in.size(), &opts, &sink, result.data()) != 0;
+  if (res.fp && fclose(res.fp) != 0) res.write_failed = true;
+  if (!ok || res.write_failed) {
+    fprintf(stderr, "ERROR: %s\n", res.write_failed ? ("write error on " + out_name).c_str() : pbsim_last_error());
+    if (in_names.size() > 1)
+      for (size_t f = 0; f < in_names.size(); f++) fprintf(stderr, "ERROR: file %zu is %s\n", f, in_names[f].c_str());
+    if (!out_name.empty()) unlink(out_name.c_str());
+    quit(-1);
+  }
+  std::string text((size_t)pbsim_errors_report(result.data(), NULL, 0), '\0');
+  pbsim_errors_report(result.data(), &text[0], (int64_t)text.size());
+  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
+  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
+  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
+  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int device) {
@@ -1266,6 +1376,8 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
     if (!strcmp(argv[i], "--depth-bam")) return depth_bam_main(argc, argv, comm, device);
   for (int i = 1; i < argc; i++)
     if (!strcmp(argv[i], "--stats-bam")) return stats_bam_main(argc, argv, comm, device);
+  for (int i = 1; i < argc; i++)
+    if (!strcmp(argv[i], "--errors-bam")) return errors_bam_main(argc, argv, comm, device);
   if (argc >= 2 && !strcmp(argv[1], "--sort-truth-bam")) {
     // the standalone mode: no simulation, the named files sorted and indexed in place on one GPU
     if (comm && comm->world > 1) die(": --sort-truth-bam runs on one GPU.");
