@@ -620,6 +620,76 @@ int pbsim_bam_errors(pbsim_ctx *ctx, const pbsim_errors_ref *refs, int n_refs, c
  * / cols)) in double arithmetic, "*" where cols or sub is 0; "HI\t<bin>\t<reads>".  Integer divisions; 0 where the divisor is 0.
  * Returns the text's length, and writes it (no NUL) where buf holds cap >= that many bytes; -1: bad argument. */
 int64_t pbsim_errors_report(const pbsim_errors_result *result, char *buf, int64_t cap);
+/* The pileup of the aligned reads of one or more BAM files against the genome they were aligned to, on the GPU: per reference
+ * position what the reads say there, the call of every site and the sites where the pile does not spell the genome (what
+ * `samtools mpileup`, `samtools consensus`, pysamstats --type variation or bam-readcount tell).
+ * The genome (refs), the files, the references looked up by name, the l_ref check, the container kinds and every refusal are
+ * pbsim_bam_errors's; so are the classes of a record (skipped_flag with exclude_flags, default 0x900; unaligned; skipped_mapq
+ * with min_mapq; skipped_ref; aligned; then no_seq, misfit, scored) and the resolution of the CIGAR with the CG placeholder.  Only
+ * a scored record adds to the pileup.  counts: records, skipped_flag, unaligned, skipped_mapq, skipped_ref, aligned, no_seq,
+ * misfit, scored.
+ * Cells.  Every position p of every genome record has eight cells: 0 .. 3 A C G T, 4 other, 5 del, 6 ins, 7 masked.  A cell is
+ * an unsigned 32-bit number and additions to it are modulo 2^32 (below 2^32 scored records only the ins cell can wrap, through
+ * that many I ops at one anchor); everything made from cells (depth, the sums) is 64-bit arithmetic on the cells' values.
+ * Columns.  r, the reference class, and b, the read class, are pbsim_bam_errors's (codes 1 2 4 8 -> 0 .. 3, code 0 -> r, every
+ * other code 4; a genome byte that is not A C G T has r = 4).  An M, = or X column at reference position p adds 1 to cell b of p
+ * -- unless the record has qualities (its first quality byte is not 0xFF) and the base's quality byte is below min_baseq
+ * (default 0): then it adds 1 to masked and nothing else.  A record without qualities is never masked.  A D column adds 1 to
+ * del.  N only advances; S, H, P and ops of length 0 do nothing.
+ * Insertions.  An I op of length >= 1 that begins where the record's reference position is q adds 1 to ins of q - 1 where
+ * q > pos, whichever op moved the position there; with q == pos (nothing of the reference consumed yet) it adds 1 to
+ * ins_unanchored and to no position.  Inserted bases are not looked at and their qualities mask nothing.
+ * Sites, over every position of every genome record.  depth = A + C + G + T + other + del (ins and masked are no part of it).
+ * A site is ref_n if the genome's class is 4; else low if depth < min_depth (default 1: an uncovered site is low); else called.
+ * The call is the largest of the five cells A C G T del; among equals the genome's own class wins if it is one of them, else the
+ * first in that order (so a called site whose five cells are all 0 -- only other there, or min_depth 0 -- calls the genome's
+ * base).  A called site is concordant if the call is the genome's class, a del_site if the call is del, else a sub_site;
+ * apart from that it is an ins_site if 2 ins > depth.  discordant counts the called sites that are a sub_site, a del_site or
+ * an ins_site, each once.  sites[]: sites, ref_n, low, called, concordant, sub_site, del_site, ins_site, discordant.
+ * cell_sums[k]: the sum of cell k over all positions.  max_depth: the largest depth of any position.  hp_called[v], hp_sub[v],
+ * hp_del[v], hp_ins[v]: the called sites, sub_sites, del_sites and ins_sites by the genome's class byte v, min(v, 11) as
+ * pbsim_bam_errors takes it: the consensus errors inside homopolymers.
+ * The text, only where sink->on_text is not NULL, in offset order, in pieces of at most piece_bytes (a piece may end inside a
+ * line), genome records in their order and positions ascending; format 0 (sites): the discordant sites only; format 1 (all):
+ * every position.  One line per site:
+ *   name\tpos1\tref\tdepth\tA\tC\tG\tT\tN\tdel\tins\tmasked\tcall\tclass\n
+ * name the genome record's; pos1 = p + 1; ref the prepared genome byte; N the other cell; call one of A C G T, * for del, and .
+ * where the site is not called; class one of ref_n, low, match, sub, del, match+ins, sub+ins, del+ins.
+ * The cells themselves, only where sink->on_cells is not NULL: a host copy per genome record in order, l_ref x 8 values,
+ * position-major, after the text.
+ * tests/pileup_model.py states the rule in plain Python.  exclude_flags outside 0 .. 65535, min_mapq and min_baseq outside
+ * 0 .. 255, min_depth < 0, format outside 0 and 1, a negative piece_bytes, a missing name and two equal names fail before any
+ * device work; a file of 2^36 inflated bytes or more and 2^32 - 1 records or more in one file are refused.  The stage holds in
+ * HBM at once the genome at 2 bytes per base, the cells at 32 bytes per position, a class byte per position, one file's inflated
+ * stream and 69 bytes per record (and the text), and does not chunk: an allocation that does not fit fails with the bytes it
+ * needed; a tables-only context fails as pbsim_inflate_buffer does.  After any failure the context stays usable. */
+typedef struct pbsim_pileup_opts { /* NULL: {0x900, 0, 0, 0, 1, 0} */
+  int32_t exclude_flags, min_mapq, min_baseq;
+  int32_t format;      /* 0 sites, 1 all */
+  int64_t min_depth;
+  int64_t piece_bytes; /* 0: the default; else the most text one on_text call carries */
+} pbsim_pileup_opts;
+typedef struct pbsim_pileup_sink {
+  void *user;
+  int (*on_text)(void *user, const char *bytes, int64_t n, int64_t offset); /* in offset order; may be NULL */
+  int (*on_cells)(void *user, int32_t ref, const uint32_t *cells, int64_t l_ref); /* host copy, l_ref x 8, per genome record in
+                                                                                      order, after the text; may be NULL */
+} pbsim_pileup_sink;
+typedef struct pbsim_pileup_result {
+  int64_t counts[9];
+  int64_t sites[9];
+  int64_t cell_sums[8];
+  int64_t ins_unanchored, max_depth;
+  int64_t hp_called[12], hp_sub[12], hp_del[12], hp_ins[12];
+} pbsim_pileup_result;
+int pbsim_bam_pileup(pbsim_ctx *ctx, const pbsim_errors_ref *refs, int n_refs, const pbsim_errors_file *files, int n_files,
+                     const pbsim_pileup_opts *opts, const pbsim_pileup_sink *sink, pbsim_pileup_result *result);
+/* The report text, no device needed: "# records=N skipped_flag=N .. scored=N", the counts by their names; "S" and the nine values
+ * of sites, then discordant * 1000000 / called (integer division; 0 where called is 0) and the consensus quality floor(-10000
+ * log10(discordant / called)) in double arithmetic, "*" where either is 0; "C" and the eight values of cell_sums, then
+ * ins_unanchored and max_depth; "HP\t<v>\t<called>\t<sub>\t<del>\t<ins>" per class with a value that is not 0.  Returns the text's
+ * length, and writes it (no NUL) where buf holds cap >= that many bytes; -1: bad argument. */
+int64_t pbsim_pileup_report(const pbsim_pileup_result *result, char *buf, int64_t cap);
 
 /* ---- batch primitives (used by the drivers above, bench.py, multi-GPU) ------
  * pbsim_batch_walk     header draw + bucketing + HMM walk of reads

@@ -227,6 +227,31 @@ class ErrorsResult(C.Structure):
     _fields_ = [("counts", C.c_int64 * 14), ("totals", C.c_int64 * 11)] + [(name, C.c_int64 * n) for name, n in ERRORS_ARRAYS] + \
                [(name, C.c_int64) for name in ERRORS_FIT]
 
+
+class PileupOpts(C.Structure):
+    _fields_ = [("exclude_flags", C.c_int32), ("min_mapq", C.c_int32), ("min_baseq", C.c_int32), ("format", C.c_int32),
+                ("min_depth", C.c_int64), ("piece_bytes", C.c_int64)]
+
+
+PILEUP_TEXT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64)
+PILEUP_CELLS_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64)
+
+
+class PileupSink(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("on_text", PILEUP_TEXT_CB), ("on_cells", PILEUP_CELLS_CB)]
+
+
+PILEUP_COUNTS = ["records", "skipped_flag", "unaligned", "skipped_mapq", "skipped_ref", "aligned", "no_seq", "misfit", "scored"]
+PILEUP_SITES = ["sites", "ref_n", "low", "called", "concordant", "sub_site", "del_site", "ins_site", "discordant"]
+PILEUP_CELLS = ["A", "C", "G", "T", "other", "del", "ins", "masked"]
+PILEUP_HP = ["hp_called", "hp_sub", "hp_del", "hp_ins"]
+PILEUP_FORMATS = {"sites": 0, "all": 1}
+
+
+class PileupResult(C.Structure):
+    _fields_ = [("counts", C.c_int64 * 9), ("sites", C.c_int64 * 9), ("cell_sums", C.c_int64 * 8), ("ins_unanchored", C.c_int64),
+                ("max_depth", C.c_int64)] + [(name, C.c_int64 * 12) for name in PILEUP_HP]
+
 # every symbol include/pbsim3_amd.h declares: (name, restype, argtypes)
 API = [
     ("pbsim_job_add_record", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
@@ -322,6 +347,9 @@ API = [
     ("pbsim_bam_errors", C.c_int, [C.c_void_p, C.POINTER(ErrorsRef), C.c_int, C.POINTER(ErrorsFile), C.c_int, C.POINTER(ErrorsOpts),
                                    C.POINTER(ErrorsSink), C.POINTER(ErrorsResult)]),
     ("pbsim_errors_report", C.c_int64, [C.POINTER(ErrorsResult), C.c_char_p, C.c_int64]),
+    ("pbsim_bam_pileup", C.c_int, [C.c_void_p, C.POINTER(ErrorsRef), C.c_int, C.POINTER(ErrorsFile), C.c_int, C.POINTER(PileupOpts),
+                                   C.POINTER(PileupSink), C.POINTER(PileupResult)]),
+    ("pbsim_pileup_report", C.c_int64, [C.POINTER(PileupResult), C.c_char_p, C.c_int64]),
     ("pbsim_batch_walk", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_slot_count", C.c_int, []),
     ("pbsim_select_slot", C.c_int, [C.c_void_p, C.c_int]),
@@ -471,6 +499,37 @@ def errors_report(result) -> bytes:
         raise PbsimError("pbsim_errors_report: bad argument")
     buf = C.create_string_buffer(max(n, 1))
     load().pbsim_errors_report(C.byref(res), buf, n)
+    return buf.raw[:n]
+
+
+def _pileup_dict(res) -> dict:
+    """a PileupResult as a dict: counts and sites as dicts by name, cell_sums as a dict by cell, the four arrays as lists"""
+    out = dict(counts=dict(zip(PILEUP_COUNTS, (int(v) for v in res.counts))), sites=dict(zip(PILEUP_SITES, (int(v) for v in res.sites))),
+               cell_sums=dict(zip(PILEUP_CELLS, (int(v) for v in res.cell_sums))), ins_unanchored=int(res.ins_unanchored),
+               max_depth=int(res.max_depth))
+    for name in PILEUP_HP:
+        out[name] = [int(v) for v in getattr(res, name)]
+    return out
+
+
+def pileup_report(result) -> bytes:
+    """The report text of Context.bam_pileup's result (the dict; counts, sites and cell_sums as dicts by name or as the values in
+    order): pbsim_pileup_report, no device needed."""
+    def vals(x, names):
+        return [int(x[k]) for k in names] if isinstance(x, dict) else [int(v) for v in x]
+    parts = [("counts", vals(result["counts"], PILEUP_COUNTS)), ("sites", vals(result["sites"], PILEUP_SITES)),
+             ("cell_sums", vals(result["cell_sums"], PILEUP_CELLS))] + [(name, [int(v) for v in result[name]]) for name in PILEUP_HP]
+    res = PileupResult()
+    for name, v in parts:
+        if len(v) != len(getattr(res, name)):
+            raise ValueError("pileup_report: %s has %d values, not %d" % (name, len(v), len(getattr(res, name))))
+        setattr(res, name, type(getattr(res, name))(*v))
+    res.ins_unanchored, res.max_depth = int(result["ins_unanchored"]), int(result["max_depth"])
+    n = load().pbsim_pileup_report(C.byref(res), None, 0)
+    if n < 0:
+        raise PbsimError("pbsim_pileup_report: bad argument")
+    buf = C.create_string_buffer(max(n, 1))
+    load().pbsim_pileup_report(C.byref(res), buf, n)
     return buf.raw[:n]
 
 
@@ -1102,6 +1161,51 @@ class Context:
         out = _errors_dict(res)
         got = (out, errors_report(out))
         return got + (b"".join(parts),) if text else got
+
+    def bam_pileup(self, files, genome, ref_names=None, text=False, fmt="sites", min_mapq=0, exclude_flags=0x900, min_baseq=0, min_depth=1,
+                   arrays=False, piece_bytes=0):
+        """The pileup of the aligned reads of BAM files against their genome (pbsim_bam_pileup; the rule: include/pbsim3_amd.h).
+        files, genome and ref_names as bam_errors takes them; fmt: "sites" (the discordant sites) or "all" (every position).
+        Returns (result, report): a dict -- counts, sites and cell_sums as dicts by name, ins_unanchored, max_depth, and hp_called,
+        hp_sub, hp_del, hp_ins as lists -- and the report text; with `text` a further item, the lines; with `arrays` a further
+        item, a list with one uint32 tensor [l_ref, 8] per genome record: the cells A C G T other del ins masked."""
+        import numpy as np
+        if arrays:
+            import torch
+        if fmt not in PILEUP_FORMATS:
+            raise ValueError("fmt must be sites or all")
+        if isinstance(files, (bytes, bytearray, memoryview)):
+            files = [files]
+        files = [bytes(f) for f in files]
+        names = list(ref_names) if ref_names is not None else [None] * len(files)
+        if len(names) != len(files):
+            raise ValueError("ref_names: one entry per file (%d given for %d files)" % (len(names), len(files)))
+        names = [None if nm is None else (nm.encode() if isinstance(nm, str) else bytes(nm)) for nm in names]
+        genome = [((nm.encode() if isinstance(nm, str) else bytes(nm)), bytes(lines)) for nm, lines in genome]
+        refs = (ErrorsRef * max(len(genome), 1))(*[ErrorsRef(nm, C.cast(C.c_char_p(lines), C.c_void_p), len(lines)) for nm, lines in genome])
+        arr = (ErrorsFile * max(len(files), 1))(*[ErrorsFile(C.cast(C.c_char_p(f), C.c_void_p), len(f), nm) for f, nm in zip(files, names)])
+        parts, at, cells = [], [0], []
+
+        def on_text(user, ptr, n, offset):
+            if offset != at[0]:      # (the pieces come in offset order)
+                return 0
+            parts.append(C.string_at(ptr, n))
+            at[0] += n
+            return 1
+
+        def on_cells(user, ref, ptr, l_ref):
+            a = np.frombuffer(C.string_at(ptr, 32 * l_ref), dtype=np.uint32).copy() if l_ref else np.zeros(0, np.uint32)
+            cells.append(torch.from_numpy(a.reshape(l_ref, 8)))
+            return 1
+        sink = PileupSink(None, PILEUP_TEXT_CB(on_text) if text else PILEUP_TEXT_CB(), PILEUP_CELLS_CB(on_cells) if arrays else PILEUP_CELLS_CB())
+        opts = PileupOpts(int(exclude_flags), int(min_mapq), int(min_baseq), PILEUP_FORMATS[fmt], int(min_depth), int(piece_bytes))
+        res = PileupResult()
+        _check(self.lib.pbsim_bam_pileup(self.h, refs, len(genome), arr, len(files), C.byref(opts), C.byref(sink), C.byref(res)))
+        out = _pileup_dict(res)
+        got = (out, pileup_report(out))
+        if text:
+            got += (b"".join(parts),)
+        return got + (cells,) if arrays else got
 
     def set_transcripts(self, ids, plus, minus, seqs):
         """ids: list[str]; plus/minus: expression counts; seqs: list[bytes]."""

@@ -302,3 +302,59 @@ def errors_bam(argv):
         if "" in got["ref_names"]:
             raise ValueError("(errors-ref-names): an empty name.")
     return got
+
+
+def pileup_bam(argv):
+    """`pbsim --pileup-bam FILE [--pileup-bam FILE ...] --pileup-genome FASTA [--pileup-ref-names a,b,..] [--pileup-out FILE]
+    [--pileup-format sites|all] [--pileup-min-mapq N] [--pileup-min-baseq N] [--pileup-min-depth N]` -> dict(bams, genome, ref_names,
+    out, fmt, min_mapq, min_baseq, min_depth): the stand-alone mode that piles the aligned reads up against their genome
+    (pbsim_bam_pileup).  What pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
+    takes = ("--pileup-bam", "--pileup-genome", "--pileup-ref-names", "--pileup-out", "--pileup-format", "--pileup-min-mapq", "--pileup-min-baseq",
+             "--pileup-min-depth", "--device")
+    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
+    got = dict(bams=[], genome=None, ref_names=None, out=None, fmt="sites", min_mapq=0, min_baseq=0, min_depth=1)
+    if any(a.split("=")[0] in ranks for a in argv):
+        raise ValueError("--pileup-bam runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a not in takes:
+            raise ValueError("(%s): --pileup-bam takes --pileup-genome, --pileup-ref-names, --pileup-out, --pileup-format, --pileup-min-mapq, "
+                             "--pileup-min-baseq, --pileup-min-depth and --device, and no other option." % a)
+        if i + 1 >= len(argv):
+            raise ValueError("(%s): the option needs a value." % a)
+        v = argv[i + 1]
+        i += 2
+        if a == "--pileup-bam":
+            got["bams"].append(v)
+        elif a == "--pileup-genome":
+            got["genome"] = v
+        elif a == "--pileup-ref-names":
+            got["ref_names"] = v.split(",")
+        elif a == "--pileup-out":
+            got["out"] = v
+        elif a == "--pileup-format":
+            if v not in ("sites", "all"):
+                raise ValueError("(pileup-format: %s): sites or all." % v)
+            got["fmt"] = v
+        elif a in ("--pileup-min-mapq", "--pileup-min-baseq"):
+            n = _whole(v)
+            if n is None or n > 255:
+                raise ValueError("(%s: %s): a whole number, 0 .. 255." % (a[2:], v))
+            got[a[9:].replace("-", "_")] = n
+        elif a == "--pileup-min-depth":
+            n = _whole(v)
+            if n is None or n > 1000000000000:
+                raise ValueError("(pileup-min-depth: %s): a whole number, 0 .. 1000000000000." % v)
+            got["min_depth"] = n
+    if not got["bams"]:
+        raise ValueError("--pileup-bam FILE: name the BAM file.")
+    if not got["genome"]:
+        raise ValueError("--pileup-bam needs --pileup-genome FASTA: the genome the reads were aligned to.")
+    if got["ref_names"] is not None:
+        if len(got["ref_names"]) != len(got["bams"]):
+            raise ValueError("(pileup-ref-names): %d names for %d --pileup-bam files: the k-th name goes to the k-th file."
+                             % (len(got["ref_names"]), len(got["bams"])))
+        if "" in got["ref_names"]:
+            raise ValueError("(pileup-ref-names): an empty name.")
+    return got

@@ -1,8 +1,7 @@
 // bam_errors.cpp -- pbsim_bam_errors: the error profile of the aligned reads of BAM files against their genome (the rule:
-// include/pbsim3_amd.h, tests/errors_model.py).  The host's part: the genome into HBM, squeezed and prepared record by record
-// (kernels.hip's k_lines_* and k_hp_*), each file's stream and its records (bam_stream.cpp), the references by name
-// (bam_errors_rule.cpp), the buffers, and the text's way to the sink; the kernels are inflate.hip's, bam_scan.hip's and
-// bam_errors.hip's.
+// include/pbsim3_amd.h, tests/errors_model.py).  The host's part: the genome into HBM (bam_genome.cpp), each file's stream and
+// its records (bam_stream.cpp), the references by name (bam_errors_rule.cpp), the buffers, and the text's way to the sink
+// (bam_genome.cpp); the kernels are inflate.hip's, bam_scan.hip's and bam_errors.hip's.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -13,6 +12,7 @@
 #include <vector>
 
 #include "bam_errors.h"
+#include "bam_genome.h"
 #include "bam_scan.h"
 #include "bam_stream.h"
 #include "ctx.h"
@@ -27,110 +27,13 @@ const BamStage kStage = {kWho, "the stage holds the genome at 2 bytes per base, 
 
 int alloc(DevBuf &b, int64_t n, const char *what) { return bam_stage_alloc(kStage, b, n, what); }
 
-struct Genome {
-  DevBuf seq, hp;
-  std::vector<int64_t> at, len;  // where each record begins in both buffers (a multiple of 64); its bases
-};
-
-// every record's lines into HBM, squeezed to its bases and prepared on its own: 64 zero bytes lie behind each, which the
-// preparation's sixteen-byte loads need and which keep a run from reaching the next record
-int load_genome(pbsim_ctx *c, const pbsim_errors_ref *refs, int n_refs, Genome *g) {
-  hipStream_t st = c->stream;
-  int64_t total = 0, longest = 0;
-  for (int r = 0; r < n_refs; r++) {
-    g->at.push_back(total);
-    total += (refs[r].bytes + 63) / 64 * 64 + 64;
-    longest = std::max(longest, refs[r].bytes);
-  }
-  const int64_t line_tiles = (longest + 4095) / 4096, hp_tiles = (longest + kHpTile - 1) / kHpTile;
-  DevBuf d_lines, d_tmp, d_tiles, d_flags;
-  if (!alloc(g->seq, total, "the genome's bases") || !alloc(g->hp, total, "the genome's homopolymer classes") ||
-      !alloc(d_lines, longest + 64, "a genome record's lines") || !alloc(d_tmp, (line_tiles + 1 + line_tiles / 1024 + 16) * 8, "the squeeze's scratch") ||
-      !alloc(d_tiles, (hp_tiles + 1) * 4 * 8, "the preparation's scratch") || !alloc(d_flags, (int64_t)sizeof(DeviceFlags), "the preparation's flags"))
-    return PBSIM_FAILED;
-  HIP_OK(hipMemsetAsync(g->seq.p, 0, (size_t)total, st));
-  HIP_OK(hipMemsetAsync(g->hp.p, 0, (size_t)total, st));
-  int64_t *tmp = d_tmp.as<int64_t>();
-  for (int r = 0; r < n_refs; r++) {
-    const int64_t bytes = refs[r].bytes;
-    int64_t kept = 0;
-    if (bytes > 0) {
-      const int64_t n_tiles = (bytes + 4095) / 4096;
-      HIP_OK(hipMemcpyAsync(d_lines.p, refs[r].lines, (size_t)bytes, hipMemcpyHostToDevice, st));
-      launch_squeeze_lines(d_lines.as<uint8_t>(), bytes, g->seq.as<uint8_t>() + g->at[(size_t)r], tmp + 1, tmp + 1 + n_tiles + 1, tmp, st);
-      HIP_OK(hipGetLastError());
-      HIP_OK(hipMemcpyAsync(&kept, tmp, 8, hipMemcpyDeviceToHost, st));
-      HIP_OK(hipStreamSynchronize(st));  // (the staging buffer is the next record's too)
-    }
-    g->len.push_back(kept);
-    if (kept > 0) {
-      const int64_t n = (kept + kHpTile - 1) / kHpTile;
-      int64_t *t = d_tiles.as<int64_t>();
-      HIP_OK(hipMemsetAsync(d_flags.p, 0, sizeof(DeviceFlags), st));
-      launch_prepare_reference(g->seq.as<uint8_t>() + g->at[(size_t)r], g->hp.as<uint8_t>() + g->at[(size_t)r], 0, kept, t, t + (n + 1), t + 2 * (n + 1),
-                               t + 3 * (n + 1), 0, d_flags.as<DeviceFlags>(), st);
-      HIP_OK(hipGetLastError());
-    }
-  }
-  HIP_OK(hipStreamSynchronize(st));  // (the scratch goes with this frame)
-  return PBSIM_SUCCEEDED;
-}
-
-struct FileText {
-  DevBuf d;
-  int64_t n = 0;
-};
-
-// the texts, one file's behind the other, through two pinned pieces: one on its way to the host while the sink has the other.  A
-// piece does not cross from one file's text into the next one's buffer, so it may be shorter than piece_bytes there.
-int deliver_text(hipStream_t st, std::deque<FileText> &texts, int64_t n_text, int64_t piece_bytes, const pbsim_errors_sink *sink) {
-  const int64_t piece = std::min(piece_bytes, n_text);
-  HostBuf pinned[2];
-  hipEvent_t done[2] = {nullptr, nullptr};
-  for (int k = 0; k < 2; k++) {
-    if (pinned[k].ensure((size_t)piece) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(std::string(kWho) + "no pinned host memory for a piece of " + std::to_string(piece) + " bytes of text");
-    }
-  }
-  struct Events {
-    hipEvent_t *e;
-    ~Events() {
-      for (int k = 0; k < 2; k++)
-        if (e[k]) (void)hipEventDestroy(e[k]);
-    }
-  } guard = {done};
-  for (int k = 0; k < 2; k++) HIP_OK(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
-  struct Piece {
-    size_t f;
-    int64_t at, n;
-  };
-  std::vector<Piece> pieces;
-  for (size_t f = 0; f < texts.size(); f++)
-    for (int64_t at = 0; at < texts[f].n; at += piece) pieces.push_back({f, at, std::min(piece, texts[f].n - at)});
-  auto start_copy = [&](const Piece &p, int which) {
-    hipError_t e = hipMemcpyAsync(pinned[which].p, texts[p.f].d.as<char>() + p.at, (size_t)p.n, hipMemcpyDeviceToHost, st);
-    return e != hipSuccess ? e : hipEventRecord(done[which], st);
-  };
-  HIP_OK(start_copy(pieces[0], 0));
-  int64_t offset = 0;
-  for (size_t k = 0; k < pieces.size(); k++) {
-    const int which = (int)(k & 1);
-    if (k + 1 < pieces.size()) HIP_OK(start_copy(pieces[k + 1], which ^ 1));
-    HIP_OK(hipEventSynchronize(done[which]));
-    if (!sink->on_text(sink->user, (const char *)pinned[which].p, pieces[k].n, offset)) return fail("sink aborted (text)");
-    offset += pieces[k].n;
-  }
-  return PBSIM_SUCCEEDED;
-}
-
 int errors_bam(pbsim_ctx *c, const pbsim_errors_ref *refs, int n_refs, const pbsim_errors_file *files, int n_files, const pbsim_errors_opts &o,
                const pbsim_errors_sink *sink, pbsim_errors_result *result) {
   hipStream_t st = c->stream;
   BamPhases ph(st, "errors");
   const bool want_text = sink && sink->on_text;
   Genome genome;
-  if (!load_genome(c, refs, n_refs, &genome)) return PBSIM_FAILED;
+  if (!load_genome(c, kStage, refs, n_refs, &genome)) return PBSIM_FAILED;
   ph.mark("genome");
   const ErrGenome g = {genome.seq.as<uint8_t>(), genome.hp.as<uint8_t>()};
   DevBuf d_cells;
@@ -255,7 +158,7 @@ int errors_bam(pbsim_ctx *c, const pbsim_errors_ref *refs, int n_refs, const pbs
   std::vector<uint64_t> h_cells(kErrCells);
   HIP_OK(hipMemcpyAsync(h_cells.data(), d_cells.p, kErrCells * 8, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
-  if (want_text && n_text > 0 && !deliver_text(st, texts, n_text, o.piece_bytes, sink)) return PBSIM_FAILED;
+  if (want_text && n_text > 0 && !deliver_text(st, kStage, texts, n_text, o.piece_bytes, sink->on_text, sink->user)) return PBSIM_FAILED;
   HIP_OK(hipStreamSynchronize(st));
   ph.mark("deliver");
   // ---- what the caller is told

@@ -353,6 +353,11 @@ void print_help() {
           "  [--errors-min-mapq Q (0)] [--errors-exclude-flags F (0x900)]: no simulation; the aligned reads of BAM files against\n"
           "  their genome on the GPU: substitution matrix, indel lengths, deletions by homopolymer class and the --hp-del-bias they\n"
           "  suggest, qualities against the errors found, NM checked; the report to stdout, one line per read to --errors-out\n"
+          "  pbsim --pileup-bam FILE [--pileup-bam FILE ...] --pileup-genome FASTA [--pileup-ref-names a,b,..] [--pileup-out FILE]\n"
+          "  [--pileup-format sites|all (sites)] [--pileup-min-mapq N (0)] [--pileup-min-baseq N (0)] [--pileup-min-depth N (1)]:\n"
+          "  no simulation; the pileup of the aligned reads of BAM files against their genome on the GPU: per position the bases,\n"
+          "  deletions and insertions the reads show, the call of every site; the report to stdout, one line per discordant site\n"
+          "  (or per position) to --pileup-out\n"
           "  --genome, --transcript, --template and --sample may be gzip-compressed (recognised by content): BGZF is\n"
           "  inflated on the GPU, other gzip by zlib on the host; the whole inflated file is held in host memory\n\n");
 }
@@ -1365,6 +1370,119 @@ int errors_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
   return 0;
 }
 
+// `pbsim --pileup-bam FILE [--pileup-bam FILE ...] --pileup-genome FASTA ...`: the pileup of aligned reads against their genome
+// (pbsim_bam_pileup), the report to stdout, the sites' text to --pileup-out.  What can be refused from the command line alone is
+// refused before a GPU is touched.
+int pileup_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
+  if (comm && comm->world > 1) die(": --pileup-bam runs on one GPU.");
+  std::vector<std::string> in_names, names;
+  std::string out_name, genome_name, names_arg;
+  bool have_names = false;
+  long long min_mapq = 0, min_baseq = 0, min_depth = 1, format = 0;
+  for (int i = 1; i < argc; i++) {
+    const std::string a = argv[i];
+    const bool takes = a == "--pileup-bam" || a == "--pileup-genome" || a == "--pileup-ref-names" || a == "--pileup-out" || a == "--pileup-format" ||
+                       a == "--pileup-min-mapq" || a == "--pileup-min-baseq" || a == "--pileup-min-depth" || a == "--device";
+    if (!takes)
+      die(" (%s): --pileup-bam takes --pileup-genome, --pileup-ref-names, --pileup-out, --pileup-format, --pileup-min-mapq, --pileup-min-baseq, "
+          "--pileup-min-depth and --device, and no other option.",
+          argv[i]);
+    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
+    const char *v = argv[++i];
+    if (a == "--pileup-bam") in_names.push_back(v);
+    else if (a == "--pileup-genome") genome_name = v;
+    else if (a == "--pileup-ref-names") names_arg = v, have_names = true;
+    else if (a == "--pileup-out") out_name = v;
+    else if (a == "--device") device = device >= 0 ? device : atoi(v);
+    else if (a == "--pileup-format") {
+      if (!strcmp(v, "sites")) format = 0;
+      else if (!strcmp(v, "all")) format = 1;
+      else die(" (pileup-format: %s): sites or all.", v);
+    } else if (a == "--pileup-min-mapq") {
+      if (!whole_number(v, 10, 0, 255, &min_mapq)) die(" (pileup-min-mapq: %s): a whole number, 0 .. 255.", v);
+    } else if (a == "--pileup-min-baseq") {
+      if (!whole_number(v, 10, 0, 255, &min_baseq)) die(" (pileup-min-baseq: %s): a whole number, 0 .. 255.", v);
+    } else {
+      if (!whole_number(v, 10, 0, 1000000000000LL, &min_depth)) die(" (pileup-min-depth: %s): a whole number, 0 .. 1000000000000.", v);
+    }
+  }
+  if (in_names.empty()) die(": --pileup-bam FILE: name the BAM file.");
+  if (genome_name.empty()) die(": --pileup-bam needs --pileup-genome FASTA: the genome the reads were aligned to.");
+  if (have_names) {
+    for (size_t at = 0;;) {
+      const size_t comma = names_arg.find(',', at);
+      names.push_back(names_arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
+      if (comma == std::string::npos) break;
+      at = comma + 1;
+    }
+    char got[32], want[32];
+    snprintf(got, sizeof got, "%zu", names.size());
+    snprintf(want, sizeof want, "%zu", in_names.size());
+    if (names.size() != in_names.size()) die(" (pileup-ref-names): %s names for %s --pileup-bam files: the k-th name goes to the k-th file.", got, want);
+    for (const std::string &n : names)
+      if (n.empty()) die(" (pileup-ref-names): an empty name.");
+  }
+  std::vector<MappedFile> files(in_names.size());
+  for (size_t f = 0; f < files.size(); f++)
+    if (!files[f].open_file(in_names[f])) die(": Cannot open file: %s", in_names[f].c_str());
+  // the genome, through the input path of --errors-genome: each record's sequence lines, its name the id up to the first white space
+  pbsim::FastaMap fm;
+  {
+    pbsim::GenomeInfo gm;
+    bool fallback = false;
+    std::string err;
+    if (!pbsim::map_genome(genome_name.c_str(), &fm, &gm, false, &fallback, &err))
+      die(": --pileup-genome %s: %s", genome_name.c_str(),
+          fallback ? "not a FASTA file that can be mapped (a regular file that begins with '>' and holds no NUL byte)" : err.c_str());
+  }
+  std::vector<std::string> ref_names;
+  for (const pbsim::FastaRecord &r : fm.recs) ref_names.push_back(r.id.substr(0, r.id.find_first_of(" \t\r\n\v\f")));
+  std::vector<pbsim_errors_ref> refs;
+  for (size_t r = 0; r < fm.recs.size(); r++) refs.push_back(pbsim_errors_ref{ref_names[r].c_str(), fm.recs[r].lines, fm.recs[r].bytes});
+  pbsim_params p;
+  pbsim_params_default(&p);
+  p.strategy = PBSIM_STRATEGY_WGS;
+  p.method = PBSIM_METHOD_ERR;
+  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
+  if (!ctx) check(0);
+  struct Result {
+    FILE *fp = NULL;
+    bool write_failed = false;
+  } res;
+  if (!out_name.empty()) {
+    res.fp = fopen(out_name.c_str(), "wb");
+    if (!res.fp) die(": Cannot open output file: %s", out_name.c_str());
+  }
+  std::vector<pbsim_errors_file> in(files.size());
+  for (size_t f = 0; f < files.size(); f++) in[f] = pbsim_errors_file{files[f].map, (int64_t)files[f].n, have_names ? names[f].c_str() : NULL};
+  pbsim_pileup_opts opts = {0x900, (int32_t)min_mapq, (int32_t)min_baseq, (int32_t)format, (int64_t)min_depth, 0};
+  pbsim_pileup_sink sink = {&res,
+                            [](void *u, const char *z, int64_t k, int64_t) {
+                              Result *x = (Result *)u;
+                              if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
+                              return x->write_failed ? 0 : 1;
+                            },
+                            NULL};
+  if (!res.fp) sink.on_text = NULL;
+  pbsim_pileup_result result;
+  const bool ok = pbsim_bam_pileup(ctx, refs.data(), (int)refs.size(), in.data(), (int)in.size(), &opts, &sink, &result) != 0;
+  if (res.fp && fclose(res.fp) != 0) res.write_failed = true;
+  if (!ok || res.write_failed) {
+    fprintf(stderr, "ERROR: %s\n", res.write_failed ? ("write error on " + out_name).c_str() : pbsim_last_error());
+    if (in_names.size() > 1)
+      for (size_t f = 0; f < in_names.size(); f++) fprintf(stderr, "ERROR: file %zu is %s\n", f, in_names[f].c_str());
+    if (!out_name.empty()) unlink(out_name.c_str());
+    quit(-1);
+  }
+  std::string text((size_t)pbsim_pileup_report(&result, NULL, 0), '\0');
+  pbsim_pileup_report(&result, &text[0], (int64_t)text.size());
+  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
+  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
+  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
+  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int device) {
@@ -1378,6 +1496,8 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
     if (!strcmp(argv[i], "--stats-bam")) return stats_bam_main(argc, argv, comm, device);
   for (int i = 1; i < argc; i++)
     if (!strcmp(argv[i], "--errors-bam")) return errors_bam_main(argc, argv, comm, device);
+  for (int i = 1; i < argc; i++)
+    if (!strcmp(argv[i], "--pileup-bam")) return pileup_bam_main(argc, argv, comm, device);
   if (argc >= 2 && !strcmp(argv[1], "--sort-truth-bam")) {
     // the standalone mode: no simulation, the named files sorted and indexed in place on one GPU
     if (comm && comm->world > 1) die(": --sort-truth-bam runs on one GPU.");
