@@ -690,6 +690,62 @@ int pbsim_bam_pileup(pbsim_ctx *ctx, const pbsim_errors_ref *refs, int n_refs, c
  * ins_unanchored and max_depth; "HP\t<v>\t<called>\t<sub>\t<del>\t<ins>" per class with a value that is not 0.  Returns the text's
  * length, and writes it (no NUL) where buf holds cap >= that many bytes; -1: bad argument. */
 int64_t pbsim_pileup_report(const pbsim_pileup_result *result, char *buf, int64_t cap);
+/* The consensus FASTA of the aligned reads of one or more BAM files against the genome they were aligned to, on the GPU: the
+ * sequence the pile of reads spells, as `samtools consensus` or a polisher would hand it back.
+ * Front half.  The genome, the files, the references by name, the record classes, the CIGAR resolution, the cells and the sites
+ * are exactly pbsim_bam_pileup's, with the same options exclude_flags, min_mapq, min_baseq and min_depth: counts[9], sites[9],
+ * ins_unanchored and max_depth equal pbsim_bam_pileup's on the same input.
+ * Insertion cells.  An I op of length L >= 1 of a scored record that is anchored at position a (the pileup's rule: a = q - 1 with
+ * q > pos) adds, for every offset j with 0 <= j < min(L, max_ins), 1 to cell b of (a, j), b the read class of the inserted
+ * base's 4-bit code: 1 2 4 8 -> 0 .. 3, every other code (0 included) -> 4.  Inserted bases' qualities mask nothing.  The cells
+ * are unsigned 32-bit numbers, additions modulo 2^32; n(a, j) is the sum of the five cells, so n(a, 0) is the pileup's ins cell
+ * of a.  Unanchored insertions add nowhere.
+ * The consensus of a position p of a genome record.  A ref_n or low site emits one byte: with fill 0 `N`, with fill 1 the
+ * prepared genome byte.  A called site emits its call (A C G T); a site that calls del emits nothing.  A called site that is an
+ * ins_site (2 ins > depth) then emits the insertion: for j = 0, 1, .. while j < max_ins and 2 n(p, j) > depth(p) the largest
+ * of the A C G T cells of (p, j), among equals the first, and `N` where all four are 0.  n(p, j) does not increase with j, so
+ * the insertion is a prefix and its first base is there exactly when the site is an ins_site.
+ * The FASTA.  Genome records in their order, each `>name\n`, then its consensus bases in lines of line_width bases (0: one
+ * line) with `\n` after every line, the last partial one included; a record of no consensus bases is its header line alone.
+ * bases[]: out (all bases written), kept (concordant sites), sub, ins (inserted bases emitted), fill, del (called sites that
+ * emit nothing): out = kept + sub + ins + fill and sites = kept + sub + del + fill.  ins_sites; ins_longest, the longest
+ * insertion emitted; ins_capped, the ins_sites whose insertion has exactly max_ins bases; ins_len[v], the ins_sites by
+ * min(length, 63); text_bytes, the size of the FASTA (also where no text is asked for).
+ * Sink.  on_text: the FASTA in offset order in pieces of at most piece_bytes; on_record(user, ref, l_ref, l_cons): per genome
+ * record in order, after the text, its length and that of its consensus.  Either may be NULL; with no on_text no text is made,
+ * but the result is complete.
+ * tests/consensus_model.py states the rule in plain Python.  fill outside 0 and 1, max_ins outside 1 .. 65535, line_width
+ * outside 0 .. 2^20 and everything pbsim_bam_pileup refuses fail before any device work.  Beside what the pileup holds in HBM
+ * the stage keeps 8 bytes per inserted base of an anchored I op (below max_ins) until the sites are called, then 20 bytes per
+ * base of the longest insertion seen at each ins_site.  After any failure the context stays usable and the result is zeroed. */
+typedef struct pbsim_consensus_opts { /* NULL: {0x900, 0, 0, 0, 1, 1024, 60, 0} */
+  int32_t exclude_flags, min_mapq, min_baseq;
+  int32_t fill;        /* 0: N at a ref_n or low site, 1: the prepared genome byte */
+  int64_t min_depth;
+  int32_t max_ins;     /* 1 .. 65535: the most bases one insertion emits */
+  int32_t line_width;  /* 0 .. 2^20, 0: one line per record */
+  int64_t piece_bytes; /* 0: the default; else the most text one on_text call carries */
+} pbsim_consensus_opts;
+typedef struct pbsim_consensus_sink {
+  void *user;
+  int (*on_text)(void *user, const char *bytes, int64_t n, int64_t offset); /* in offset order; may be NULL */
+  int (*on_record)(void *user, int32_t ref, int64_t l_ref, int64_t l_cons);  /* per genome record, after the text; may be NULL */
+} pbsim_consensus_sink;
+typedef struct pbsim_consensus_result {
+  int64_t counts[9];
+  int64_t sites[9];
+  int64_t ins_unanchored, max_depth;
+  int64_t bases[6];
+  int64_t ins_sites, ins_longest, ins_capped;
+  int64_t ins_len[64];
+  int64_t text_bytes;
+} pbsim_consensus_result;
+int pbsim_bam_consensus(pbsim_ctx *ctx, const pbsim_errors_ref *refs, int n_refs, const pbsim_errors_file *files, int n_files,
+                        const pbsim_consensus_opts *opts, const pbsim_consensus_sink *sink, pbsim_consensus_result *result);
+/* The report text, no device needed: the "#" line of the counts and the "S" line as pbsim_pileup_report writes them; "K" and the
+ * six values of bases, then ins_sites, ins_longest and ins_capped; "IL\t<bin>\t<sites>" for the bins of ins_len that are not
+ * empty.  Returns the text's length, and writes it (no NUL) where buf holds cap >= that many bytes; -1: bad argument. */
+int64_t pbsim_consensus_report(const pbsim_consensus_result *result, char *buf, int64_t cap);
 
 /* ---- batch primitives (used by the drivers above, bench.py, multi-GPU) ------
  * pbsim_batch_walk     header draw + bucketing + HMM walk of reads

@@ -252,6 +252,29 @@ class PileupResult(C.Structure):
     _fields_ = [("counts", C.c_int64 * 9), ("sites", C.c_int64 * 9), ("cell_sums", C.c_int64 * 8), ("ins_unanchored", C.c_int64),
                 ("max_depth", C.c_int64)] + [(name, C.c_int64 * 12) for name in PILEUP_HP]
 
+
+class ConsensusOpts(C.Structure):
+    _fields_ = [("exclude_flags", C.c_int32), ("min_mapq", C.c_int32), ("min_baseq", C.c_int32), ("fill", C.c_int32), ("min_depth", C.c_int64),
+                ("max_ins", C.c_int32), ("line_width", C.c_int32), ("piece_bytes", C.c_int64)]
+
+
+CONSENSUS_TEXT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64)
+CONSENSUS_RECORD_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_int64)
+
+
+class ConsensusSink(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("on_text", CONSENSUS_TEXT_CB), ("on_record", CONSENSUS_RECORD_CB)]
+
+
+CONSENSUS_BASES = ["out", "kept", "sub", "ins", "fill", "del"]
+CONSENSUS_FILL = {"n": 0, "ref": 1}
+
+
+class ConsensusResult(C.Structure):
+    _fields_ = [("counts", C.c_int64 * 9), ("sites", C.c_int64 * 9), ("ins_unanchored", C.c_int64), ("max_depth", C.c_int64),
+                ("bases", C.c_int64 * 6), ("ins_sites", C.c_int64), ("ins_longest", C.c_int64), ("ins_capped", C.c_int64),
+                ("ins_len", C.c_int64 * 64), ("text_bytes", C.c_int64)]
+
 # every symbol include/pbsim3_amd.h declares: (name, restype, argtypes)
 API = [
     ("pbsim_job_add_record", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
@@ -350,6 +373,9 @@ API = [
     ("pbsim_bam_pileup", C.c_int, [C.c_void_p, C.POINTER(ErrorsRef), C.c_int, C.POINTER(ErrorsFile), C.c_int, C.POINTER(PileupOpts),
                                    C.POINTER(PileupSink), C.POINTER(PileupResult)]),
     ("pbsim_pileup_report", C.c_int64, [C.POINTER(PileupResult), C.c_char_p, C.c_int64]),
+    ("pbsim_bam_consensus", C.c_int, [C.c_void_p, C.POINTER(ErrorsRef), C.c_int, C.POINTER(ErrorsFile), C.c_int, C.POINTER(ConsensusOpts),
+                                      C.POINTER(ConsensusSink), C.POINTER(ConsensusResult)]),
+    ("pbsim_consensus_report", C.c_int64, [C.POINTER(ConsensusResult), C.c_char_p, C.c_int64]),
     ("pbsim_batch_walk", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_slot_count", C.c_int, []),
     ("pbsim_select_slot", C.c_int, [C.c_void_p, C.c_int]),
@@ -530,6 +556,40 @@ def pileup_report(result) -> bytes:
         raise PbsimError("pbsim_pileup_report: bad argument")
     buf = C.create_string_buffer(max(n, 1))
     load().pbsim_pileup_report(C.byref(res), buf, n)
+    return buf.raw[:n]
+
+
+CONSENSUS_SCALARS = ["ins_unanchored", "max_depth", "ins_sites", "ins_longest", "ins_capped", "text_bytes"]
+
+
+def _consensus_dict(res) -> dict:
+    """a ConsensusResult as a dict: counts, sites and bases as dicts by name, ins_len as a list, the rest as numbers"""
+    out = dict(counts=dict(zip(PILEUP_COUNTS, (int(v) for v in res.counts))), sites=dict(zip(PILEUP_SITES, (int(v) for v in res.sites))),
+               bases=dict(zip(CONSENSUS_BASES, (int(v) for v in res.bases))), ins_len=[int(v) for v in res.ins_len])
+    for name in CONSENSUS_SCALARS:
+        out[name] = int(getattr(res, name))
+    return out
+
+
+def consensus_report(result) -> bytes:
+    """The report text of Context.bam_consensus's result (the dict; counts, sites and bases as dicts by name or as the values in
+    order): pbsim_consensus_report, no device needed."""
+    def vals(x, names):
+        return [int(x[k]) for k in names] if isinstance(x, dict) else [int(v) for v in x]
+    parts = [("counts", vals(result["counts"], PILEUP_COUNTS)), ("sites", vals(result["sites"], PILEUP_SITES)),
+             ("bases", vals(result["bases"], CONSENSUS_BASES)), ("ins_len", [int(v) for v in result["ins_len"]])]
+    res = ConsensusResult()
+    for name, v in parts:
+        if len(v) != len(getattr(res, name)):
+            raise ValueError("consensus_report: %s has %d values, not %d" % (name, len(v), len(getattr(res, name))))
+        setattr(res, name, type(getattr(res, name))(*v))
+    for name in CONSENSUS_SCALARS:
+        setattr(res, name, int(result.get(name, 0)))
+    n = load().pbsim_consensus_report(C.byref(res), None, 0)
+    if n < 0:
+        raise PbsimError("pbsim_consensus_report: bad argument")
+    buf = C.create_string_buffer(max(n, 1))
+    load().pbsim_consensus_report(C.byref(res), buf, n)
     return buf.raw[:n]
 
 
@@ -1206,6 +1266,47 @@ class Context:
         if text:
             got += (b"".join(parts),)
         return got + (cells,) if arrays else got
+
+    def bam_consensus(self, files, genome, ref_names=None, text=True, min_mapq=0, exclude_flags=0x900, min_baseq=0, min_depth=1, fill="n",
+                      max_ins=1024, line_width=60, piece_bytes=0):
+        """The consensus FASTA of the aligned reads of BAM files against their genome (pbsim_bam_consensus; the rule:
+        include/pbsim3_amd.h).  files, genome and ref_names as bam_pileup takes them; fill: "n" (N at a site that is not called) or
+        "ref" (the genome's base there).  Returns (result, report): a dict -- counts, sites and bases as dicts by name, ins_len as a
+        list, ins_unanchored, max_depth, ins_sites, ins_longest, ins_capped, text_bytes -- and the report text; with `text` two
+        further items, the FASTA and a list of (l_ref, l_cons) per genome record."""
+        if fill not in CONSENSUS_FILL:
+            raise ValueError("fill must be n or ref")
+        if isinstance(files, (bytes, bytearray, memoryview)):
+            files = [files]
+        files = [bytes(f) for f in files]
+        names = list(ref_names) if ref_names is not None else [None] * len(files)
+        if len(names) != len(files):
+            raise ValueError("ref_names: one entry per file (%d given for %d files)" % (len(names), len(files)))
+        names = [None if nm is None else (nm.encode() if isinstance(nm, str) else bytes(nm)) for nm in names]
+        genome = [((nm.encode() if isinstance(nm, str) else bytes(nm)), bytes(lines)) for nm, lines in genome]
+        refs = (ErrorsRef * max(len(genome), 1))(*[ErrorsRef(nm, C.cast(C.c_char_p(lines), C.c_void_p), len(lines)) for nm, lines in genome])
+        arr = (ErrorsFile * max(len(files), 1))(*[ErrorsFile(C.cast(C.c_char_p(f), C.c_void_p), len(f), nm) for f, nm in zip(files, names)])
+        parts, at, lengths = [], [0], []
+
+        def on_text(user, ptr, n, offset):
+            if offset != at[0]:      # (the pieces come in offset order)
+                return 0
+            parts.append(C.string_at(ptr, n))
+            at[0] += n
+            return 1
+
+        def on_record(user, ref, l_ref, l_cons):
+            lengths.append((int(l_ref), int(l_cons)))
+            return 1
+        sink = ConsensusSink(None, CONSENSUS_TEXT_CB(on_text) if text else CONSENSUS_TEXT_CB(),
+                             CONSENSUS_RECORD_CB(on_record) if text else CONSENSUS_RECORD_CB())
+        opts = ConsensusOpts(int(exclude_flags), int(min_mapq), int(min_baseq), CONSENSUS_FILL[fill], int(min_depth), int(max_ins), int(line_width),
+                             int(piece_bytes))
+        res = ConsensusResult()
+        _check(self.lib.pbsim_bam_consensus(self.h, refs, len(genome), arr, len(files), C.byref(opts), C.byref(sink), C.byref(res)))
+        out = _consensus_dict(res)
+        got = (out, consensus_report(out))
+        return got + (b"".join(parts), lengths) if text else got
 
     def set_transcripts(self, ids, plus, minus, seqs):
         """ids: list[str]; plus/minus: expression counts; seqs: list[bytes]."""

@@ -358,3 +358,79 @@ def pileup_bam(argv):
         if "" in got["ref_names"]:
             raise ValueError("(pileup-ref-names): an empty name.")
     return got
+
+
+def consensus_bam(argv):
+    """`pbsim --consensus-bam FILE [--consensus-bam FILE ...] --consensus-genome FASTA --consensus-out FILE [--consensus-ref-names a,b,..]
+    [--consensus-min-mapq N] [--consensus-min-baseq N] [--consensus-min-depth N] [--consensus-exclude-flags F] [--consensus-fill n|ref]
+    [--consensus-max-ins N] [--consensus-line-width N]` -> dict(bams, genome, ref_names, out, min_mapq, min_baseq, min_depth,
+    exclude_flags, fill, max_ins, line_width): the stand-alone mode that writes the consensus FASTA of the aligned reads
+    (pbsim_bam_consensus).  What pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
+    takes = ("--consensus-bam", "--consensus-genome", "--consensus-ref-names", "--consensus-out", "--consensus-min-mapq", "--consensus-min-baseq",
+             "--consensus-min-depth", "--consensus-exclude-flags", "--consensus-fill", "--consensus-max-ins", "--consensus-line-width", "--device")
+    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
+    got = dict(bams=[], genome=None, ref_names=None, out=None, min_mapq=0, min_baseq=0, min_depth=1, exclude_flags=0x900, fill="n", max_ins=1024,
+               line_width=60)
+    if any(a.split("=")[0] in ranks for a in argv):
+        raise ValueError("--consensus-bam runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a not in takes:
+            raise ValueError("(%s): --consensus-bam takes --consensus-genome, --consensus-out, --consensus-ref-names, --consensus-min-mapq, "
+                             "--consensus-min-baseq, --consensus-min-depth, --consensus-exclude-flags, --consensus-fill, --consensus-max-ins, "
+                             "--consensus-line-width and --device, and no other option." % a)
+        if i + 1 >= len(argv):
+            raise ValueError("(%s): the option needs a value." % a)
+        v = argv[i + 1]
+        i += 2
+        if a == "--consensus-bam":
+            got["bams"].append(v)
+        elif a == "--consensus-genome":
+            got["genome"] = v
+        elif a == "--consensus-ref-names":
+            got["ref_names"] = v.split(",")
+        elif a == "--consensus-out":
+            got["out"] = v
+        elif a == "--consensus-fill":
+            if v not in ("n", "ref"):
+                raise ValueError("(consensus-fill: %s): n or ref." % v)
+            got["fill"] = v
+        elif a == "--consensus-exclude-flags":
+            n = _whole(v, 16 if v[:2] in ("0x", "0X") else 10)
+            if n is None or n > 65535:
+                raise ValueError("(consensus-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535." % v)
+            got["exclude_flags"] = n
+        elif a in ("--consensus-min-mapq", "--consensus-min-baseq"):
+            n = _whole(v)
+            if n is None or n > 255:
+                raise ValueError("(%s: %s): a whole number, 0 .. 255." % (a[2:], v))
+            got[a[12:].replace("-", "_")] = n
+        elif a == "--consensus-min-depth":
+            n = _whole(v)
+            if n is None or n > 1000000000000:
+                raise ValueError("(consensus-min-depth: %s): a whole number, 0 .. 1000000000000." % v)
+            got["min_depth"] = n
+        elif a == "--consensus-max-ins":
+            n = _whole(v)
+            if n is None or not 1 <= n <= 65535:
+                raise ValueError("(consensus-max-ins: %s): a whole number, 1 .. 65535." % v)
+            got["max_ins"] = n
+        elif a == "--consensus-line-width":
+            n = _whole(v)
+            if n is None or n > 1048576:
+                raise ValueError("(consensus-line-width: %s): a whole number, 0 .. 1048576 (0: one line per record)." % v)
+            got["line_width"] = n
+    if not got["bams"]:
+        raise ValueError("--consensus-bam FILE: name the BAM file.")
+    if not got["genome"]:
+        raise ValueError("--consensus-bam needs --consensus-genome FASTA: the genome the reads were aligned to.")
+    if not got["out"]:
+        raise ValueError("--consensus-bam needs --consensus-out FILE: where the consensus FASTA goes.")
+    if got["ref_names"] is not None:
+        if len(got["ref_names"]) != len(got["bams"]):
+            raise ValueError("(consensus-ref-names): %d names for %d --consensus-bam files: the k-th name goes to the k-th file."
+                             % (len(got["ref_names"]), len(got["bams"])))
+        if "" in got["ref_names"]:
+            raise ValueError("(consensus-ref-names): an empty name.")
+    return got
