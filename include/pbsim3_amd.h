@@ -746,6 +746,62 @@ int pbsim_bam_consensus(pbsim_ctx *ctx, const pbsim_errors_ref *refs, int n_refs
  * six values of bases, then ins_sites, ins_longest and ins_capped; "IL\t<bin>\t<sites>" for the bins of ins_len that are not
  * empty.  Returns the text's length, and writes it (no NUL) where buf holds cap >= that many bytes; -1: bad argument. */
 int64_t pbsim_consensus_report(const pbsim_consensus_result *result, char *buf, int64_t cap);
+/* The differences between the genome and what the pile of aligned reads of one or more BAM files spells, as VCFv4.2, on the GPU:
+ * the haploid variants the reads support, each as one event.
+ * Front half.  Everything up to the insertion every ins_site emits is pbsim_bam_consensus's, with the same options exclude_flags,
+ * min_mapq, min_baseq, min_depth and max_ins: counts[9], sites[9], ins_unanchored and max_depth equal that stage's.
+ * What a position p spells, E(p).  A ref_n or low site spells the prepared genome byte (the consensus with fill 1); a called
+ * site spells its call, or nothing where it calls del; an ins_site -- a del_site that is one included -- then spells its insertion
+ * as the consensus emits it.
+ * Groups.  Within one genome record every position that is not a del_site is an anchor.  An anchor's group is the anchor and the
+ * run of del_sites directly behind it, up to the next anchor or the record's end; the record's first anchor also takes the
+ * del_sites in front of it (VCF's rule for an event at position 1: the base behind it is included).  No group crosses into
+ * another genome record.  A genome record that has positions and no anchor writes nothing: it counts in unplaced_records and its
+ * positions in unplaced_sites.
+ * Records.  For a group over positions lo .. hi REF is the prepared genome bytes of lo .. hi and ALT is E(lo) .. E(hi) joined; a
+ * record is written exactly when ALT differs from REF as byte strings (a deleted base that the insertion at its own site puts
+ * back gives none).  The records are ascending and do not overlap; applied to the prepared genome they give the consensus with
+ * fill 1.  The line: name, POS = lo + 1, `.`, REF, ALT, `.`, `.`, `DP=d;MS=m;TYPE=t`, tab-separated.  DP is the depth at the
+ * group's anchor.  MS, the minimum support, is the smallest over the group of: the call's cell at a sub_site, the del cell at
+ * every del_site, n(p, j) for every inserted base emitted.  TYPE: snv where both strings have one byte; ins where REF has one
+ * byte and ALT begins with it; del where ALT has one byte and REF begins with it; else complex.  QUAL and FILTER are `.`: the
+ * stage has no probability model.  No sample columns, no left-normalisation.
+ * The header, written by the host in front of the records: fileformat, source, one contig line per genome record in order (empty
+ * ones included), three INFO lines (DP, MS, TYPE), the column line.  It counts in text_bytes.
+ * types[]: snv, ins, del, complex; ref_bases, alt_bases: the bytes of all REF and all ALT strings; longest_ref, longest_alt;
+ * header_bytes; text_bytes, header and records (also where no text is asked for).
+ * Sink.  on_text: the VCF in offset order in pieces of at most piece_bytes; on_record(user, ref, l_ref, n_variants): per genome
+ * record in order, after the text.  Either may be NULL; with no on_text no text is made, but the result is complete.
+ * tests/call_model.py states the rule in plain Python.  max_ins outside 1 .. 65535 and everything pbsim_bam_pileup refuses fail
+ * before any device work.  The stage holds what pbsim_bam_consensus holds, and the text.  One lane walks a whole group: a
+ * deletion run of n positions costs n steps of one lane.  After any failure the context stays usable and the result is zeroed. */
+typedef struct pbsim_call_opts { /* NULL: {0x900, 0, 0, 1024, 1, 0} */
+  int32_t exclude_flags, min_mapq, min_baseq;
+  int32_t max_ins;     /* 1 .. 65535: the most bases one insertion emits */
+  int64_t min_depth;
+  int64_t piece_bytes; /* 0: the default; else the most text one on_text call carries */
+} pbsim_call_opts;
+typedef struct pbsim_call_sink {
+  void *user;
+  int (*on_text)(void *user, const char *bytes, int64_t n, int64_t offset);    /* in offset order; may be NULL */
+  int (*on_record)(void *user, int32_t ref, int64_t l_ref, int64_t n_variants); /* per genome record, after the text; may be NULL */
+} pbsim_call_sink;
+typedef struct pbsim_call_result {
+  int64_t counts[9];
+  int64_t sites[9];
+  int64_t ins_unanchored, max_depth;
+  int64_t variants;
+  int64_t types[4];
+  int64_t ref_bases, alt_bases, longest_ref, longest_alt;
+  int64_t unplaced_records, unplaced_sites;
+  int64_t header_bytes, text_bytes;
+} pbsim_call_result;
+int pbsim_bam_call(pbsim_ctx *ctx, const pbsim_errors_ref *refs, int n_refs, const pbsim_errors_file *files, int n_files,
+                   const pbsim_call_opts *opts, const pbsim_call_sink *sink, pbsim_call_result *result);
+/* The report text, no device needed: the "#" line of the counts and the "S" line as pbsim_pileup_report writes them; "V" and
+ * variants, the four types, ref_bases, alt_bases, longest_ref, longest_alt, unplaced_records and unplaced_sites.  Returns the
+ * text's length, and writes it (no NUL) where buf holds cap >= that many bytes; -1: bad argument. */
+int64_t pbsim_call_report(const pbsim_call_result *result, char *buf, int64_t cap);
 
 /* ---- batch primitives (used by the drivers above, bench.py, multi-GPU) ------
  * pbsim_batch_walk     header draw + bucketing + HMM walk of reads

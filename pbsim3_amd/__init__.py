@@ -275,6 +275,29 @@ class ConsensusResult(C.Structure):
                 ("bases", C.c_int64 * 6), ("ins_sites", C.c_int64), ("ins_longest", C.c_int64), ("ins_capped", C.c_int64),
                 ("ins_len", C.c_int64 * 64), ("text_bytes", C.c_int64)]
 
+
+class CallOpts(C.Structure):
+    _fields_ = [("exclude_flags", C.c_int32), ("min_mapq", C.c_int32), ("min_baseq", C.c_int32), ("max_ins", C.c_int32), ("min_depth", C.c_int64),
+                ("piece_bytes", C.c_int64)]
+
+
+CALL_TEXT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64)
+CALL_RECORD_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_int64)
+
+
+class CallSink(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("on_text", CALL_TEXT_CB), ("on_record", CALL_RECORD_CB)]
+
+
+CALL_TYPES = ["snv", "ins", "del", "complex"]
+
+
+class CallResult(C.Structure):
+    _fields_ = [("counts", C.c_int64 * 9), ("sites", C.c_int64 * 9), ("ins_unanchored", C.c_int64), ("max_depth", C.c_int64),
+                ("variants", C.c_int64), ("types", C.c_int64 * 4), ("ref_bases", C.c_int64), ("alt_bases", C.c_int64), ("longest_ref", C.c_int64),
+                ("longest_alt", C.c_int64), ("unplaced_records", C.c_int64), ("unplaced_sites", C.c_int64), ("header_bytes", C.c_int64),
+                ("text_bytes", C.c_int64)]
+
 # every symbol include/pbsim3_amd.h declares: (name, restype, argtypes)
 API = [
     ("pbsim_job_add_record", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
@@ -376,6 +399,9 @@ API = [
     ("pbsim_bam_consensus", C.c_int, [C.c_void_p, C.POINTER(ErrorsRef), C.c_int, C.POINTER(ErrorsFile), C.c_int, C.POINTER(ConsensusOpts),
                                       C.POINTER(ConsensusSink), C.POINTER(ConsensusResult)]),
     ("pbsim_consensus_report", C.c_int64, [C.POINTER(ConsensusResult), C.c_char_p, C.c_int64]),
+    ("pbsim_bam_call", C.c_int, [C.c_void_p, C.POINTER(ErrorsRef), C.c_int, C.POINTER(ErrorsFile), C.c_int, C.POINTER(CallOpts), C.POINTER(CallSink),
+                                 C.POINTER(CallResult)]),
+    ("pbsim_call_report", C.c_int64, [C.POINTER(CallResult), C.c_char_p, C.c_int64]),
     ("pbsim_batch_walk", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_slot_count", C.c_int, []),
     ("pbsim_select_slot", C.c_int, [C.c_void_p, C.c_int]),
@@ -590,6 +616,40 @@ def consensus_report(result) -> bytes:
         raise PbsimError("pbsim_consensus_report: bad argument")
     buf = C.create_string_buffer(max(n, 1))
     load().pbsim_consensus_report(C.byref(res), buf, n)
+    return buf.raw[:n]
+
+
+CALL_SCALARS = ["ins_unanchored", "max_depth", "variants", "ref_bases", "alt_bases", "longest_ref", "longest_alt", "unplaced_records", "unplaced_sites",
+                "header_bytes", "text_bytes"]
+
+
+def _call_dict(res) -> dict:
+    """a CallResult as a dict: counts, sites and types as dicts by name, the rest as numbers"""
+    out = dict(counts=dict(zip(PILEUP_COUNTS, (int(v) for v in res.counts))), sites=dict(zip(PILEUP_SITES, (int(v) for v in res.sites))),
+               types=dict(zip(CALL_TYPES, (int(v) for v in res.types))))
+    for name in CALL_SCALARS:
+        out[name] = int(getattr(res, name))
+    return out
+
+
+def call_report(result) -> bytes:
+    """The report text of Context.bam_call's result (the dict; counts, sites and types as dicts by name or as the values in order):
+    pbsim_call_report, no device needed."""
+    def vals(x, names):
+        return [int(x[k]) for k in names] if isinstance(x, dict) else [int(v) for v in x]
+    parts = [("counts", vals(result["counts"], PILEUP_COUNTS)), ("sites", vals(result["sites"], PILEUP_SITES)), ("types", vals(result["types"], CALL_TYPES))]
+    res = CallResult()
+    for name, v in parts:
+        if len(v) != len(getattr(res, name)):
+            raise ValueError("call_report: %s has %d values, not %d" % (name, len(v), len(getattr(res, name))))
+        setattr(res, name, type(getattr(res, name))(*v))
+    for name in CALL_SCALARS:
+        setattr(res, name, int(result.get(name, 0)))
+    n = load().pbsim_call_report(C.byref(res), None, 0)
+    if n < 0:
+        raise PbsimError("pbsim_call_report: bad argument")
+    buf = C.create_string_buffer(max(n, 1))
+    load().pbsim_call_report(C.byref(res), buf, n)
     return buf.raw[:n]
 
 
@@ -1307,6 +1367,42 @@ class Context:
         out = _consensus_dict(res)
         got = (out, consensus_report(out))
         return got + (b"".join(parts), lengths) if text else got
+
+    def bam_call(self, files, genome, ref_names=None, text=True, min_mapq=0, exclude_flags=0x900, min_baseq=0, min_depth=1, max_ins=1024, piece_bytes=0):
+        """The differences between the genome and what the pile of aligned reads of BAM files spells, as VCF (pbsim_bam_call; the
+        rule: include/pbsim3_amd.h).  files, genome and ref_names as bam_consensus takes them.  Returns (result, report): a dict --
+        counts, sites and types as dicts by name, ins_unanchored, max_depth, variants, ref_bases, alt_bases, longest_ref, longest_alt,
+        unplaced_records, unplaced_sites, header_bytes, text_bytes -- and the report text; with `text` two further items, the VCF and
+        a list of (l_ref, n_variants) per genome record."""
+        if isinstance(files, (bytes, bytearray, memoryview)):
+            files = [files]
+        files = [bytes(f) for f in files]
+        names = list(ref_names) if ref_names is not None else [None] * len(files)
+        if len(names) != len(files):
+            raise ValueError("ref_names: one entry per file (%d given for %d files)" % (len(names), len(files)))
+        names = [None if nm is None else (nm.encode() if isinstance(nm, str) else bytes(nm)) for nm in names]
+        genome = [((nm.encode() if isinstance(nm, str) else bytes(nm)), bytes(lines)) for nm, lines in genome]
+        refs = (ErrorsRef * max(len(genome), 1))(*[ErrorsRef(nm, C.cast(C.c_char_p(lines), C.c_void_p), len(lines)) for nm, lines in genome])
+        arr = (ErrorsFile * max(len(files), 1))(*[ErrorsFile(C.cast(C.c_char_p(f), C.c_void_p), len(f), nm) for f, nm in zip(files, names)])
+        parts, at, records = [], [0], []
+
+        def on_text(user, ptr, n, offset):
+            if offset != at[0]:      # (the pieces come in offset order)
+                return 0
+            parts.append(C.string_at(ptr, n))
+            at[0] += n
+            return 1
+
+        def on_record(user, ref, l_ref, n_variants):
+            records.append((int(l_ref), int(n_variants)))
+            return 1
+        sink = CallSink(None, CALL_TEXT_CB(on_text) if text else CALL_TEXT_CB(), CALL_RECORD_CB(on_record) if text else CALL_RECORD_CB())
+        opts = CallOpts(int(exclude_flags), int(min_mapq), int(min_baseq), int(max_ins), int(min_depth), int(piece_bytes))
+        res = CallResult()
+        _check(self.lib.pbsim_bam_call(self.h, refs, len(genome), arr, len(files), C.byref(opts), C.byref(sink), C.byref(res)))
+        out = _call_dict(res)
+        got = (out, call_report(out))
+        return got + (b"".join(parts), records) if text else got
 
     def set_transcripts(self, ids, plus, minus, seqs):
         """ids: list[str]; plus/minus: expression counts; seqs: list[bytes]."""

@@ -434,3 +434,67 @@ def consensus_bam(argv):
         if "" in got["ref_names"]:
             raise ValueError("(consensus-ref-names): an empty name.")
     return got
+
+
+def call_bam(argv):
+    """`pbsim --call-bam FILE [--call-bam FILE ...] --call-genome FASTA --call-out FILE [--call-ref-names a,b,..] [--call-min-mapq N]
+    [--call-min-baseq N] [--call-min-depth N] [--call-exclude-flags F] [--call-max-ins N]` -> dict(bams, genome, ref_names, out,
+    min_mapq, min_baseq, min_depth, exclude_flags, max_ins): the stand-alone mode that writes the variants the aligned reads support
+    as VCF (pbsim_bam_call).  What pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
+    takes = ("--call-bam", "--call-genome", "--call-ref-names", "--call-out", "--call-min-mapq", "--call-min-baseq", "--call-min-depth",
+             "--call-exclude-flags", "--call-max-ins", "--device")
+    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
+    got = dict(bams=[], genome=None, ref_names=None, out=None, min_mapq=0, min_baseq=0, min_depth=1, exclude_flags=0x900, max_ins=1024)
+    if any(a.split("=")[0] in ranks for a in argv):
+        raise ValueError("--call-bam runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a not in takes:
+            raise ValueError("(%s): --call-bam takes --call-genome, --call-out, --call-ref-names, --call-min-mapq, --call-min-baseq, --call-min-depth, "
+                             "--call-exclude-flags, --call-max-ins and --device, and no other option." % a)
+        if i + 1 >= len(argv):
+            raise ValueError("(%s): the option needs a value." % a)
+        v = argv[i + 1]
+        i += 2
+        if a == "--call-bam":
+            got["bams"].append(v)
+        elif a == "--call-genome":
+            got["genome"] = v
+        elif a == "--call-ref-names":
+            got["ref_names"] = v.split(",")
+        elif a == "--call-out":
+            got["out"] = v
+        elif a == "--call-exclude-flags":
+            n = _whole(v, 16 if v[:2] in ("0x", "0X") else 10)
+            if n is None or n > 65535:
+                raise ValueError("(call-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535." % v)
+            got["exclude_flags"] = n
+        elif a in ("--call-min-mapq", "--call-min-baseq"):
+            n = _whole(v)
+            if n is None or n > 255:
+                raise ValueError("(%s: %s): a whole number, 0 .. 255." % (a[2:], v))
+            got[a[7:].replace("-", "_")] = n
+        elif a == "--call-min-depth":
+            n = _whole(v)
+            if n is None or n > 1000000000000:
+                raise ValueError("(call-min-depth: %s): a whole number, 0 .. 1000000000000." % v)
+            got["min_depth"] = n
+        elif a == "--call-max-ins":
+            n = _whole(v)
+            if n is None or not 1 <= n <= 65535:
+                raise ValueError("(call-max-ins: %s): a whole number, 1 .. 65535." % v)
+            got["max_ins"] = n
+    if not got["bams"]:
+        raise ValueError("--call-bam FILE: name the BAM file.")
+    if not got["genome"]:
+        raise ValueError("--call-bam needs --call-genome FASTA: the genome the reads were aligned to.")
+    if not got["out"]:
+        raise ValueError("--call-bam needs --call-out FILE: where the VCF goes.")
+    if got["ref_names"] is not None:
+        if len(got["ref_names"]) != len(got["bams"]):
+            raise ValueError("(call-ref-names): %d names for %d --call-bam files: the k-th name goes to the k-th file."
+                             % (len(got["ref_names"]), len(got["bams"])))
+        if "" in got["ref_names"]:
+            raise ValueError("(call-ref-names): an empty name.")
+    return got

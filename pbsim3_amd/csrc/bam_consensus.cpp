@@ -3,7 +3,8 @@
 // into HBM, the table zeroed, then per file its front half (bam_pileup_front.h) and the column pass, which here also logs the
 // inserted bases of the anchored I ops; the logs outlive their files, the streams do not.  Then once the site pass; the ins_sites
 // compacted into slots, the logs tallied into the slots' cells; the base pass, the FASTA and its way to the sink.  The kernels are
-// bam_errors.hip's, bam_pileup.hip's and bam_consensus.hip's.
+// bam_errors.hip's, bam_pileup.hip's and bam_consensus.hip's.  Everything up to the base pass's first half is consensus_front
+// (bam_consensus_front.h), which pbsim_bam_call goes through as well.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "bam_consensus.h"
+#include "bam_consensus_front.h"
 #include "bam_genome.h"
 #include "bam_pileup_front.h"
 #include "kernels.h"
@@ -32,17 +34,20 @@ struct FileLog {
   int64_t cap = 0, n = 0;
 };
 
-int consensus_bam(pbsim_ctx *c, const pbsim_errors_ref *refs, int n_refs, const pbsim_errors_file *files, int n_files, const pbsim_consensus_opts &o,
-                  const pbsim_consensus_sink *sink, pbsim_consensus_result *result) {
+}  // namespace
+
+int consensus_front(pbsim_ctx *c, const BamStage &stage, BamPhases &ph, const pbsim_errors_ref *refs, int n_refs, const pbsim_errors_file *files,
+                    int n_files, int32_t exclude_flags, int32_t min_mapq, int32_t min_baseq, int64_t min_depth, int32_t max_ins, ConsFront *out) {
   hipStream_t st = c->stream;
-  BamPhases ph(st, "consensus");
-  const bool want_text = sink && sink->on_text;
-  Genome genome;
-  if (!load_genome(c, kStage, refs, n_refs, &genome)) return PBSIM_FAILED;
+  auto alloc = [&](DevBuf &b, int64_t n, const char *what) { return bam_stage_alloc(stage, b, n, what); };
+  ConsFront &fr = *out;
+  Genome &genome = fr.genome;
+  if (!load_genome(c, stage, refs, n_refs, &genome)) return PBSIM_FAILED;
   ph.mark("genome");
   const ErrGenome g = {genome.seq.as<uint8_t>(), genome.hp.as<uint8_t>()};
   const int64_t total = genome.total;
-  DevBuf d_table, d_cls, d_cells, d_pile, d_cons, d_counts;
+  DevBuf &d_table = fr.d_table, &d_cls = fr.d_cls, &d_cells = fr.d_cells, &d_pile = fr.d_pile, &d_cons = fr.d_cons;
+  DevBuf d_counts;
   if (!alloc(d_table, total * kPileWidth * 4, "the cells of every position") || !alloc(d_cls, total, "the sites' classes") ||
       !alloc(d_cells, kErrCells * 8, "the record counts") || !alloc(d_pile, kPileCells * 8, "the counts") ||
       !alloc(d_cons, kConsCells * 8, "the base counts") || !alloc(d_counts, (int64_t)n_files * 16, "the logs' counters"))
@@ -57,11 +62,11 @@ int consensus_bam(pbsim_ctx *c, const pbsim_errors_ref *refs, int n_refs, const 
   HIP_OK(hipMemsetAsync(d_cons.p, 0, kConsCells * 8, st));
   HIP_OK(hipMemsetAsync(d_counts.p, 0, (size_t)n_files * 16, st));
   ph.mark("zero");
-  int64_t n_all = 0, inflated = 0, segments = 0, logged = 0;
+  int64_t &n_all = fr.n_all, &inflated = fr.inflated, &segments = fr.segments, &logged = fr.logged;
   std::deque<FileLog> logs;
   for (int f = 0; f < n_files; f++) {
     PileFile pf;
-    if (!pileup_file_front(c, kStage, ph, refs, n_refs, genome, files, f, n_files, o.exclude_flags, o.min_mapq, cells, &pf)) return PBSIM_FAILED;
+    if (!pileup_file_front(c, stage, ph, refs, n_refs, genome, files, f, n_files, exclude_flags, min_mapq, cells, &pf)) return PBSIM_FAILED;
     inflated += pf.s.N, n_all += pf.n_rec, segments += pf.n_seg;
     if (pf.n_seg > 0) {
       // the log, sized from the CIGAR sums of the scored records: every inserted base can leave one entry
@@ -75,13 +80,13 @@ int consensus_bam(pbsim_ctx *c, const pbsim_errors_ref *refs, int n_refs, const 
       log.cap = (int64_t)most;
       if (!alloc(log.d, log.cap * 8, "the log of inserted bases")) return PBSIM_FAILED;
       const ConsLog to = {log.d.as<unsigned long long>(), counts + 2 * f + 1, log.cap};
-      launch_consensus_columns(pf.recs, pf.er, g, pf.d_seg.as<ErrSegment>(), pf.n_seg, (uint32_t)o.min_baseq, table, pile, to, (uint32_t)o.max_ins, st);
+      launch_consensus_columns(pf.recs, pf.er, g, pf.d_seg.as<ErrSegment>(), pf.n_seg, (uint32_t)min_baseq, table, pile, to, (uint32_t)max_ins, st);
       HIP_OK(hipGetLastError());
       ph.mark("columns");
       HIP_OK(hipMemcpyAsync(&asked, counts + 2 * f + 1, 8, hipMemcpyDeviceToHost, st));
       HIP_OK(hipStreamSynchronize(st));
       if ((int64_t)asked > log.cap)
-        return fail(std::string(kWho) + "the column pass met " + std::to_string(asked) + " inserted bases where the records' CIGARs sum to " +
+        return fail(stage.who + "the column pass met " + std::to_string(asked) + " inserted bases where the records' CIGARs sum to " +
                     std::to_string(log.cap));
       log.n = (int64_t)asked;
       logged += log.n;
@@ -89,14 +94,14 @@ int consensus_bam(pbsim_ctx *c, const pbsim_errors_ref *refs, int n_refs, const 
     HIP_OK(hipStreamSynchronize(st));  // the stream and the per-record arrays go with this frame
   }
   // ---- the sites, once
-  std::string names;
-  std::vector<int64_t> name_at;
+  std::string &names = fr.names;
+  std::vector<int64_t> &name_at = fr.name_at;
   for (int r = 0; r < n_refs; r++) {
     name_at.push_back((int64_t)names.size());
     names += refs[r].name;
   }
   name_at.push_back((int64_t)names.size());
-  DevBuf d_at, d_len, d_name_at, d_names;
+  DevBuf &d_at = fr.d_at, &d_len = fr.d_len, &d_name_at = fr.d_name_at, &d_names = fr.d_names;
   if (!alloc(d_at, n_refs * 8, "the genome records' places") || !alloc(d_len, n_refs * 8, "the genome records' lengths") ||
       !alloc(d_name_at, (n_refs + 1) * 8, "the genome records' names") || !alloc(d_names, (int64_t)names.size() + 1, "the genome records' names"))
     return PBSIM_FAILED;
@@ -104,24 +109,25 @@ int consensus_bam(pbsim_ctx *c, const pbsim_errors_ref *refs, int n_refs, const 
   HIP_OK(hipMemcpyAsync(d_len.p, genome.len.data(), (size_t)n_refs * 8, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemcpyAsync(d_name_at.p, name_at.data(), name_at.size() * 8, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemcpyAsync(d_names.p, names.data(), names.size(), hipMemcpyHostToDevice, st));
-  const PileGenome pg = {n_refs, total, d_at.as<int64_t>(), d_len.as<int64_t>(), d_name_at.as<int64_t>(), d_names.as<char>(), g.seq, g.hp};
+  const PileGenome pg = fr.pg = {n_refs, total, d_at.as<int64_t>(), d_len.as<int64_t>(), d_name_at.as<int64_t>(), d_names.as<char>(), g.seq, g.hp};
   const uint8_t *cls = d_cls.as<uint8_t>();
-  launch_pileup_sites(pg, table, o.min_depth, d_cls.as<uint8_t>(), pile, st);
+  launch_pileup_sites(pg, table, min_depth, d_cls.as<uint8_t>(), pile, st);
   HIP_OK(hipGetLastError());
   ph.mark("sites");
   // ---- the slots: the ins_sites in order, the longest insertion logged at each, the cells behind them
-  const int64_t tiles = (total + kConsTile - 1) / kConsTile;
-  DevBuf d_tile, d_scan_tmp, d_pos, d_slot_len, d_slot_off, d_slot_cell;
+  const int64_t tiles = fr.tiles = (total + kConsTile - 1) / kConsTile;
+  DevBuf &d_tile = fr.d_tile, &d_scan_tmp = fr.d_scan_tmp, &d_pos = fr.d_pos, &d_slot_len = fr.d_slot_len, &d_slot_off = fr.d_slot_off,
+         &d_slot_cell = fr.d_slot_cell;
   if (!alloc(d_tile, (tiles + 1) * 8, "the tiles") || !alloc(d_scan_tmp, (tiles / 1024 + 8) * 8, "the scan's scratch")) return PBSIM_FAILED;
   int64_t *tile = d_tile.as<int64_t>();
-  int64_t n_slots = 0, n_cells = 0;
+  int64_t n_slots = 0, &n_cells = fr.n_cells;
   launch_consensus_slot_sizes(pg, cls, tile, st);
   HIP_OK(hipGetLastError());
   launch_exclusive_scan_i64(tile, tile, tiles, d_scan_tmp.as<int64_t>(), tile + tiles, st);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(&n_slots, tile + tiles, 8, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
-  ConsSlots slots = {n_slots, nullptr, nullptr, nullptr, nullptr};
+  ConsSlots &slots = fr.slots = {n_slots, nullptr, nullptr, nullptr, nullptr};
   if (n_slots > 0) {
     DevBuf d_slot_tmp;
     if (!alloc(d_pos, n_slots * 8, "the ins_sites' places") || !alloc(d_slot_len, (n_slots + 1) * 8, "the insertions' lengths") ||
@@ -153,13 +159,34 @@ int consensus_bam(pbsim_ctx *c, const pbsim_errors_ref *refs, int n_refs, const 
   HIP_OK(hipStreamSynchronize(st));
   logs.clear();
   // ---- the bases: what every position emits, and where every record's bases and bytes begin
-  DevBuf d_part, d_base_at, d_byte_at;
+  DevBuf &d_part = fr.d_part, &d_base_at = fr.d_base_at, &d_byte_at = fr.d_byte_at;
   if (!alloc(d_part, n_refs * 8, "the genome records' parts") || !alloc(d_base_at, (n_refs + 1) * 8, "the genome records' bases") ||
       !alloc(d_byte_at, n_refs * 8, "the genome records' bytes"))
     return PBSIM_FAILED;
-  const ConsRecords rec = {d_part.as<int64_t>(), d_base_at.as<int64_t>(), d_byte_at.as<int64_t>()};
-  launch_consensus_base_sizes(pg, table, cls, slots, (uint32_t)o.max_ins, rec, tile, cons, st);
+  const ConsRecords rec = fr.rec = {d_part.as<int64_t>(), d_base_at.as<int64_t>(), d_byte_at.as<int64_t>()};
+  launch_consensus_base_sizes(pg, table, cls, slots, (uint32_t)max_ins, rec, tile, cons, st);
   HIP_OK(hipGetLastError());
+  return PBSIM_SUCCEEDED;
+}
+
+namespace {
+
+int consensus_bam(pbsim_ctx *c, const pbsim_errors_ref *refs, int n_refs, const pbsim_errors_file *files, int n_files, const pbsim_consensus_opts &o,
+                  const pbsim_consensus_sink *sink, pbsim_consensus_result *result) {
+  hipStream_t st = c->stream;
+  BamPhases ph(st, "consensus");
+  const bool want_text = sink && sink->on_text;
+  ConsFront fr;
+  if (!consensus_front(c, kStage, ph, refs, n_refs, files, n_files, o.exclude_flags, o.min_mapq, o.min_baseq, o.min_depth, o.max_ins, &fr)) return PBSIM_FAILED;
+  const Genome &genome = fr.genome;
+  const PileGenome &pg = fr.pg;
+  const ConsSlots &slots = fr.slots;
+  const ConsRecords &rec = fr.rec;
+  const std::vector<int64_t> &name_at = fr.name_at;
+  const uint8_t *cls = fr.d_cls.as<uint8_t>();
+  int64_t *tile = fr.d_tile.as<int64_t>();
+  const int64_t tiles = fr.tiles, n_all = fr.n_all, inflated = fr.inflated, segments = fr.segments, logged = fr.logged, n_slots = slots.n, n_cells = fr.n_cells;
+  DevBuf &d_cells = fr.d_cells, &d_pile = fr.d_pile, &d_cons = fr.d_cons, &d_scan_tmp = fr.d_scan_tmp, &d_base_at = fr.d_base_at, &d_byte_at = fr.d_byte_at;
   launch_exclusive_scan_i64(tile, tile, tiles, d_scan_tmp.as<int64_t>(), tile + tiles, st);
   HIP_OK(hipGetLastError());
   launch_consensus_record_bases(pg, rec.part, tile, d_base_at.as<int64_t>(), st);

@@ -363,6 +363,10 @@ void print_help() {
           "  [--consensus-fill n|ref (n)] [--consensus-max-ins N (1024)] [--consensus-line-width N (60)]: no simulation; the consensus of\n"
           "  the aligned reads of BAM files against their genome on the GPU: the call of every site with the insertions the reads\n"
           "  agree on, as FASTA to --consensus-out; the report to stdout\n"
+          "  pbsim --call-bam FILE [--call-bam FILE ...] --call-genome FASTA --call-out FILE [--call-ref-names a,b,..] [--call-min-mapq N (0)]\n"
+          "  [--call-min-baseq N (0)] [--call-min-depth N (1)] [--call-exclude-flags F (0x900)] [--call-max-ins N (1024)]: no simulation; the\n"
+          "  differences between the genome and what the aligned reads of BAM files spell on the GPU, joined into events: substitutions,\n"
+          "  insertions and deletions as VCF records with depth and minimum support to --call-out; the report to stdout\n"
           "  --genome, --transcript, --template and --sample may be gzip-compressed (recognised by content): BGZF is\n"
           "  inflated on the GPU, other gzip by zlib on the host; the whole inflated file is held in host memory\n\n");
 }
@@ -1611,6 +1615,121 @@ int consensus_bam_main(int argc, char **argv, const pbsim_comm *comm, int device
   return 0;
 }
 
+// `pbsim --call-bam FILE [--call-bam FILE ...] --call-genome FASTA --call-out FILE ...`: the variants the aligned reads support
+// against their genome (pbsim_bam_call), the report to stdout, the VCF to --call-out.  What can be refused from the command
+// line alone is refused before a GPU is touched.
+int call_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
+  if (comm && comm->world > 1) die(": --call-bam runs on one GPU.");
+  std::vector<std::string> in_names, names;
+  std::string out_name, genome_name, names_arg;
+  bool have_names = false;
+  long long min_mapq = 0, min_baseq = 0, min_depth = 1, exclude = 0x900, max_ins = 1024;
+  for (int i = 1; i < argc; i++) {
+    const std::string a = argv[i];
+    const bool takes = a == "--call-bam" || a == "--call-genome" || a == "--call-ref-names" || a == "--call-out" || a == "--call-min-mapq" ||
+                       a == "--call-min-baseq" || a == "--call-min-depth" || a == "--call-exclude-flags" || a == "--call-max-ins" || a == "--device";
+    if (!takes)
+      die(" (%s): --call-bam takes --call-genome, --call-out, --call-ref-names, --call-min-mapq, --call-min-baseq, --call-min-depth, "
+          "--call-exclude-flags, --call-max-ins and --device, and no other option.",
+          argv[i]);
+    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
+    const char *v = argv[++i];
+    if (a == "--call-bam") in_names.push_back(v);
+    else if (a == "--call-genome") genome_name = v;
+    else if (a == "--call-ref-names") names_arg = v, have_names = true;
+    else if (a == "--call-out") out_name = v;
+    else if (a == "--device") device = device >= 0 ? device : atoi(v);
+    else if (a == "--call-exclude-flags") {
+      const bool hex = v[0] == '0' && (v[1] == 'x' || v[1] == 'X');
+      if (!whole_number(v, hex ? 16 : 10, 0, 65535, &exclude)) die(" (call-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535.", v);
+    } else if (a == "--call-max-ins") {
+      if (!whole_number(v, 10, 1, 65535, &max_ins)) die(" (call-max-ins: %s): a whole number, 1 .. 65535.", v);
+    } else if (a == "--call-min-mapq") {
+      if (!whole_number(v, 10, 0, 255, &min_mapq)) die(" (call-min-mapq: %s): a whole number, 0 .. 255.", v);
+    } else if (a == "--call-min-baseq") {
+      if (!whole_number(v, 10, 0, 255, &min_baseq)) die(" (call-min-baseq: %s): a whole number, 0 .. 255.", v);
+    } else {
+      if (!whole_number(v, 10, 0, 1000000000000LL, &min_depth)) die(" (call-min-depth: %s): a whole number, 0 .. 1000000000000.", v);
+    }
+  }
+  if (in_names.empty()) die(": --call-bam FILE: name the BAM file.");
+  if (genome_name.empty()) die(": --call-bam needs --call-genome FASTA: the genome the reads were aligned to.");
+  if (out_name.empty()) die(": --call-bam needs --call-out FILE: where the VCF goes.");
+  if (have_names) {
+    for (size_t at = 0;;) {
+      const size_t comma = names_arg.find(',', at);
+      names.push_back(names_arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
+      if (comma == std::string::npos) break;
+      at = comma + 1;
+    }
+    char got[32], want[32];
+    snprintf(got, sizeof got, "%zu", names.size());
+    snprintf(want, sizeof want, "%zu", in_names.size());
+    if (names.size() != in_names.size()) die(" (call-ref-names): %s names for %s --call-bam files: the k-th name goes to the k-th file.", got, want);
+    for (const std::string &n : names)
+      if (n.empty()) die(" (call-ref-names): an empty name.");
+  }
+  std::vector<MappedFile> files(in_names.size());
+  for (size_t f = 0; f < files.size(); f++)
+    if (!files[f].open_file(in_names[f])) die(": Cannot open file: %s", in_names[f].c_str());
+  // the genome, through the input path of --errors-genome: each record's sequence lines, its name the id up to the first white space
+  pbsim::FastaMap fm;
+  {
+    pbsim::GenomeInfo gm;
+    bool fallback = false;
+    std::string err;
+    if (!pbsim::map_genome(genome_name.c_str(), &fm, &gm, false, &fallback, &err))
+      die(": --call-genome %s: %s", genome_name.c_str(),
+          fallback ? "not a FASTA file that can be mapped (a regular file that begins with '>' and holds no NUL byte)" : err.c_str());
+  }
+  std::vector<std::string> ref_names;
+  for (const pbsim::FastaRecord &r : fm.recs) ref_names.push_back(r.id.substr(0, r.id.find_first_of(" \t\r\n\v\f")));
+  std::vector<pbsim_errors_ref> refs;
+  for (size_t r = 0; r < fm.recs.size(); r++) refs.push_back(pbsim_errors_ref{ref_names[r].c_str(), fm.recs[r].lines, fm.recs[r].bytes});
+  pbsim_params p;
+  pbsim_params_default(&p);
+  p.strategy = PBSIM_STRATEGY_WGS;
+  p.method = PBSIM_METHOD_ERR;
+  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
+  if (!ctx) check(0);
+  struct Result {
+    FILE *fp = NULL;
+    bool write_failed = false;
+  } res;
+  if (!out_name.empty()) {
+    res.fp = fopen(out_name.c_str(), "wb");
+    if (!res.fp) die(": Cannot open output file: %s", out_name.c_str());
+  }
+  std::vector<pbsim_errors_file> in(files.size());
+  for (size_t f = 0; f < files.size(); f++) in[f] = pbsim_errors_file{files[f].map, (int64_t)files[f].n, have_names ? names[f].c_str() : NULL};
+  pbsim_call_opts opts = {(int32_t)exclude, (int32_t)min_mapq, (int32_t)min_baseq, (int32_t)max_ins, (int64_t)min_depth, 0};
+  pbsim_call_sink sink = {&res,
+                            [](void *u, const char *z, int64_t k, int64_t) {
+                              Result *x = (Result *)u;
+                              if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
+                              return x->write_failed ? 0 : 1;
+                            },
+                            NULL};
+  if (!res.fp) sink.on_text = NULL;
+  pbsim_call_result result;
+  const bool ok = pbsim_bam_call(ctx, refs.data(), (int)refs.size(), in.data(), (int)in.size(), &opts, &sink, &result) != 0;
+  if (res.fp && fclose(res.fp) != 0) res.write_failed = true;
+  if (!ok || res.write_failed) {
+    fprintf(stderr, "ERROR: %s\n", res.write_failed ? ("write error on " + out_name).c_str() : pbsim_last_error());
+    if (in_names.size() > 1)
+      for (size_t f = 0; f < in_names.size(); f++) fprintf(stderr, "ERROR: file %zu is %s\n", f, in_names[f].c_str());
+    if (!out_name.empty()) unlink(out_name.c_str());
+    quit(-1);
+  }
+  std::string text((size_t)pbsim_call_report(&result, NULL, 0), '\0');
+  pbsim_call_report(&result, &text[0], (int64_t)text.size());
+  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
+  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
+  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
+  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int device) {
@@ -1628,6 +1747,8 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
     if (!strcmp(argv[i], "--pileup-bam")) return pileup_bam_main(argc, argv, comm, device);
   for (int i = 1; i < argc; i++)
     if (!strcmp(argv[i], "--consensus-bam")) return consensus_bam_main(argc, argv, comm, device);
+  for (int i = 1; i < argc; i++)
+    if (!strcmp(argv[i], "--call-bam")) return call_bam_main(argc, argv, comm, device);
   if (argc >= 2 && !strcmp(argv[1], "--sort-truth-bam")) {
     // the standalone mode: no simulation, the named files sorted and indexed in place on one GPU
     if (comm && comm->world > 1) die(": --sort-truth-bam runs on one GPU.");
