@@ -802,6 +802,75 @@ int pbsim_bam_call(pbsim_ctx *ctx, const pbsim_errors_ref *refs, int n_refs, con
  * variants, the four types, ref_bases, alt_bases, longest_ref, longest_alt, unplaced_records and unplaced_sites.  Returns the
  * text's length, and writes it (no NUL) where buf holds cap >= that many bytes; -1: bad argument. */
 int64_t pbsim_call_report(const pbsim_call_result *result, char *buf, int64_t cap);
+/* A variant genome and its truth variants drawn from a genome and a seed on the GPU: SNVs, insertions and deletions, the variant
+ * genome as FASTA (to simulate from) and the variants as VCFv4.2 in the dialect pbsim_bam_call writes, so that a call set can be
+ * compared with the truth line by line.  No BAM is read: refs are the genome's records as pbsim_bam_errors takes them (the line
+ * feeds dropped, a-z upper-cased, each record on its own; two equal names, a missing name and a record of 2^31 - 1 bases or more
+ * are refused; empty records are allowed).
+ * Draws.  D(r, p, sub, j) is word j % 4 of philox4x32_10(ctr = (j / 4, sub, p, r), key = (seed, 0x4D555441)) shifted right by one
+ * (31 bits), r the record's index in refs and p the 0-based position.  Nothing else enters a draw: the result does not depend on
+ * tiles, grids or the other records' contents.
+ * Events.  A position is eligible where its prepared byte is A, C, G or T; every other position draws nothing.  At an eligible p,
+ * e = D(r, p, 0, 0) % 1000000: e < snv_ppm an snv, e < snv_ppm + ins_ppm an ins, e < snv_ppm + ins_ppm + del_ppm a del, else
+ * nothing.  An ins or del has length L = 1 + the number of leading draws j = 0, 1, .. with D(r, p, 1, j) % 1000000 < ext_ppm, at
+ * most max_indel.  A del at p covers p + 1 .. p + L, cut at the record's end and in front of the first byte that is not A C G T
+ * (pbsim_bam_call spells the genome's byte at a ref_n site: a deleted N would not come back); a run cut to nothing is no event
+ * and counts in void_del.  drawn[]: the snv, ins and del events that are left.
+ * The deleted set is the union of all del runs, whatever happens to the events that drew them; a record's position 0 is never in
+ * it.  At a deleted position an snv or ins is `dropped`, a del is `merged`: its run still counts in the union.
+ * What p spells, E(p): nothing where p is deleted; at an snv "ACGT"[(i + 1 + D(r, p, 0, 1) % 3) % 4], i the genome's base; at an
+ * ins the genome's byte, then L bases "ACGT"[D(r, p, 2, j) % 4], j = 0 .. L - 1; else the prepared byte.
+ * FASTA.  Per record in order `>name`, then E(0) .. E(n - 1) joined in lines of line_width (0: one line), the layout of
+ * pbsim_bam_consensus; an empty record writes only its header line.
+ * VCF.  The positions that are not deleted are anchors; an anchor's group is the anchor and the deleted run behind it.  REF is the
+ * group's prepared bytes, ALT is E(anchor); a line is written exactly where they differ: name, POS = anchor + 1, `.`, REF, ALT,
+ * `.`, `.`, `TYPE=t`, tab-separated, t snv, ins or del as pbsim_bam_call types them (complex cannot arise).  No
+ * left-normalisation.  The header, written by the host, counts in vcf_bytes: fileformat, source,
+ * `##pbsim_mutate=seed=..;snv_ppm=..;ins_ppm=..;del_ppm=..;ext_ppm=..;max_indel=..`, one contig line per record, the TYPE INFO
+ * line as pbsim_bam_call words it, the column line.
+ * Origin map (where on_origin is set): one int32 per written base of a record: p for the base that stands for genome position p,
+ * kept or substituted; -1 - p for a base inserted behind p.  With the per-base reference coordinates of pbsim_simulate_arrays it
+ * takes a read simulated from the variant genome back to the original one.
+ * Result.  variants = sum(types) = sum(drawn) - dropped - merged; bases_out = bases_in + inserted - deleted; substituted =
+ * types[snv].  fasta_bytes and vcf_bytes are complete also where no text is asked for.
+ * Sink.  on_fasta, then on_vcf: each text in offset order in pieces of at most piece_bytes; then per genome record in order
+ * on_record(user, ref, l_ref, l_out, n_variants) and on_origin(user, ref, origin, l_out), origin a host copy that holds during the
+ * call.  Each may be NULL; a text or map that is not asked for is not made.
+ * tests/mutate_model.py states the rule in plain Python.  Bad options fail before any device work.  The stage holds the genome at
+ * 2 bytes per base (as the BAM stages prepare it), three bytes and one 8-byte end per position, the texts and, where asked for, 4 bytes per written base in HBM at
+ * once, and does not chunk; an allocation that does not fit fails with the bytes it needed.  One lane walks a whole deletion
+ * group and writes a whole insertion.  After any failure the context stays usable and the result is zeroed. */
+typedef struct pbsim_mutate_opts { /* NULL: {1, 1000, 100, 100, 500000, 50, 60, 0} */
+  uint32_t seed;
+  int32_t snv_ppm, ins_ppm, del_ppm; /* each 0 .. 1000000, their sum at most 1000000: events per million eligible positions */
+  int32_t ext_ppm;                   /* 0 .. 999999: an indel grows by one base with this chance per million */
+  int32_t max_indel;                 /* 1 .. 65535 */
+  int32_t line_width;                /* 0 .. 1048576; 0: one line per record */
+  int64_t piece_bytes;               /* 0: the default; else the most text one on_fasta or on_vcf call carries */
+} pbsim_mutate_opts;
+typedef struct pbsim_mutate_sink {
+  void *user;
+  int (*on_fasta)(void *user, const char *bytes, int64_t n, int64_t offset); /* in offset order; may be NULL */
+  int (*on_vcf)(void *user, const char *bytes, int64_t n, int64_t offset);   /* in offset order, after the FASTA; may be NULL */
+  int (*on_record)(void *user, int32_t ref, int64_t l_ref, int64_t l_out, int64_t n_variants); /* per genome record; may be NULL */
+  int (*on_origin)(void *user, int32_t ref, const int32_t *origin, int64_t l_out);             /* behind its on_record; may be NULL */
+} pbsim_mutate_sink;
+typedef struct pbsim_mutate_result {
+  int64_t records, bases_in, eligible, bases_out;
+  int64_t drawn[3]; /* snv, ins, del */
+  int64_t void_del, dropped, merged;
+  int64_t substituted, inserted, deleted; /* bases */
+  int64_t variants;
+  int64_t types[3]; /* snv, ins, del */
+  int64_t ref_bases, alt_bases, longest_ref, longest_alt;
+  int64_t header_bytes, vcf_bytes, fasta_bytes;
+} pbsim_mutate_result;
+int pbsim_genome_mutate(pbsim_ctx *ctx, const pbsim_errors_ref *refs, int n_refs, const pbsim_mutate_opts *opts, const pbsim_mutate_sink *sink,
+                        pbsim_mutate_result *result);
+/* The report text, no device needed: a "#" line with the names and an "M" line with the values of the result in its order, the
+ * arrays spread (drawn_snv, drawn_ins, drawn_del; snv, ins, del), tab-separated.  Returns the text's length, and writes it (no
+ * NUL) where buf holds cap >= that many bytes; -1: bad argument. */
+int64_t pbsim_mutate_report(const pbsim_mutate_result *result, char *buf, int64_t cap);
 
 /* ---- batch primitives (used by the drivers above, bench.py, multi-GPU) ------
  * pbsim_batch_walk     header draw + bucketing + HMM walk of reads

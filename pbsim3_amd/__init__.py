@@ -298,6 +298,33 @@ class CallResult(C.Structure):
                 ("longest_alt", C.c_int64), ("unplaced_records", C.c_int64), ("unplaced_sites", C.c_int64), ("header_bytes", C.c_int64),
                 ("text_bytes", C.c_int64)]
 
+
+
+class MutateOpts(C.Structure):
+    _fields_ = [("seed", C.c_uint32), ("snv_ppm", C.c_int32), ("ins_ppm", C.c_int32), ("del_ppm", C.c_int32), ("ext_ppm", C.c_int32),
+                ("max_indel", C.c_int32), ("line_width", C.c_int32), ("piece_bytes", C.c_int64)]
+
+
+MUTATE_TEXT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64)
+MUTATE_RECORD_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64)
+MUTATE_ORIGIN_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64)
+
+
+class MutateSink(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("on_fasta", MUTATE_TEXT_CB), ("on_vcf", MUTATE_TEXT_CB), ("on_record", MUTATE_RECORD_CB),
+                ("on_origin", MUTATE_ORIGIN_CB)]
+
+
+MUTATE_TYPES = ["snv", "ins", "del"]
+
+
+class MutateResult(C.Structure):
+    _fields_ = [("records", C.c_int64), ("bases_in", C.c_int64), ("eligible", C.c_int64), ("bases_out", C.c_int64), ("drawn", C.c_int64 * 3),
+                ("void_del", C.c_int64), ("dropped", C.c_int64), ("merged", C.c_int64), ("substituted", C.c_int64), ("inserted", C.c_int64),
+                ("deleted", C.c_int64), ("variants", C.c_int64), ("types", C.c_int64 * 3), ("ref_bases", C.c_int64), ("alt_bases", C.c_int64),
+                ("longest_ref", C.c_int64), ("longest_alt", C.c_int64), ("header_bytes", C.c_int64), ("vcf_bytes", C.c_int64),
+                ("fasta_bytes", C.c_int64)]
+
 # every symbol include/pbsim3_amd.h declares: (name, restype, argtypes)
 API = [
     ("pbsim_job_add_record", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
@@ -402,6 +429,9 @@ API = [
     ("pbsim_bam_call", C.c_int, [C.c_void_p, C.POINTER(ErrorsRef), C.c_int, C.POINTER(ErrorsFile), C.c_int, C.POINTER(CallOpts), C.POINTER(CallSink),
                                  C.POINTER(CallResult)]),
     ("pbsim_call_report", C.c_int64, [C.POINTER(CallResult), C.c_char_p, C.c_int64]),
+    ("pbsim_genome_mutate", C.c_int, [C.c_void_p, C.POINTER(ErrorsRef), C.c_int, C.POINTER(MutateOpts), C.POINTER(MutateSink),
+                                      C.POINTER(MutateResult)]),
+    ("pbsim_mutate_report", C.c_int64, [C.POINTER(MutateResult), C.c_char_p, C.c_int64]),
     ("pbsim_batch_walk", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_slot_count", C.c_int, []),
     ("pbsim_select_slot", C.c_int, [C.c_void_p, C.c_int]),
@@ -650,6 +680,39 @@ def call_report(result) -> bytes:
         raise PbsimError("pbsim_call_report: bad argument")
     buf = C.create_string_buffer(max(n, 1))
     load().pbsim_call_report(C.byref(res), buf, n)
+    return buf.raw[:n]
+
+
+MUTATE_SCALARS = ["records", "bases_in", "eligible", "bases_out", "void_del", "dropped", "merged", "substituted", "inserted", "deleted", "variants",
+                  "ref_bases", "alt_bases", "longest_ref", "longest_alt", "header_bytes", "vcf_bytes", "fasta_bytes"]
+
+
+def _mutate_dict(res) -> dict:
+    """a MutateResult as a dict: drawn and types as dicts by name, the rest as numbers"""
+    out = dict(drawn=dict(zip(MUTATE_TYPES, (int(v) for v in res.drawn))), types=dict(zip(MUTATE_TYPES, (int(v) for v in res.types))))
+    for name in MUTATE_SCALARS:
+        out[name] = int(getattr(res, name))
+    return out
+
+
+def mutate_report(result) -> bytes:
+    """The report text of Context.mutate_genome's result (the dict; drawn and types as dicts by name or as the values in order):
+    pbsim_mutate_report, no device needed."""
+    def vals(x, names):
+        return [int(x[k]) for k in names] if isinstance(x, dict) else [int(v) for v in x]
+    res = MutateResult()
+    for name in ("drawn", "types"):
+        v = vals(result[name], MUTATE_TYPES)
+        if len(v) != len(getattr(res, name)):
+            raise ValueError("mutate_report: %s has %d values, not %d" % (name, len(v), len(getattr(res, name))))
+        setattr(res, name, type(getattr(res, name))(*v))
+    for name in MUTATE_SCALARS:
+        setattr(res, name, int(result.get(name, 0)))
+    n = load().pbsim_mutate_report(C.byref(res), None, 0)
+    if n < 0:
+        raise PbsimError("pbsim_mutate_report: bad argument")
+    buf = C.create_string_buffer(max(n, 1))
+    load().pbsim_mutate_report(C.byref(res), buf, n)
     return buf.raw[:n]
 
 
@@ -1403,6 +1466,50 @@ class Context:
         out = _call_dict(res)
         got = (out, call_report(out))
         return got + (b"".join(parts), records) if text else got
+
+    def mutate_genome(self, genome, seed=1, snv_ppm=1000, ins_ppm=100, del_ppm=100, ext_ppm=500000, max_indel=50, line_width=60, text=True,
+                      origin=False, piece_bytes=0):
+        """A variant genome and its truth variants drawn from `genome` -- a list of (name, sequence lines) -- and a seed
+        (pbsim_genome_mutate; the rule: include/pbsim3_amd.h).  Returns (result, report): a dict -- drawn and types as dicts by name,
+        records, bases_in, eligible, bases_out, void_del, dropped, merged, substituted, inserted, deleted, variants, ref_bases,
+        alt_bases, longest_ref, longest_alt, header_bytes, vcf_bytes, fasta_bytes -- and the report text; with `text` three further
+        items, the FASTA, the VCF and a list of (l_ref, l_out, n_variants) per genome record; with `origin` one more, a list of numpy
+        int32 arrays, per record and written base the genome position it stands for, -1 - p for a base inserted behind p."""
+        import numpy as np
+        genome = [((nm.encode() if isinstance(nm, str) else bytes(nm)), bytes(lines)) for nm, lines in genome]
+        refs = (ErrorsRef * max(len(genome), 1))(*[ErrorsRef(nm, C.cast(C.c_char_p(lines), C.c_void_p), len(lines)) for nm, lines in genome])
+        texts, at, records, origins = ([], []), [0, 0], [], []
+
+        def on_text(which):
+            def take(user, ptr, n, offset):
+                if offset != at[which]:      # (the pieces come in offset order)
+                    return 0
+                texts[which].append(C.string_at(ptr, n))
+                at[which] += n
+                return 1
+            return take
+
+        def on_record(user, ref, l_ref, l_out, n_variants):
+            records.append((int(l_ref), int(l_out), int(n_variants)))
+            return 1
+
+        def on_origin(user, ref, ptr, l_out):
+            origins.append(np.frombuffer(C.string_at(ptr, 4 * l_out), dtype=np.int32).copy() if l_out else np.zeros(0, np.int32))
+            return 1
+        sink = MutateSink(None, MUTATE_TEXT_CB(on_text(0)) if text else MUTATE_TEXT_CB(), MUTATE_TEXT_CB(on_text(1)) if text else MUTATE_TEXT_CB(),
+                          MUTATE_RECORD_CB(on_record) if text else MUTATE_RECORD_CB(), MUTATE_ORIGIN_CB(on_origin) if origin else MUTATE_ORIGIN_CB())
+        for name, v in (("seed", seed), ("snv_ppm", snv_ppm), ("ins_ppm", ins_ppm), ("del_ppm", del_ppm), ("ext_ppm", ext_ppm),
+                        ("max_indel", max_indel), ("line_width", line_width)):
+            if not (0 <= int(v) < 2 ** 32 if name == "seed" else -2 ** 31 <= int(v) < 2 ** 31):
+                raise ValueError("%s: %d does not fit its 32-bit field" % (name, int(v)))
+        opts = MutateOpts(int(seed), int(snv_ppm), int(ins_ppm), int(del_ppm), int(ext_ppm), int(max_indel), int(line_width), int(piece_bytes))
+        res = MutateResult()
+        _check(self.lib.pbsim_genome_mutate(self.h, refs, len(genome), C.byref(opts), C.byref(sink), C.byref(res)))
+        out = _mutate_dict(res)
+        got = (out, mutate_report(out))
+        if text:
+            got += (b"".join(texts[0]), b"".join(texts[1]), records)
+        return got + (origins,) if origin else got
 
     def set_transcripts(self, ids, plus, minus, seqs):
         """ids: list[str]; plus/minus: expression counts; seqs: list[bytes]."""

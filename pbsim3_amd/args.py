@@ -498,3 +498,62 @@ def call_bam(argv):
         if "" in got["ref_names"]:
             raise ValueError("(call-ref-names): an empty name.")
     return got
+
+
+def mutate_genome(argv):
+    """`pbsim --mutate-genome FASTA --mutate-out FASTA --mutate-vcf FILE [--mutate-seed N] [--mutate-snv-ppm N] [--mutate-ins-ppm N]
+    [--mutate-del-ppm N] [--mutate-ext-ppm N] [--mutate-max-indel N] [--mutate-line-width N]` -> dict(genome, out, vcf, seed, snv_ppm,
+    ins_ppm, del_ppm, ext_ppm, max_indel, line_width): the stand-alone mode that draws a variant genome and its truth VCF
+    (pbsim_genome_mutate).  What pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
+    takes = ("--mutate-genome", "--mutate-out", "--mutate-vcf", "--mutate-seed", "--mutate-snv-ppm", "--mutate-ins-ppm", "--mutate-del-ppm",
+             "--mutate-ext-ppm", "--mutate-max-indel", "--mutate-line-width", "--device")
+    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
+    got = dict(genome=None, out=None, vcf=None, seed=1, snv_ppm=1000, ins_ppm=100, del_ppm=100, ext_ppm=500000, max_indel=50, line_width=60)
+    if any(a.split("=")[0] in ranks for a in argv):
+        raise ValueError("--mutate-genome runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a not in takes:
+            raise ValueError("(%s): --mutate-genome takes --mutate-out, --mutate-vcf, --mutate-seed, --mutate-snv-ppm, --mutate-ins-ppm, "
+                             "--mutate-del-ppm, --mutate-ext-ppm, --mutate-max-indel, --mutate-line-width and --device, and no other option." % a)
+        if i + 1 >= len(argv):
+            raise ValueError("(%s): the option needs a value." % a)
+        v = argv[i + 1]
+        i += 2
+        if a in ("--mutate-genome", "--mutate-out", "--mutate-vcf"):
+            got[a[9:]] = v
+        elif a == "--mutate-seed":
+            n = _whole(v)
+            if n is None or n > 4294967295:
+                raise ValueError("(mutate-seed: %s): a whole number, 0 .. 4294967295." % v)
+            got["seed"] = n
+        elif a in ("--mutate-snv-ppm", "--mutate-ins-ppm", "--mutate-del-ppm"):
+            n = _whole(v)
+            if n is None or n > 1000000:
+                raise ValueError("(%s: %s): a whole number, 0 .. 1000000." % (a[2:], v))
+            got[a[9:].replace("-", "_")] = n
+        elif a == "--mutate-ext-ppm":
+            n = _whole(v)
+            if n is None or n > 999999:
+                raise ValueError("(mutate-ext-ppm: %s): a whole number, 0 .. 999999." % v)
+            got["ext_ppm"] = n
+        elif a == "--mutate-max-indel":
+            n = _whole(v)
+            if n is None or not 1 <= n <= 65535:
+                raise ValueError("(mutate-max-indel: %s): a whole number, 1 .. 65535." % v)
+            got["max_indel"] = n
+        elif a == "--mutate-line-width":
+            n = _whole(v)
+            if n is None or n > 1048576:
+                raise ValueError("(mutate-line-width: %s): a whole number, 0 .. 1048576 (0: one line per record)." % v)
+            got["line_width"] = n
+    if not got["genome"]:
+        raise ValueError("--mutate-genome FASTA: name the genome.")
+    if not got["out"]:
+        raise ValueError("--mutate-genome needs --mutate-out FASTA: where the variant genome goes.")
+    if not got["vcf"]:
+        raise ValueError("--mutate-genome needs --mutate-vcf FILE: where the truth variants go.")
+    if got["snv_ppm"] + got["ins_ppm"] + got["del_ppm"] > 1000000:
+        raise ValueError("(mutate-snv-ppm + mutate-ins-ppm + mutate-del-ppm): the three rates sum to more than 1000000.")
+    return got

@@ -367,6 +367,11 @@ void print_help() {
           "  [--call-min-baseq N (0)] [--call-min-depth N (1)] [--call-exclude-flags F (0x900)] [--call-max-ins N (1024)]: no simulation; the\n"
           "  differences between the genome and what the aligned reads of BAM files spell on the GPU, joined into events: substitutions,\n"
           "  insertions and deletions as VCF records with depth and minimum support to --call-out; the report to stdout\n"
+          "  pbsim --mutate-genome FASTA --mutate-out FASTA --mutate-vcf FILE [--mutate-seed N (1)] [--mutate-snv-ppm N (1000)]\n"
+          "  [--mutate-ins-ppm N (100)] [--mutate-del-ppm N (100)] [--mutate-ext-ppm N (500000)] [--mutate-max-indel N (50)]\n"
+          "  [--mutate-line-width N (60)]: no simulation; SNVs, insertions and deletions drawn per position of the genome on the GPU:\n"
+          "  the variant genome as FASTA to --mutate-out (simulate from it), the truth variants as VCF in --call-bam's dialect to\n"
+          "  --mutate-vcf; the report to stdout\n"
           "  --genome, --transcript, --template and --sample may be gzip-compressed (recognised by content): BGZF is\n"
           "  inflated on the GPU, other gzip by zlib on the host; the whole inflated file is held in host memory\n\n");
 }
@@ -1730,6 +1735,118 @@ int call_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
   return 0;
 }
 
+// `pbsim --mutate-genome FASTA --mutate-out FASTA --mutate-vcf FILE ...`: a variant genome and its truth variants drawn from the
+// genome and a seed (pbsim_genome_mutate), the report to stdout, the variant genome to --mutate-out, the VCF to --mutate-vcf.  What
+// can be refused from the command line alone is refused before a GPU is touched.
+int mutate_genome_main(int argc, char **argv, const pbsim_comm *comm, int device) {
+  if (comm && comm->world > 1) die(": --mutate-genome runs on one GPU.");
+  std::string genome_name, out_name, vcf_name;
+  long long seed = 1, snv = 1000, ins = 100, del = 100, ext = 500000, max_indel = 50, line_width = 60;
+  for (int i = 1; i < argc; i++) {
+    const std::string a = argv[i];
+    const bool takes = a == "--mutate-genome" || a == "--mutate-out" || a == "--mutate-vcf" || a == "--mutate-seed" || a == "--mutate-snv-ppm" ||
+                       a == "--mutate-ins-ppm" || a == "--mutate-del-ppm" || a == "--mutate-ext-ppm" || a == "--mutate-max-indel" ||
+                       a == "--mutate-line-width" || a == "--device";
+    if (!takes)
+      die(" (%s): --mutate-genome takes --mutate-out, --mutate-vcf, --mutate-seed, --mutate-snv-ppm, --mutate-ins-ppm, --mutate-del-ppm, "
+          "--mutate-ext-ppm, --mutate-max-indel, --mutate-line-width and --device, and no other option.",
+          argv[i]);
+    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
+    const char *v = argv[++i];
+    if (a == "--mutate-genome") genome_name = v;
+    else if (a == "--mutate-out") out_name = v;
+    else if (a == "--mutate-vcf") vcf_name = v;
+    else if (a == "--device") device = device >= 0 ? device : atoi(v);
+    else if (a == "--mutate-seed") {
+      if (!whole_number(v, 10, 0, 4294967295LL, &seed)) die(" (mutate-seed: %s): a whole number, 0 .. 4294967295.", v);
+    } else if (a == "--mutate-ext-ppm") {
+      if (!whole_number(v, 10, 0, 999999, &ext)) die(" (mutate-ext-ppm: %s): a whole number, 0 .. 999999.", v);
+    } else if (a == "--mutate-max-indel") {
+      if (!whole_number(v, 10, 1, 65535, &max_indel)) die(" (mutate-max-indel: %s): a whole number, 1 .. 65535.", v);
+    } else if (a == "--mutate-line-width") {
+      if (!whole_number(v, 10, 0, 1048576, &line_width)) die(" (mutate-line-width: %s): a whole number, 0 .. 1048576 (0: one line per record).", v);
+    } else {
+      long long *to = a == "--mutate-snv-ppm" ? &snv : a == "--mutate-ins-ppm" ? &ins : &del;
+      if (!whole_number(v, 10, 0, 1000000, to)) die(" (%s: %s): a whole number, 0 .. 1000000.", a.c_str() + 2, v);
+    }
+  }
+  if (genome_name.empty()) die(": --mutate-genome FASTA: name the genome.");
+  if (out_name.empty()) die(": --mutate-genome needs --mutate-out FASTA: where the variant genome goes.");
+  if (vcf_name.empty()) die(": --mutate-genome needs --mutate-vcf FILE: where the truth variants go.");
+  if (snv + ins + del > 1000000) die(" (mutate-snv-ppm + mutate-ins-ppm + mutate-del-ppm): the three rates sum to more than 1000000.");
+  if (access(genome_name.c_str(), R_OK) != 0) die(": --mutate-genome %s: Cannot open file: %s", genome_name.c_str(), genome_name.c_str());
+  pbsim_params p;
+  pbsim_params_default(&p);
+  p.strategy = PBSIM_STRATEGY_WGS;
+  p.method = PBSIM_METHOD_ERR;
+  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
+  if (!ctx) check(0);
+  // the genome, through the input path of --errors-genome: each record's sequence lines, its name the id up to the first white
+  // space; the context is there first, since a BGZF file is inflated on its device
+  pbsim::FastaMap fm;
+  {
+    pbsim::GenomeInfo gm;
+    bool fallback = false;
+    std::string err;
+    pbsim::set_input_context(ctx);
+    const bool mapped = pbsim::map_genome(genome_name.c_str(), &fm, &gm, false, &fallback, &err);
+    pbsim::set_input_context(nullptr);
+    if (!mapped)
+      die(": --mutate-genome %s: %s", genome_name.c_str(),
+          fallback ? "not a FASTA file that can be mapped (a regular file that begins with '>' and holds no NUL byte)" : err.c_str());
+  }
+  std::vector<std::string> ref_names;
+  for (const pbsim::FastaRecord &r : fm.recs) ref_names.push_back(r.id.substr(0, r.id.find_first_of(" \t\r\n\v\f")));
+  std::vector<pbsim_errors_ref> refs;
+  for (size_t r = 0; r < fm.recs.size(); r++) refs.push_back(pbsim_errors_ref{ref_names[r].c_str(), fm.recs[r].lines, fm.recs[r].bytes});
+  struct Out {
+    FILE *fp = NULL;
+    bool write_failed = false;
+  } fasta, vcf;
+  fasta.fp = fopen(out_name.c_str(), "wb");
+  if (!fasta.fp) die(": Cannot open output file: %s", out_name.c_str());
+  vcf.fp = fopen(vcf_name.c_str(), "wb");
+  if (!vcf.fp) {
+    fclose(fasta.fp);
+    unlink(out_name.c_str());
+    die(": Cannot open output file: %s", vcf_name.c_str());
+  }
+  struct Both {
+    Out *fasta, *vcf;
+  } both = {&fasta, &vcf};
+  pbsim_mutate_opts opts = {(uint32_t)seed, (int32_t)snv, (int32_t)ins, (int32_t)del, (int32_t)ext, (int32_t)max_indel, (int32_t)line_width, 0};
+  pbsim_mutate_sink sink = {&both,
+                            [](void *u, const char *z, int64_t k, int64_t) {
+                              Out *x = ((Both *)u)->fasta;
+                              if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
+                              return x->write_failed ? 0 : 1;
+                            },
+                            [](void *u, const char *z, int64_t k, int64_t) {
+                              Out *x = ((Both *)u)->vcf;
+                              if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
+                              return x->write_failed ? 0 : 1;
+                            },
+                            NULL, NULL};
+  pbsim_mutate_result result;
+  const bool ok = pbsim_genome_mutate(ctx, refs.data(), (int)refs.size(), &opts, &sink, &result) != 0;
+  if (fclose(fasta.fp) != 0) fasta.write_failed = true;
+  if (fclose(vcf.fp) != 0) vcf.write_failed = true;
+  if (!ok || fasta.write_failed || vcf.write_failed) {
+    fprintf(stderr, "ERROR: %s\n",
+            fasta.write_failed ? ("write error on " + out_name).c_str() : vcf.write_failed ? ("write error on " + vcf_name).c_str() : pbsim_last_error());
+    unlink(out_name.c_str());
+    unlink(vcf_name.c_str());
+    quit(-1);
+  }
+  std::string text((size_t)pbsim_mutate_report(&result, NULL, 0), '\0');
+  pbsim_mutate_report(&result, &text[0], (int64_t)text.size());
+  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
+  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
+  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
+  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int device) {
@@ -1749,6 +1866,8 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
     if (!strcmp(argv[i], "--consensus-bam")) return consensus_bam_main(argc, argv, comm, device);
   for (int i = 1; i < argc; i++)
     if (!strcmp(argv[i], "--call-bam")) return call_bam_main(argc, argv, comm, device);
+  for (int i = 1; i < argc; i++)
+    if (!strcmp(argv[i], "--mutate-genome")) return mutate_genome_main(argc, argv, comm, device);
   if (argc >= 2 && !strcmp(argv[1], "--sort-truth-bam")) {
     // the standalone mode: no simulation, the named files sorted and indexed in place on one GPU
     if (comm && comm->world > 1) die(": --sort-truth-bam runs on one GPU.");

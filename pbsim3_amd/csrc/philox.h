@@ -34,6 +34,7 @@ constexpr uint32_t kPhiloxW1 = 0xBB67AE85u;
 
 constexpr uint32_t kStreamHeader = 0x48445221u;  // "HDR!"
 constexpr uint32_t kStreamWalk = 0x57414C4Bu;    // "WALK"
+constexpr uint32_t kStreamMutate = 0x4D555441u;  // "MUTA": ctr = (draw / 4, sub, position, record), see genome_mutate.hip
 
 struct U4 {
   uint32_t x, y, z, w;
