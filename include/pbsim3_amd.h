@@ -804,7 +804,7 @@ int pbsim_bam_call(pbsim_ctx *ctx, const pbsim_errors_ref *refs, int n_refs, con
 int64_t pbsim_call_report(const pbsim_call_result *result, char *buf, int64_t cap);
 /* A variant genome and its truth variants drawn from a genome and a seed on the GPU: SNVs, insertions and deletions, the variant
  * genome as FASTA (to simulate from) and the variants as VCFv4.2 in the dialect pbsim_bam_call writes, so that a call set can be
- * compared with the truth line by line.  No BAM is read: refs are the genome's records as pbsim_bam_errors takes them (the line
+ * compared with the truth (pbsim_vcf_compare).  No BAM is read: refs are the genome's records as pbsim_bam_errors takes them (the line
  * feeds dropped, a-z upper-cased, each record on its own; two equal names, a missing name and a record of 2^31 - 1 bases or more
  * are refused; empty records are allowed).
  * Draws.  D(r, p, sub, j) is word j % 4 of philox4x32_10(ctr = (j / 4, sub, p, r), key = (seed, 0x4D555441)) shifted right by one
@@ -871,6 +871,69 @@ int pbsim_genome_mutate(pbsim_ctx *ctx, const pbsim_errors_ref *refs, int n_refs
  * arrays spread (drawn_snv, drawn_ins, drawn_del; snv, ins, del), tab-separated.  Returns the text's length, and writes it (no
  * NUL) where buf holds cap >= that many bytes; -1: bad argument. */
 int64_t pbsim_mutate_report(const pbsim_mutate_result *result, char *buf, int64_t cap);
+/* A call set scored against the truth variants on the GPU: two VCF texts over one genome, every indel moved to its leftmost
+ * placement first, so that `c1 6 A AA` and `c1 3 A AA` over GCAAAAT are one insertion.  refs are the genome's records as
+ * pbsim_bam_errors takes them (prepared: the line feeds dropped, a-z upper-cased).  ref_names (NULL: the records' own names) gives
+ * per genome record the contig name the VCFs use for it; a missing or empty name and two equal names are refused.
+ * Lines.  A line ends at \n; a \r just in front of that \n is dropped; the last line needs no \n.  Empty lines and lines that begin
+ * with # are not data lines.  Data lines are numbered from 1 per file.  Columns are separated by tabs: CHROM, POS, ID, REF, ALT,
+ * QUAL, FILTER, INFO; FILTER is present where the line has seven columns, INFO where it has eight.
+ * Classes.  The first that applies takes a data line out.  malformed: fewer than five columns, an empty CHROM, REF or ALT, a POS
+ * that is not one or more digits with a value 1 .. 2^31 - 1.  unknown_contig: CHROM is none of the names, byte by byte.
+ * unsupported: REF or ALT, a-z upper-cased, holds a byte outside ACGTN (so `,`, `<`, `*`, `.`).  ref_mismatch: REF runs past the
+ * record's end or differs from the prepared genome bytes at POS - 1.  filtered: FILTER is present and neither `.` nor `PASS`; in
+ * the calls also MS < min_ms, MS the value of the leading digits (held to 2^31 - 1) behind the first `MS=` that begins INFO or
+ * follows a `;` in it, 0 without one.  no_change: REF equals ALT.
+ * The form (r, s, d, X) of a line that is left: r the genome record, s = POS - 1; while REF and ALT both have bytes and their last
+ * bytes agree both lose the last byte; while both have bytes and their first bytes agree both lose the first byte and s grows by 1;
+ * if exactly one is empty now the other, Y, moves left: while s > 0 and the genome's byte at s - 1 equals Y's last byte, Y is
+ * rotated right by one and s falls by 1.  The walk stays inside the record.  d is the length of what is left of REF, X what is
+ * left of ALT, upper-cased: no padding base.  Type: snv where d = 1 and |X| = 1; ins where d = 0; del where |X| = 0; else complex.
+ * Duplicates.  Within one file a line whose form equals that of an earlier line of the file is `dup`; the others are compared.
+ * Verdicts.  Forms are equal where r, s, d and the bytes of X are.  A compared truth line is `found` where a compared call has an
+ * equal form, else `missed`; a compared call is `tp` where a compared truth line has an equal form, else `fp_site` where one has
+ * the same (r, s), else `fp`.  MATE is the number of the line with the equal form in the other file, else 0.
+ * Result.  files[truth, calls][]: lines, malformed, unknown_contig, unsupported, ref_mismatch, filtered, no_change, dup, compared,
+ * shifted (lines the left move moved, dup ones included), longest_shift (steps).  types[snv, ins, del, complex][]: truth, found,
+ * calls, tp, fp (fp_site included), fp_site.  lengths[ins, del][bin][]: truth, found, calls, tp, the bin by |X| of an ins and d of
+ * a del: 1, 2-5, 6-15, 16-49, 50+.  ms[min(MS, 63)][]: tp, fp of the compared calls.  text_bytes: the annotated text's size under
+ * `lines`, also where no text is asked for.
+ * The annotated text (sink->on_text, in offset order in pieces of at most piece_bytes; NULL: none is made): the header line
+ * `#file line CHROM POS REF ALT type start ref_len alt verdict mate` (tab-separated, as every line), then one line per data line,
+ * truth first, each file in order: T or C, the line's number, CHROM, POS, REF, ALT as in the file (`.` for a column the line lacks
+ * or that is empty), the type, s + 1, d, X (`.` where X is empty; all four `.` for a line a class took out), the verdict or the
+ * class, MATE.  lines 0 leaves out `found` and `tp`; lines 1 writes every data line.
+ * tests/compare_model.py states the rule in plain Python.  lines outside 0 .. 1, a negative min_ms or piece_bytes and a bad name
+ * fail before any device work.  Limits: both files' data lines together number below 2^31; no data line is longer than 2^31 - 1
+ * bytes; the genome's limits are pbsim_bam_errors's.  The stage holds the genome (2 bytes per base), both texts, 104 bytes per data
+ * line, the sort's scratch and the annotated text in HBM at once and does not chunk.  One lane parses a whole line and walks a whole left move: a
+ * tandem repeat of n bases costs n steps of one lane; one lane walks its run of lines at one (r, s), quadratic in the run's length.
+ * After any failure the context stays usable and the result is zeroed. */
+typedef struct pbsim_compare_opts { /* NULL: {0, 0, 0} */
+  int32_t lines;       /* 0: the annotated text leaves out found and tp; 1: every data line */
+  int32_t min_ms;      /* 0 .. 2^31 - 1: a call with MS below it is filtered */
+  int64_t piece_bytes; /* 0: the default; else the most text one on_text call carries */
+} pbsim_compare_opts;
+typedef struct pbsim_compare_sink {
+  void *user;
+  int (*on_text)(void *user, const char *bytes, int64_t n, int64_t offset); /* in offset order; may be NULL */
+} pbsim_compare_sink;
+typedef struct pbsim_compare_result {
+  int64_t files[2][11];
+  int64_t types[4][6];
+  int64_t lengths[2][5][4];
+  int64_t ms[64][2];
+  int64_t text_bytes;
+} pbsim_compare_result;
+int pbsim_vcf_compare(pbsim_ctx *ctx, const pbsim_errors_ref *refs, int n_refs, const char *const *ref_names, const void *truth, int64_t n_truth,
+                      const void *calls, int64_t n_calls, const pbsim_compare_opts *opts, const pbsim_compare_sink *sink,
+                      pbsim_compare_result *result);
+/* The report text, no device needed: "#" and the names of files[], "T" and "C" with the values; "P\t<type>" per type and for `all`
+ * with truth, found, calls, tp, fp, fp_site, recall_ppm = found * 1000000 / truth and precision_ppm = tp * 1000000 / calls (integer
+ * division; 0 where the denominator is 0); "L\t<ins|del>\t<bin>" with the four numbers for the bins that are not all 0;
+ * "Q\t<ms>" with tp, fp and the sums of tp and fp over this bin and all higher ones -- what min_ms = ms would leave -- for the bins
+ * that are not empty.  Returns the text's length, and writes it (no NUL) where buf holds cap >= that many bytes; -1: bad argument. */
+int64_t pbsim_compare_report(const pbsim_compare_result *result, char *buf, int64_t cap);
 
 /* ---- batch primitives (used by the drivers above, bench.py, multi-GPU) ------
  * pbsim_batch_walk     header draw + bucketing + HMM walk of reads

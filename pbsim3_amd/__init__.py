@@ -325,6 +325,25 @@ class MutateResult(C.Structure):
                 ("longest_ref", C.c_int64), ("longest_alt", C.c_int64), ("header_bytes", C.c_int64), ("vcf_bytes", C.c_int64),
                 ("fasta_bytes", C.c_int64)]
 
+
+class CompareOpts(C.Structure):
+    _fields_ = [("lines", C.c_int32), ("min_ms", C.c_int32), ("piece_bytes", C.c_int64)]
+
+
+COMPARE_TEXT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64)
+
+
+class CompareSink(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("on_text", COMPARE_TEXT_CB)]
+
+
+COMPARE_LINES = {"discordant": 0, "all": 1}
+
+
+class CompareResult(C.Structure):
+    _fields_ = [("files", C.c_int64 * 11 * 2), ("types", C.c_int64 * 6 * 4), ("lengths", C.c_int64 * 4 * 5 * 2), ("ms", C.c_int64 * 2 * 64),
+                ("text_bytes", C.c_int64)]
+
 # every symbol include/pbsim3_amd.h declares: (name, restype, argtypes)
 API = [
     ("pbsim_job_add_record", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
@@ -432,6 +451,9 @@ API = [
     ("pbsim_genome_mutate", C.c_int, [C.c_void_p, C.POINTER(ErrorsRef), C.c_int, C.POINTER(MutateOpts), C.POINTER(MutateSink),
                                       C.POINTER(MutateResult)]),
     ("pbsim_mutate_report", C.c_int64, [C.POINTER(MutateResult), C.c_char_p, C.c_int64]),
+    ("pbsim_vcf_compare", C.c_int, [C.c_void_p, C.POINTER(ErrorsRef), C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int64, C.c_char_p, C.c_int64,
+                                    C.POINTER(CompareOpts), C.POINTER(CompareSink), C.POINTER(CompareResult)]),
+    ("pbsim_compare_report", C.c_int64, [C.POINTER(CompareResult), C.c_char_p, C.c_int64]),
     ("pbsim_batch_walk", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_slot_count", C.c_int, []),
     ("pbsim_select_slot", C.c_int, [C.c_void_p, C.c_int]),
@@ -713,6 +735,40 @@ def mutate_report(result) -> bytes:
         raise PbsimError("pbsim_mutate_report: bad argument")
     buf = C.create_string_buffer(max(n, 1))
     load().pbsim_mutate_report(C.byref(res), buf, n)
+    return buf.raw[:n]
+
+
+COMPARE_SHAPES = dict(files=(2, 11), types=(4, 6), lengths=(2, 5, 4), ms=(64, 2))
+
+
+def _nested(x):
+    """a ctypes array of arrays as lists of ints"""
+    return [_nested(v) for v in x] if hasattr(x, "__len__") else int(x)
+
+
+def _compare_dict(res) -> dict:
+    """a CompareResult as a dict: files [truth, calls][11], types [snv, ins, del, complex][6], lengths [ins, del][bin][4], ms [64][2] as
+    nested lists in the header's order, text_bytes as a number"""
+    out = {name: _nested(getattr(res, name)) for name in COMPARE_SHAPES}
+    out["text_bytes"] = int(res.text_bytes)
+    return out
+
+
+def compare_report(result) -> bytes:
+    """The report text of Context.compare_vcf's result (the dict of nested lists): pbsim_compare_report, no device needed."""
+    import numpy as np
+    res = CompareResult()
+    for name, shape in COMPARE_SHAPES.items():
+        v = np.asarray(result.get(name, np.zeros(shape, np.int64)), dtype=np.int64)
+        if v.shape != shape:
+            raise ValueError("compare_report: %s has the shape %s, not %s" % (name, v.shape, shape))
+        C.memmove(C.addressof(getattr(res, name)), np.ascontiguousarray(v).ctypes.data, v.nbytes)
+    res.text_bytes = int(result.get("text_bytes", 0))
+    n = load().pbsim_compare_report(C.byref(res), None, 0)
+    if n < 0:
+        raise PbsimError("pbsim_compare_report: bad argument")
+    buf = C.create_string_buffer(max(n, 1))
+    load().pbsim_compare_report(C.byref(res), buf, n)
     return buf.raw[:n]
 
 
@@ -1510,6 +1566,41 @@ class Context:
         if text:
             got += (b"".join(texts[0]), b"".join(texts[1]), records)
         return got + (origins,) if origin else got
+
+    def compare_vcf(self, truth, calls, genome, ref_names=None, lines="discordant", min_ms=0, text=True, piece_bytes=0):
+        """A call set scored against the truth variants, both VCF texts over `genome` -- a list of (name, sequence lines) --, every
+        indel moved to its leftmost placement first (pbsim_vcf_compare; the rule: include/pbsim3_amd.h).  ref_names: per genome
+        record the contig name the VCFs use for it (None: the records' own).  lines: "discordant" or "all" (or 0, 1).  Returns
+        (result, report): a dict of nested lists -- files, types, lengths, ms -- with text_bytes, and the report text; with `text`
+        one further item, the annotated text."""
+        truth, calls = bytes(truth), bytes(calls)
+        genome = [((nm.encode() if isinstance(nm, str) else bytes(nm)), bytes(ls)) for nm, ls in genome]
+        refs = (ErrorsRef * max(len(genome), 1))(*[ErrorsRef(nm, C.cast(C.c_char_p(ls), C.c_void_p), len(ls)) for nm, ls in genome])
+        names = None
+        if ref_names is not None:
+            used = [nm.encode() if isinstance(nm, str) else bytes(nm) for nm in ref_names]
+            if len(used) != len(genome):
+                raise ValueError("ref_names: one entry per genome record (%d given for %d records)" % (len(used), len(genome)))
+            names = (C.c_char_p * max(len(used), 1))(*used)
+        for name, v in (("lines", COMPARE_LINES.get(lines, lines)), ("min_ms", min_ms)):
+            if not -2 ** 31 <= int(v) < 2 ** 31:
+                raise ValueError("%s: %d does not fit its 32-bit field" % (name, int(v)))
+        parts, at = [], [0]
+
+        def on_text(user, ptr, n, offset):
+            if offset != at[0]:      # (the pieces come in offset order)
+                return 0
+            parts.append(C.string_at(ptr, n))
+            at[0] += n
+            return 1
+        sink = CompareSink(None, COMPARE_TEXT_CB(on_text) if text else COMPARE_TEXT_CB())
+        opts = CompareOpts(int(COMPARE_LINES.get(lines, lines)), int(min_ms), int(piece_bytes))
+        res = CompareResult()
+        _check(self.lib.pbsim_vcf_compare(self.h, refs, len(genome), names, truth, len(truth), calls, len(calls), C.byref(opts), C.byref(sink),
+                                          C.byref(res)))
+        out = _compare_dict(res)
+        got = (out, compare_report(out))
+        return got + (b"".join(parts),) if text else got
 
     def set_transcripts(self, ids, plus, minus, seqs):
         """ids: list[str]; plus/minus: expression counts; seqs: list[bytes]."""

@@ -557,3 +557,50 @@ def mutate_genome(argv):
     if got["snv_ppm"] + got["ins_ppm"] + got["del_ppm"] > 1000000:
         raise ValueError("(mutate-snv-ppm + mutate-ins-ppm + mutate-del-ppm): the three rates sum to more than 1000000.")
     return got
+
+
+def compare_vcf(argv):
+    """`pbsim --compare-vcf CALLS --compare-truth TRUTH --compare-genome FASTA [--compare-out FILE] [--compare-lines discordant|all]
+    [--compare-min-ms N] [--compare-ref-names a,b,..]` -> dict(calls, truth, genome, out, lines, min_ms, ref_names): the stand-alone
+    mode that scores a call set against the truth variants (pbsim_vcf_compare).  What pbsim_cli_main refuses from the command line
+    alone raises ValueError with its message."""
+    takes = ("--compare-vcf", "--compare-truth", "--compare-genome", "--compare-out", "--compare-lines", "--compare-min-ms", "--compare-ref-names",
+             "--device")
+    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
+    got = dict(calls=None, truth=None, genome=None, out=None, lines="discordant", min_ms=0, ref_names=None)
+    if any(a.split("=")[0] in ranks for a in argv):
+        raise ValueError("--compare-vcf runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a not in takes:
+            raise ValueError("(%s): --compare-vcf takes --compare-truth, --compare-genome, --compare-out, --compare-lines, --compare-min-ms, "
+                             "--compare-ref-names and --device, and no other option." % a)
+        if i + 1 >= len(argv):
+            raise ValueError("(%s): the option needs a value." % a)
+        v = argv[i + 1]
+        i += 2
+        if a == "--compare-vcf":
+            got["calls"] = v
+        elif a in ("--compare-truth", "--compare-genome", "--compare-out"):
+            got[a[10:]] = v
+        elif a == "--compare-ref-names":
+            got["ref_names"] = v.split(",")
+        elif a == "--compare-lines":
+            if v not in ("discordant", "all"):
+                raise ValueError("(compare-lines: %s): discordant or all." % v)
+            got["lines"] = v
+        elif a == "--compare-min-ms":
+            n = _whole(v)
+            if n is None or n > 2147483647:
+                raise ValueError("(compare-min-ms: %s): a whole number, 0 .. 2147483647." % v)
+            got["min_ms"] = n
+    if not got["calls"]:
+        raise ValueError("--compare-vcf CALLS: name the call set.")
+    if not got["truth"]:
+        raise ValueError("--compare-vcf needs --compare-truth VCF: the truth variants.")
+    if not got["genome"]:
+        raise ValueError("--compare-vcf needs --compare-genome FASTA: the genome both files speak of.")
+    if got["ref_names"] is not None and "" in got["ref_names"]:
+        raise ValueError("(compare-ref-names): an empty name.")
+    return got

@@ -371,7 +371,11 @@ void print_help() {
           "  [--mutate-ins-ppm N (100)] [--mutate-del-ppm N (100)] [--mutate-ext-ppm N (500000)] [--mutate-max-indel N (50)]\n"
           "  [--mutate-line-width N (60)]: no simulation; SNVs, insertions and deletions drawn per position of the genome on the GPU:\n"
           "  the variant genome as FASTA to --mutate-out (simulate from it), the truth variants as VCF in --call-bam's dialect to\n"
-          "  --mutate-vcf; the report to stdout\n"
+          "  --mutate-vcf (score a call set against it with --compare-vcf); the report to stdout\n"
+          "  pbsim --compare-vcf CALLS --compare-truth TRUTH --compare-genome FASTA [--compare-out FILE] [--compare-lines discordant|all\n"
+          "  (discordant)] [--compare-min-ms N (0)] [--compare-ref-names a,b,..]: no simulation; a call set scored against the truth\n"
+          "  variants on the GPU, every indel moved to its leftmost placement first: recall and precision per type, per indel length\n"
+          "  and per MS to stdout, one annotated line per data line to --compare-out; the three inputs may be gzip-compressed\n"
           "  --genome, --transcript, --template and --sample may be gzip-compressed (recognised by content): BGZF is\n"
           "  inflated on the GPU, other gzip by zlib on the host; the whole inflated file is held in host memory\n\n");
 }
@@ -1847,6 +1851,137 @@ int mutate_genome_main(int argc, char **argv, const pbsim_comm *comm, int device
   return 0;
 }
 
+// `pbsim --compare-vcf CALLS --compare-truth TRUTH --compare-genome FASTA ...`: a call set scored against the truth variants
+// (pbsim_vcf_compare), the report to stdout, the annotated lines to --compare-out.  What can be refused from the command line
+// alone is refused before a GPU is touched.  The context is made before the files are read: a BGZF file is inflated on its device.
+int compare_vcf_main(int argc, char **argv, const pbsim_comm *comm, int device) {
+  if (comm && comm->world > 1) die(": --compare-vcf runs on one GPU.");
+  std::string calls_name, truth_name, genome_name, out_name, names_arg;
+  std::vector<std::string> names;
+  bool have_names = false;
+  long long lines = 0, min_ms = 0;
+  for (int i = 1; i < argc; i++) {
+    const std::string a = argv[i];
+    const bool takes = a == "--compare-vcf" || a == "--compare-truth" || a == "--compare-genome" || a == "--compare-out" || a == "--compare-lines" ||
+                       a == "--compare-min-ms" || a == "--compare-ref-names" || a == "--device";
+    if (!takes)
+      die(" (%s): --compare-vcf takes --compare-truth, --compare-genome, --compare-out, --compare-lines, --compare-min-ms, --compare-ref-names "
+          "and --device, and no other option.",
+          argv[i]);
+    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
+    const char *v = argv[++i];
+    if (a == "--compare-vcf") calls_name = v;
+    else if (a == "--compare-truth") truth_name = v;
+    else if (a == "--compare-genome") genome_name = v;
+    else if (a == "--compare-out") out_name = v;
+    else if (a == "--compare-ref-names") names_arg = v, have_names = true;
+    else if (a == "--device") device = device >= 0 ? device : atoi(v);
+    else if (a == "--compare-lines") {
+      if (strcmp(v, "discordant") && strcmp(v, "all")) die(" (compare-lines: %s): discordant or all.", v);
+      lines = !strcmp(v, "all");
+    } else {
+      if (!whole_number(v, 10, 0, 2147483647LL, &min_ms)) die(" (compare-min-ms: %s): a whole number, 0 .. 2147483647.", v);
+    }
+  }
+  if (calls_name.empty()) die(": --compare-vcf CALLS: name the call set.");
+  if (truth_name.empty()) die(": --compare-vcf needs --compare-truth VCF: the truth variants.");
+  if (genome_name.empty()) die(": --compare-vcf needs --compare-genome FASTA: the genome both files speak of.");
+  if (have_names) {
+    for (size_t at = 0;;) {
+      const size_t comma = names_arg.find(',', at);
+      names.push_back(names_arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
+      if (comma == std::string::npos) break;
+      at = comma + 1;
+    }
+    for (const std::string &n : names)
+      if (n.empty()) die(" (compare-ref-names): an empty name.");
+  }
+  for (const std::string *name : {&calls_name, &truth_name, &genome_name})
+    if (access(name->c_str(), R_OK) != 0) die(": Cannot open file: %s", name->c_str());
+  pbsim_params p;
+  pbsim_params_default(&p);
+  p.strategy = PBSIM_STRATEGY_WGS;
+  p.method = PBSIM_METHOD_ERR;
+  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
+  if (!ctx) check(0);
+  pbsim::set_input_context(ctx);
+  // a VCF: the inflated bytes of a gzip file, else the file as it is (an empty one has no lines)
+  struct Vcf {
+    pbsim::InputBytes gz;
+    MappedFile plain;
+    const void *bytes = NULL;
+    int64_t n = 0;
+  } vcf[2];
+  const std::string *vcf_name[2] = {&truth_name, &calls_name};
+  for (int w = 0; w < 2; w++) {
+    std::string err;
+    const int g = pbsim::open_input(vcf_name[w]->c_str(), &vcf[w].gz, &err);
+    if (g < 0) die(": %s", err.c_str());
+    if (g > 0) {
+      vcf[w].bytes = vcf[w].gz.map, vcf[w].n = (int64_t)vcf[w].gz.size;
+      continue;
+    }
+    struct stat sb;
+    if (stat(vcf_name[w]->c_str(), &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size == 0) continue;
+    if (!vcf[w].plain.open_file(*vcf_name[w])) die(": Cannot open file: %s", vcf_name[w]->c_str());
+    vcf[w].bytes = vcf[w].plain.map, vcf[w].n = (int64_t)vcf[w].plain.n;
+  }
+  pbsim::FastaMap fm;
+  {
+    pbsim::GenomeInfo gm;
+    bool fallback = false;
+    std::string err;
+    const bool mapped = pbsim::map_genome(genome_name.c_str(), &fm, &gm, false, &fallback, &err);
+    if (!mapped)
+      die(": --compare-genome %s: %s", genome_name.c_str(),
+          fallback ? "not a FASTA file that can be mapped (a regular file that begins with '>' and holds no NUL byte)" : err.c_str());
+  }
+  pbsim::set_input_context(nullptr);
+  std::vector<std::string> own_names;
+  for (const pbsim::FastaRecord &r : fm.recs) own_names.push_back(r.id.substr(0, r.id.find_first_of(" \t\r\n\v\f")));
+  std::vector<pbsim_errors_ref> refs;
+  for (size_t r = 0; r < fm.recs.size(); r++) refs.push_back(pbsim_errors_ref{own_names[r].c_str(), fm.recs[r].lines, fm.recs[r].bytes});
+  std::vector<const char *> used;
+  if (have_names) {
+    char got[32], want[32];
+    snprintf(got, sizeof got, "%zu", names.size());
+    snprintf(want, sizeof want, "%zu", refs.size());
+    if (names.size() != refs.size()) die(" (compare-ref-names): %s names for %s genome records: the k-th name goes to the k-th record.", got, want);
+    for (const std::string &n : names) used.push_back(n.c_str());
+  }
+  struct Result {
+    FILE *fp = NULL;
+    bool write_failed = false;
+  } res;
+  if (!out_name.empty()) {
+    res.fp = fopen(out_name.c_str(), "wb");
+    if (!res.fp) die(": Cannot open output file: %s", out_name.c_str());
+  }
+  pbsim_compare_opts opts = {(int32_t)lines, (int32_t)min_ms, 0};
+  pbsim_compare_sink sink = {&res, [](void *u, const char *z, int64_t k, int64_t) {
+                               Result *x = (Result *)u;
+                               if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
+                               return x->write_failed ? 0 : 1;
+                             }};
+  if (!res.fp) sink.on_text = NULL;
+  pbsim_compare_result result;
+  const bool ok = pbsim_vcf_compare(ctx, refs.data(), (int)refs.size(), have_names ? used.data() : NULL, vcf[0].bytes, vcf[0].n, vcf[1].bytes, vcf[1].n, &opts,
+                                    &sink, &result) != 0;
+  if (res.fp && fclose(res.fp) != 0) res.write_failed = true;
+  if (!ok || res.write_failed) {
+    fprintf(stderr, "ERROR: %s\n", res.write_failed ? ("write error on " + out_name).c_str() : pbsim_last_error());
+    if (!out_name.empty()) unlink(out_name.c_str());
+    quit(-1);
+  }
+  std::string text((size_t)pbsim_compare_report(&result, NULL, 0), '\0');
+  pbsim_compare_report(&result, &text[0], (int64_t)text.size());
+  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
+  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
+  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
+  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int device) {
@@ -1868,6 +2003,8 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
     if (!strcmp(argv[i], "--call-bam")) return call_bam_main(argc, argv, comm, device);
   for (int i = 1; i < argc; i++)
     if (!strcmp(argv[i], "--mutate-genome")) return mutate_genome_main(argc, argv, comm, device);
+  for (int i = 1; i < argc; i++)
+    if (!strcmp(argv[i], "--compare-vcf")) return compare_vcf_main(argc, argv, comm, device);
   if (argc >= 2 && !strcmp(argv[1], "--sort-truth-bam")) {
     // the standalone mode: no simulation, the named files sorted and indexed in place on one GPU
     if (comm && comm->world > 1) die(": --sort-truth-bam runs on one GPU.");
