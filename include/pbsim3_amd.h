@@ -934,6 +934,90 @@ int pbsim_vcf_compare(pbsim_ctx *ctx, const pbsim_errors_ref *refs, int n_refs, 
  * "Q\t<ms>" with tp, fp and the sums of tp and fp over this bin and all higher ones -- what min_ms = ms would leave -- for the bins
  * that are not empty.  Returns the text's length, and writes it (no NUL) where buf holds cap >= that many bytes; -1: bad argument. */
 int64_t pbsim_compare_report(const pbsim_compare_result *result, char *buf, int64_t cap);
+/* A VCF applied to a genome on the GPU, per haplotype: the genome's records with the lines' alleles spliced in, as FASTA (to
+ * simulate from), with an origin map on request.  It is the operation pbsim_bam_call's records and pbsim_genome_mutate's VCF are
+ * defined by: the latter's VCF applied to its genome gives its FASTA.  Haplotypes 1 and 2 of a phased VCF give the two genomes of a
+ * diploid sample.  refs and ref_names are pbsim_vcf_compare's.
+ * Lines and columns.  Exactly pbsim_vcf_compare's.  Column 9 is FORMAT, column 10 + `sample` is the sample.
+ * The allele.  ALT is split at commas into alleles 1 .. k.  With haplotype 0 the allele is 1.  With haplotype h = 1 or 2 FORMAT must
+ * be `GT` or begin with `GT:`; the genotype is the sample column up to its first `:`, one or two fields of `.` or decimal digits
+ * separated by one `/` or `|`; a genotype of one field serves both haplotypes; the allele is the value of field h.
+ * Classes.  The first that applies takes a data line out.  malformed: any of pbsim_vcf_compare's malformed conditions, or an empty
+ * allele between commas; with h != 0 also a missing sample column, a FORMAT that is not as above, a genotype that is not of that
+ * shape (more than two fields too), an allele number above k.  unknown_contig: as there.  no_call: the field is `.`.  ref_allele:
+ * the field's value is 0.  unsupported: REF or the chosen allele, a-z upper-cased, holds a byte outside ACGTN; the other alleles of
+ * the line are not looked at.  ref_mismatch, filtered (FILTER only: there is no MS rule here), no_change (REF equals the allele): as
+ * there.
+ * The form (r, s, d, X) of a line that is left: r the genome record, s = POS - 1; while REF and the allele both have bytes and their
+ * first bytes agree both lose the first byte and s grows by 1; then, while both have bytes and their last bytes agree both lose the
+ * last byte.  The prefix goes first: VCF's padding base is the first one, so pbsim_genome_mutate's `A -> ACA` stays an insertion
+ * behind its anchor.  d is the length of what is left of REF, X what is left of the allele, upper-cased.  There is no left move.
+ * Types as pbsim_vcf_compare.  s = l_ref with d = 0 is legal: an insertion behind the record's last base.
+ * Order and collisions.  The lines that are left are taken in order of (r, s, insertions before spans, line number), with end = 0 at
+ * the start of each record.  An insertion (d = 0) is applied where s >= end and no insertion at this (r, s) has been applied.  A
+ * span (d > 0) is applied where s >= end, and then end = s + d.  Every other line is `overlap`; its `by` is the number of the applied
+ * line it ran into: the span that owns end, or the earlier insertion.  This is the greedy rule of `bcftools consensus`: a line that
+ * lost blocks nothing (of [0,10), [5,20), [15,18) the first and the third are applied).  An insertion at the start of an applied
+ * span and one at its end are both applied.
+ * What comes out.  Per record, for p = 0 .. l_ref: the X of the insertion applied at p; then, for p < l_ref, the X of the span
+ * applied at p, or nothing where p lies inside an applied span behind its start, or the prepared genome byte.  The FASTA layout is
+ * pbsim_genome_mutate's; an empty record writes its header line only.
+ * Origin map (where on_origin is set): one int32 per written base of a record: p for a kept base; s + i for byte i < min(d, |X|) of
+ * a span's X; -1 - (s + d - 1) for the rest of a span's X; -1 - (s - 1) for the bytes of an insertion at s >= 1; -2^31 for the bytes
+ * of an insertion at s = 0.  This is pbsim_genome_mutate's encoding plus the one value it never needs: its insertions have an anchor.
+ * Result.  lines; one count per class; overlap; applied; types[snv, ins, del, complex] of the applied lines; bases_in; bases_out;
+ * over the applied lines inserted (the sum of |X| - min(d, |X|)), deleted (of d - min), substituted (of min): bases_out = bases_in +
+ * inserted - deleted; longest_cluster (below); fasta_bytes and text_bytes, both complete without their texts.
+ * The annotated text (on_text): the header line `#line CHROM POS REF ALT allele type start ref_len alt verdict by` (tab-separated,
+ * as every line), then one line per data line in file order: the line's number, CHROM, POS, REF, ALT, the type, s + 1, d and X
+ * spelled as pbsim_vcf_compare spells them, `allele` the chosen number in front of the type (`.` for a malformed line and a
+ * no_call), the verdict `applied`, `overlap` or the class, `by` (0 except for overlap).  lines 0 leaves out `applied`.
+ * Sink.  on_fasta, then on_text: each text in offset order in pieces of at most piece_bytes; then per genome record in order
+ * on_record(user, ref, l_ref, l_out, n_applied) and on_origin(user, ref, origin, l_out), origin a host copy that holds during the
+ * call.  Each may be NULL; a text or map that is not asked for is not made.
+ * tests/apply_model.py states the rule in plain Python.  Bad options and names fail before any device work.  With haplotype 1 or 2
+ * a file that has data lines, none of them with the sample column, fails: "no data line has a sample column N".  Limits: the data
+ * lines number below 2^31; no data line is longer than 2^31 - 1 bytes; a record has fewer than 2^31 - 1 bases; the genome's other
+ * limits are pbsim_bam_errors's.  The stage holds the genome (2 bytes per base), the VCF text, 72 bytes per data line and 33 more
+ * with the sort's scratch while the collisions are found, two 4-byte marks and one 8-byte end per position, the texts and, where asked for,
+ * 4 bytes per written base in HBM at once and does not chunk.  One lane parses a whole line and writes a whole X.  The collisions
+ * are found without a walk over all lines: the sorted lines are cut into clusters where a line begins at or behind the largest
+ * s + d of all lines in front of it (and is not an insertion just behind an insertion of its (r, s)); such a line is applied
+ * whatever came before, and one lane walks each cluster with the rule above, so a cluster of n lines costs n steps of one lane.
+ * Clusters are one line long in any sane VCF; longest_cluster reports the longest.  After any failure the context stays usable and
+ * the result is zeroed. */
+typedef struct pbsim_apply_opts { /* NULL: {0, 0, 0, 60, 0} */
+  int32_t haplotype;   /* 0: the first ALT of every line; 1, 2: that allele of the sample's GT */
+  int32_t sample;      /* 0-based sample column, read where haplotype != 0 */
+  int32_t lines;       /* 0: the annotated text leaves out `applied`; 1: every data line */
+  int32_t line_width;  /* 0 .. 1048576; 0: one line per record */
+  int64_t piece_bytes; /* 0: the default; else the most text one on_fasta or on_text call carries */
+} pbsim_apply_opts;
+typedef struct pbsim_apply_sink {
+  void *user;
+  int (*on_fasta)(void *user, const char *bytes, int64_t n, int64_t offset); /* in offset order; may be NULL */
+  int (*on_text)(void *user, const char *bytes, int64_t n, int64_t offset);  /* in offset order, after the FASTA; may be NULL */
+  int (*on_record)(void *user, int32_t ref, int64_t l_ref, int64_t l_out, int64_t n_applied); /* per genome record; may be NULL */
+  int (*on_origin)(void *user, int32_t ref, const int32_t *origin, int64_t l_out);            /* behind its on_record; may be NULL */
+} pbsim_apply_sink;
+typedef struct pbsim_apply_result {
+  int64_t lines;
+  int64_t malformed, unknown_contig, no_call, ref_allele, unsupported, ref_mismatch, filtered, no_change;
+  int64_t overlap, applied;
+  int64_t types[4]; /* snv, ins, del, complex */
+  int64_t bases_in, bases_out, inserted, deleted, substituted;
+  int64_t longest_cluster;
+  int64_t fasta_bytes, text_bytes;
+} pbsim_apply_result;
+int pbsim_vcf_apply(pbsim_ctx *ctx, const pbsim_errors_ref *refs, int n_refs, const char *const *ref_names, const void *vcf, int64_t n_vcf,
+                    const pbsim_apply_opts *opts, const pbsim_apply_sink *sink, pbsim_apply_result *result);
+/* The report text, no device needed: a "#" line with the names and an "A" line with the values of the result in its order, types
+ * spread (snv, ins, del, complex), tab-separated.  Returns the text's length, and writes it (no NUL) where buf holds cap >= that
+ * many bytes; -1: bad argument. */
+int64_t pbsim_apply_report(const pbsim_apply_result *result, char *buf, int64_t cap);
+/* The 0-based sample column that `name` has in the first line of the VCF text that begins with `#CHROM` (its columns behind
+ * FORMAT), no device needed; -1: no such line or no such name. */
+int32_t pbsim_apply_sample(const void *vcf, int64_t n_vcf, const char *name);
 
 /* ---- batch primitives (used by the drivers above, bench.py, multi-GPU) ------
  * pbsim_batch_walk     header draw + bucketing + HMM walk of reads

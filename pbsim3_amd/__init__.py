@@ -344,6 +344,33 @@ class CompareResult(C.Structure):
     _fields_ = [("files", C.c_int64 * 11 * 2), ("types", C.c_int64 * 6 * 4), ("lengths", C.c_int64 * 4 * 5 * 2), ("ms", C.c_int64 * 2 * 64),
                 ("text_bytes", C.c_int64)]
 
+class ApplyOpts(C.Structure):
+    _fields_ = [("haplotype", C.c_int32), ("sample", C.c_int32), ("lines", C.c_int32), ("line_width", C.c_int32), ("piece_bytes", C.c_int64)]
+
+
+APPLY_TEXT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64)
+APPLY_RECORD_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64)
+APPLY_ORIGIN_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64)
+
+
+class ApplySink(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("on_fasta", APPLY_TEXT_CB), ("on_text", APPLY_TEXT_CB), ("on_record", APPLY_RECORD_CB),
+                ("on_origin", APPLY_ORIGIN_CB)]
+
+
+APPLY_LINES = {"discordant": 0, "all": 1}
+APPLY_TYPES = ["snv", "ins", "del", "complex"]
+APPLY_SCALARS = ["lines", "malformed", "unknown_contig", "no_call", "ref_allele", "unsupported", "ref_mismatch", "filtered", "no_change", "overlap",
+                 "applied", "bases_in", "bases_out", "inserted", "deleted", "substituted", "longest_cluster", "fasta_bytes", "text_bytes"]
+
+
+class ApplyResult(C.Structure):
+    _fields_ = [("lines", C.c_int64), ("malformed", C.c_int64), ("unknown_contig", C.c_int64), ("no_call", C.c_int64), ("ref_allele", C.c_int64),
+                ("unsupported", C.c_int64), ("ref_mismatch", C.c_int64), ("filtered", C.c_int64), ("no_change", C.c_int64), ("overlap", C.c_int64),
+                ("applied", C.c_int64), ("types", C.c_int64 * 4), ("bases_in", C.c_int64), ("bases_out", C.c_int64), ("inserted", C.c_int64),
+                ("deleted", C.c_int64), ("substituted", C.c_int64), ("longest_cluster", C.c_int64), ("fasta_bytes", C.c_int64),
+                ("text_bytes", C.c_int64)]
+
 # every symbol include/pbsim3_amd.h declares: (name, restype, argtypes)
 API = [
     ("pbsim_job_add_record", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
@@ -454,6 +481,10 @@ API = [
     ("pbsim_vcf_compare", C.c_int, [C.c_void_p, C.POINTER(ErrorsRef), C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int64, C.c_char_p, C.c_int64,
                                     C.POINTER(CompareOpts), C.POINTER(CompareSink), C.POINTER(CompareResult)]),
     ("pbsim_compare_report", C.c_int64, [C.POINTER(CompareResult), C.c_char_p, C.c_int64]),
+    ("pbsim_vcf_apply", C.c_int, [C.c_void_p, C.POINTER(ErrorsRef), C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int64, C.POINTER(ApplyOpts),
+                                  C.POINTER(ApplySink), C.POINTER(ApplyResult)]),
+    ("pbsim_apply_report", C.c_int64, [C.POINTER(ApplyResult), C.c_char_p, C.c_int64]),
+    ("pbsim_apply_sample", C.c_int32, [C.c_char_p, C.c_int64, C.c_char_p]),
     ("pbsim_batch_walk", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_slot_count", C.c_int, []),
     ("pbsim_select_slot", C.c_int, [C.c_void_p, C.c_int]),
@@ -770,6 +801,39 @@ def compare_report(result) -> bytes:
     buf = C.create_string_buffer(max(n, 1))
     load().pbsim_compare_report(C.byref(res), buf, n)
     return buf.raw[:n]
+
+
+def _apply_dict(res) -> dict:
+    """an ApplyResult as a dict: types as a dict by name, the rest as numbers"""
+    out = dict(types=dict(zip(APPLY_TYPES, (int(v) for v in res.types))))
+    for name in APPLY_SCALARS:
+        out[name] = int(getattr(res, name))
+    return out
+
+
+def apply_report(result) -> bytes:
+    """The report text of Context.apply_vcf's result (the dict; types as a dict by name or as the values in order):
+    pbsim_apply_report, no device needed."""
+    res = ApplyResult()
+    v = result.get("types", [0] * 4)
+    v = [int(v[k]) for k in APPLY_TYPES] if isinstance(v, dict) else [int(x) for x in v]
+    if len(v) != len(res.types):
+        raise ValueError("apply_report: types has %d values, not %d" % (len(v), len(res.types)))
+    res.types = type(res.types)(*v)
+    for name in APPLY_SCALARS:
+        setattr(res, name, int(result.get(name, 0)))
+    n = load().pbsim_apply_report(C.byref(res), None, 0)
+    if n < 0:
+        raise PbsimError("pbsim_apply_report: bad argument")
+    buf = C.create_string_buffer(max(n, 1))
+    load().pbsim_apply_report(C.byref(res), buf, n)
+    return buf.raw[:n]
+
+
+def apply_sample(vcf, name) -> int:
+    """The 0-based sample column `name` has in the #CHROM line of the VCF text (pbsim_apply_sample, no device needed); -1: none."""
+    vcf = bytes(vcf)
+    return int(load().pbsim_apply_sample(vcf, len(vcf), name.encode() if isinstance(name, str) else bytes(name)))
 
 
 def inflate_bound(data: bytes) -> int:
@@ -1601,6 +1665,65 @@ class Context:
         out = _compare_dict(res)
         got = (out, compare_report(out))
         return got + (b"".join(parts),) if text else got
+
+    def apply_vcf(self, vcf, genome, ref_names=None, haplotype=0, sample=0, lines="discordant", line_width=60, fasta=True, text=True,
+                  origin=False, piece_bytes=0):
+        """The lines of a VCF text applied to `genome` -- a list of (name, sequence lines) --, per haplotype (pbsim_vcf_apply; the
+        rule: include/pbsim3_amd.h).  ref_names: per genome record the contig name the VCF uses for it (None: the records' own).
+        haplotype: 0 the first ALT of every line, 1 or 2 that allele of the sample's GT.  sample: the 0-based sample column, or the
+        sample's name in the #CHROM line.  lines: "discordant" or "all" (or 0, 1).  Returns (result, report): a dict -- types as a
+        dict by name, lines, the classes, overlap, applied, bases_in, bases_out, inserted, deleted, substituted, longest_cluster,
+        fasta_bytes, text_bytes -- and the report text; with `fasta` two further items, the FASTA and a list of (l_ref, l_out,
+        n_applied) per genome record; with `text` one more, the annotated text; with `origin` one more, a list of numpy int32 arrays
+        per record (the header states the encoding)."""
+        import numpy as np
+        vcf = bytes(vcf)
+        genome = [((nm.encode() if isinstance(nm, str) else bytes(nm)), bytes(ls)) for nm, ls in genome]
+        refs = (ErrorsRef * max(len(genome), 1))(*[ErrorsRef(nm, C.cast(C.c_char_p(ls), C.c_void_p), len(ls)) for nm, ls in genome])
+        names = None
+        if ref_names is not None:
+            used = [nm.encode() if isinstance(nm, str) else bytes(nm) for nm in ref_names]
+            if len(used) != len(genome):
+                raise ValueError("ref_names: one entry per genome record (%d given for %d records)" % (len(used), len(genome)))
+            names = (C.c_char_p * max(len(used), 1))(*used)
+        if isinstance(sample, (str, bytes)):
+            column = apply_sample(vcf, sample)
+            if column < 0:
+                raise ValueError("sample: the #CHROM line names no sample %r" % (sample,))
+            sample = column
+        for name, v in (("haplotype", haplotype), ("sample", sample), ("lines", APPLY_LINES.get(lines, lines)), ("line_width", line_width)):
+            if not -2 ** 31 <= int(v) < 2 ** 31:
+                raise ValueError("%s: %d does not fit its 32-bit field" % (name, int(v)))
+        texts, at, records, origins = ([], []), [0, 0], [], []
+
+        def on_text(which):
+            def take(user, ptr, n, offset):
+                if offset != at[which]:      # (the pieces come in offset order)
+                    return 0
+                texts[which].append(C.string_at(ptr, n))
+                at[which] += n
+                return 1
+            return take
+
+        def on_record(user, ref, l_ref, l_out, n_applied):
+            records.append((int(l_ref), int(l_out), int(n_applied)))
+            return 1
+
+        def on_origin(user, ref, ptr, l_out):
+            origins.append(np.frombuffer(C.string_at(ptr, 4 * l_out), dtype=np.int32).copy() if l_out else np.zeros(0, np.int32))
+            return 1
+        sink = ApplySink(None, APPLY_TEXT_CB(on_text(0)) if fasta else APPLY_TEXT_CB(), APPLY_TEXT_CB(on_text(1)) if text else APPLY_TEXT_CB(),
+                         APPLY_RECORD_CB(on_record) if fasta else APPLY_RECORD_CB(), APPLY_ORIGIN_CB(on_origin) if origin else APPLY_ORIGIN_CB())
+        opts = ApplyOpts(int(haplotype), int(sample), int(APPLY_LINES.get(lines, lines)), int(line_width), int(piece_bytes))
+        res = ApplyResult()
+        _check(self.lib.pbsim_vcf_apply(self.h, refs, len(genome), names, vcf, len(vcf), C.byref(opts), C.byref(sink), C.byref(res)))
+        out = _apply_dict(res)
+        got = (out, apply_report(out))
+        if fasta:
+            got += (b"".join(texts[0]), records)
+        if text:
+            got += (b"".join(texts[1]),)
+        return got + (origins,) if origin else got
 
     def set_transcripts(self, ids, plus, minus, seqs):
         """ids: list[str]; plus/minus: expression counts; seqs: list[bytes]."""

@@ -604,3 +604,59 @@ def compare_vcf(argv):
     if got["ref_names"] is not None and "" in got["ref_names"]:
         raise ValueError("(compare-ref-names): an empty name.")
     return got
+
+
+def apply_vcf(argv):
+    """`pbsim --apply-vcf VCF --apply-genome FASTA --apply-out FASTA [--apply-ref-names a,b,..] [--apply-haplotype 0|1|2] [--apply-sample
+    N|NAME] [--apply-report FILE] [--apply-lines discordant|all] [--apply-line-width N] [--apply-origin FILE]` -> dict(vcf, genome, out,
+    ref_names, haplotype, sample, report, lines, line_width, origin): the stand-alone mode that applies the lines of a VCF to a genome
+    (pbsim_vcf_apply); sample is a column (int) or a name (str).  What pbsim_cli_main refuses from the command line alone raises
+    ValueError with its message."""
+    takes = ("--apply-vcf", "--apply-genome", "--apply-out", "--apply-ref-names", "--apply-haplotype", "--apply-sample", "--apply-report",
+             "--apply-lines", "--apply-line-width", "--apply-origin", "--device")
+    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
+    got = dict(vcf=None, genome=None, out=None, ref_names=None, haplotype=0, sample=0, report=None, lines="discordant", line_width=60, origin=None)
+    if any(a.split("=")[0] in ranks for a in argv):
+        raise ValueError("--apply-vcf runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a not in takes:
+            raise ValueError("(%s): --apply-vcf takes --apply-genome, --apply-out, --apply-ref-names, --apply-haplotype, --apply-sample, "
+                             "--apply-report, --apply-lines, --apply-line-width, --apply-origin and --device, and no other option." % a)
+        if i + 1 >= len(argv):
+            raise ValueError("(%s): the option needs a value." % a)
+        v = argv[i + 1]
+        i += 2
+        if a in ("--apply-vcf", "--apply-genome", "--apply-out", "--apply-report", "--apply-origin"):
+            got[a[8:]] = v
+        elif a == "--apply-ref-names":
+            got["ref_names"] = v.split(",")
+        elif a == "--apply-haplotype":
+            n = _whole(v)
+            if n is None or n > 2:
+                raise ValueError("(apply-haplotype: %s): 0 (the first ALT of every line), 1 or 2." % v)
+            got["haplotype"] = n
+        elif a == "--apply-sample":
+            if not v:
+                raise ValueError("(apply-sample): a 0-based sample column or a sample's name.")
+            n = _whole(v)
+            got["sample"] = v if n is None or n > 2147483647 else n
+        elif a == "--apply-lines":
+            if v not in ("discordant", "all"):
+                raise ValueError("(apply-lines: %s): discordant or all." % v)
+            got["lines"] = v
+        elif a == "--apply-line-width":
+            n = _whole(v)
+            if n is None or n > 1048576:
+                raise ValueError("(apply-line-width: %s): a whole number, 0 .. 1048576 (0: one line per record)." % v)
+            got["line_width"] = n
+    if not got["vcf"]:
+        raise ValueError("--apply-vcf VCF: name the variants.")
+    if not got["genome"]:
+        raise ValueError("--apply-vcf needs --apply-genome FASTA: the genome the file speaks of.")
+    if not got["out"]:
+        raise ValueError("--apply-vcf needs --apply-out FASTA: where the spliced genome goes.")
+    if got["ref_names"] is not None and "" in got["ref_names"]:
+        raise ValueError("(apply-ref-names): an empty name.")
+    return got

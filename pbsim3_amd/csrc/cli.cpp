@@ -376,6 +376,12 @@ void print_help() {
           "  (discordant)] [--compare-min-ms N (0)] [--compare-ref-names a,b,..]: no simulation; a call set scored against the truth\n"
           "  variants on the GPU, every indel moved to its leftmost placement first: recall and precision per type, per indel length\n"
           "  and per MS to stdout, one annotated line per data line to --compare-out; the three inputs may be gzip-compressed\n"
+          "  pbsim --apply-vcf VCF --apply-genome FASTA --apply-out FASTA [--apply-ref-names a,b,..] [--apply-haplotype 0|1|2 (0)]\n"
+          "  [--apply-sample N|NAME (0)] [--apply-report FILE] [--apply-lines discordant|all (discordant)] [--apply-line-width N (60)]\n"
+          "  [--apply-origin FILE]: no simulation; the lines of a VCF applied to the genome on the GPU, the first ALT of every line or\n"
+          "  the allele the sample's GT names for the haplotype, colliding lines resolved as bcftools consensus does: the spliced genome\n"
+          "  as FASTA to --apply-out (simulate from it), the summary to stdout, one annotated line per data line to --apply-report, the\n"
+          "  origin map (int32 per written base, little-endian) to --apply-origin; both inputs may be gzip-compressed\n"
           "  --genome, --transcript, --template and --sample may be gzip-compressed (recognised by content): BGZF is\n"
           "  inflated on the GPU, other gzip by zlib on the host; the whole inflated file is held in host memory\n\n");
 }
@@ -1982,6 +1988,179 @@ int compare_vcf_main(int argc, char **argv, const pbsim_comm *comm, int device) 
   return 0;
 }
 
+// `pbsim --apply-vcf VCF --apply-genome FASTA --apply-out FASTA ...`: the lines of a VCF applied to the genome (pbsim_vcf_apply),
+// the summary to stdout, the spliced genome to --apply-out, the annotated lines to --apply-report, the origin map to
+// --apply-origin.  What can be refused from the command line alone is refused before a GPU is touched.  The context is made before
+// the files are read: a BGZF file is inflated on its device.
+int apply_vcf_main(int argc, char **argv, const pbsim_comm *comm, int device) {
+  if (comm && comm->world > 1) die(": --apply-vcf runs on one GPU.");
+  std::string vcf_name, genome_name, out_name, report_name, origin_name, names_arg, sample_name;
+  std::vector<std::string> names;
+  bool have_names = false;
+  long long haplotype = 0, sample = 0, lines = 0, line_width = 60;
+  for (int i = 1; i < argc; i++) {
+    const std::string a = argv[i];
+    const bool takes = a == "--apply-vcf" || a == "--apply-genome" || a == "--apply-out" || a == "--apply-ref-names" || a == "--apply-haplotype" ||
+                       a == "--apply-sample" || a == "--apply-report" || a == "--apply-lines" || a == "--apply-line-width" || a == "--apply-origin" ||
+                       a == "--device";
+    if (!takes)
+      die(" (%s): --apply-vcf takes --apply-genome, --apply-out, --apply-ref-names, --apply-haplotype, --apply-sample, --apply-report, --apply-lines, "
+          "--apply-line-width, --apply-origin and --device, and no other option.",
+          argv[i]);
+    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
+    const char *v = argv[++i];
+    if (a == "--apply-vcf") vcf_name = v;
+    else if (a == "--apply-genome") genome_name = v;
+    else if (a == "--apply-out") out_name = v;
+    else if (a == "--apply-report") report_name = v;
+    else if (a == "--apply-origin") origin_name = v;
+    else if (a == "--apply-ref-names") names_arg = v, have_names = true;
+    else if (a == "--device") device = device >= 0 ? device : atoi(v);
+    else if (a == "--apply-haplotype") {
+      if (!whole_number(v, 10, 0, 2, &haplotype)) die(" (apply-haplotype: %s): 0 (the first ALT of every line), 1 or 2.", v);
+    } else if (a == "--apply-sample") {
+      if (!*v) die(" (apply-sample): a 0-based sample column or a sample's name.");
+      sample_name.clear();
+      if (!whole_number(v, 10, 0, 2147483647LL, &sample)) sample_name = v, sample = 0;
+    } else if (a == "--apply-lines") {
+      if (strcmp(v, "discordant") && strcmp(v, "all")) die(" (apply-lines: %s): discordant or all.", v);
+      lines = !strcmp(v, "all");
+    } else {
+      if (!whole_number(v, 10, 0, 1048576, &line_width)) die(" (apply-line-width: %s): a whole number, 0 .. 1048576 (0: one line per record).", v);
+    }
+  }
+  if (vcf_name.empty()) die(": --apply-vcf VCF: name the variants.");
+  if (genome_name.empty()) die(": --apply-vcf needs --apply-genome FASTA: the genome the file speaks of.");
+  if (out_name.empty()) die(": --apply-vcf needs --apply-out FASTA: where the spliced genome goes.");
+  if (have_names) {
+    for (size_t at = 0;;) {
+      const size_t comma = names_arg.find(',', at);
+      names.push_back(names_arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
+      if (comma == std::string::npos) break;
+      at = comma + 1;
+    }
+    for (const std::string &n : names)
+      if (n.empty()) die(" (apply-ref-names): an empty name.");
+  }
+  for (const std::string *name : {&vcf_name, &genome_name})
+    if (access(name->c_str(), R_OK) != 0) die(": Cannot open file: %s", name->c_str());
+  pbsim_params p;
+  pbsim_params_default(&p);
+  p.strategy = PBSIM_STRATEGY_WGS;
+  p.method = PBSIM_METHOD_ERR;
+  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
+  if (!ctx) check(0);
+  pbsim::set_input_context(ctx);
+  // the VCF: the inflated bytes of a gzip file, else the file as it is (an empty one has no lines)
+  struct Vcf {
+    pbsim::InputBytes gz;
+    MappedFile plain;
+    const void *bytes = NULL;
+    int64_t n = 0;
+  } vcf;
+  {
+    std::string err;
+    const int g = pbsim::open_input(vcf_name.c_str(), &vcf.gz, &err);
+    if (g < 0) die(": %s", err.c_str());
+    struct stat sb;
+    if (g > 0) {
+      vcf.bytes = vcf.gz.map, vcf.n = (int64_t)vcf.gz.size;
+    } else if (!(stat(vcf_name.c_str(), &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size == 0)) {
+      if (!vcf.plain.open_file(vcf_name)) die(": Cannot open file: %s", vcf_name.c_str());
+      vcf.bytes = vcf.plain.map, vcf.n = (int64_t)vcf.plain.n;
+    }
+  }
+  pbsim::FastaMap fm;
+  {
+    pbsim::GenomeInfo gm;
+    bool fallback = false;
+    std::string err;
+    const bool mapped = pbsim::map_genome(genome_name.c_str(), &fm, &gm, false, &fallback, &err);
+    if (!mapped)
+      die(": --apply-genome %s: %s", genome_name.c_str(),
+          fallback ? "not a FASTA file that can be mapped (a regular file that begins with '>' and holds no NUL byte)" : err.c_str());
+  }
+  pbsim::set_input_context(nullptr);
+  if (!sample_name.empty()) {
+    const int32_t column = pbsim_apply_sample(vcf.bytes, vcf.n, sample_name.c_str());
+    if (column < 0) die(" (apply-sample: %s): the #CHROM line of %s names no such sample.", sample_name.c_str(), vcf_name.c_str());
+    sample = column;
+  }
+  std::vector<std::string> own_names;
+  for (const pbsim::FastaRecord &r : fm.recs) own_names.push_back(r.id.substr(0, r.id.find_first_of(" \t\r\n\v\f")));
+  std::vector<pbsim_errors_ref> refs;
+  for (size_t r = 0; r < fm.recs.size(); r++) refs.push_back(pbsim_errors_ref{own_names[r].c_str(), fm.recs[r].lines, fm.recs[r].bytes});
+  std::vector<const char *> used;
+  if (have_names) {
+    char got[32], want[32];
+    snprintf(got, sizeof got, "%zu", names.size());
+    snprintf(want, sizeof want, "%zu", refs.size());
+    if (names.size() != refs.size()) die(" (apply-ref-names): %s names for %s genome records: the k-th name goes to the k-th record.", got, want);
+    for (const std::string &n : names) used.push_back(n.c_str());
+  }
+  struct Out {
+    FILE *fp = NULL;
+    bool write_failed = false;
+    const std::string *name = NULL;
+  } fasta, report, origin;
+  fasta.name = &out_name, report.name = &report_name, origin.name = &origin_name;
+  Out *outs[3] = {&fasta, &report, &origin};
+  auto drop = [&]() {
+    for (Out *x : outs)
+      if (!x->name->empty()) unlink(x->name->c_str());
+  };
+  for (Out *x : outs) {
+    if (x->name->empty()) continue;
+    x->fp = fopen(x->name->c_str(), "wb");
+    if (x->fp) continue;
+    for (Out *y : outs)
+      if (y->fp) fclose(y->fp), unlink(y->name->c_str());
+    die(": Cannot open output file: %s", x->name->c_str());
+  }
+  struct All {
+    Out *fasta, *report, *origin;
+  } all = {&fasta, &report, &origin};
+  pbsim_apply_opts opts = {(int32_t)haplotype, (int32_t)sample, (int32_t)lines, (int32_t)line_width, 0};
+  pbsim_apply_sink sink = {&all,
+                           [](void *u, const char *z, int64_t k, int64_t) {
+                             Out *x = ((All *)u)->fasta;
+                             if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
+                             return x->write_failed ? 0 : 1;
+                           },
+                           [](void *u, const char *z, int64_t k, int64_t) {
+                             Out *x = ((All *)u)->report;
+                             if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
+                             return x->write_failed ? 0 : 1;
+                           },
+                           NULL,
+                           [](void *u, int32_t, const int32_t *z, int64_t k) {
+                             Out *x = ((All *)u)->origin;
+                             if (fwrite(z, 4, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
+                             return x->write_failed ? 0 : 1;
+                           }};
+  if (!report.fp) sink.on_text = NULL;
+  if (!origin.fp) sink.on_origin = NULL;
+  pbsim_apply_result result;
+  const bool ok = pbsim_vcf_apply(ctx, refs.data(), (int)refs.size(), have_names ? used.data() : NULL, vcf.bytes, vcf.n, &opts, &sink, &result) != 0;
+  const Out *failed = NULL;
+  for (Out *x : outs) {
+    if (x->fp && fclose(x->fp) != 0) x->write_failed = true;
+    if (x->write_failed && !failed) failed = x;
+  }
+  if (!ok || failed) {
+    fprintf(stderr, "ERROR: %s\n", failed ? ("write error on " + *failed->name).c_str() : pbsim_last_error());
+    drop();
+    quit(-1);
+  }
+  std::string text((size_t)pbsim_apply_report(&result, NULL, 0), '\0');
+  pbsim_apply_report(&result, &text[0], (int64_t)text.size());
+  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
+  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
+  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
+  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int device) {
@@ -2005,6 +2184,8 @@ extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int
     if (!strcmp(argv[i], "--mutate-genome")) return mutate_genome_main(argc, argv, comm, device);
   for (int i = 1; i < argc; i++)
     if (!strcmp(argv[i], "--compare-vcf")) return compare_vcf_main(argc, argv, comm, device);
+  for (int i = 1; i < argc; i++)
+    if (!strcmp(argv[i], "--apply-vcf")) return apply_vcf_main(argc, argv, comm, device);
   if (argc >= 2 && !strcmp(argv[1], "--sort-truth-bam")) {
     // the standalone mode: no simulation, the named files sorted and indexed in place on one GPU
     if (comm && comm->world > 1) die(": --sort-truth-bam runs on one GPU.");

@@ -24,6 +24,7 @@
 //   pbsim --call-bam FILE [--call-bam FILE ..] --call-genome FASTA --call-out FILE   no simulation: the variants the aligned reads support, as VCF (cli.cpp)
 //   pbsim --mutate-genome FASTA --mutate-out FASTA --mutate-vcf FILE   no simulation: a variant genome and its truth variants drawn from a seed (cli.cpp)
 //   pbsim --compare-vcf CALLS --compare-truth TRUTH --compare-genome FASTA   no simulation: a call set scored against the truth variants (cli.cpp)
+//   pbsim --apply-vcf VCF --apply-genome FASTA --apply-out FASTA   no simulation: the lines of a VCF applied to the genome, per haplotype (cli.cpp)
 // Every rank runs the same pbsim_cli_main(argv): the job is deterministic in the values the ranks exchange, so they stay
 // in lockstep; rank 0 prints the report and creates the files, every rank writes its own byte ranges.
 #include <hip/hip_runtime.h>
@@ -94,13 +95,13 @@ int main(int argc, char **argv) {
     }
   }
   {
-    // --eval-bam, --depth-bam, --stats-bam, --errors-bam, --pileup-bam, --consensus-bam, --call-bam, --mutate-genome and --compare-vcf are modes of one GPU: the options that start several ranks are refused beside them
+    // --eval-bam, --depth-bam, --stats-bam, --errors-bam, --pileup-bam, --consensus-bam, --call-bam, --mutate-genome, --compare-vcf and --apply-vcf are modes of one GPU: the options that start several ranks are refused beside them
     const char *mode = nullptr;
     bool ranks = false;
     for (int i = 1; i < argc; i++) {
       if (!mode && (!strcmp(argv[i], "--eval-bam") || !strcmp(argv[i], "--depth-bam") || !strcmp(argv[i], "--stats-bam") || !strcmp(argv[i], "--errors-bam") ||
                     !strcmp(argv[i], "--pileup-bam") || !strcmp(argv[i], "--consensus-bam") || !strcmp(argv[i], "--call-bam") ||
-                    !strcmp(argv[i], "--mutate-genome") || !strcmp(argv[i], "--compare-vcf")))
+                    !strcmp(argv[i], "--mutate-genome") || !strcmp(argv[i], "--compare-vcf") || !strcmp(argv[i], "--apply-vcf")))
         mode = argv[i];
       for (const char *o : {"--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest"})
         if (!strcmp(argv[i], o) || (!strncmp(argv[i], o, strlen(o)) && argv[i][strlen(o)] == '=')) ranks = true;

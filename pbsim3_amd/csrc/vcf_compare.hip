@@ -32,6 +32,7 @@
 
 #include "bam_pileup_walk.h"
 #include "vcf_compare.h"
+#include "vcf_text.h"
 
 namespace pbsim {
 
@@ -40,31 +41,20 @@ namespace {
 using pilewalk::kThreads;
 using pilewalk::kWaves;
 using pilewalk::u64;
-using pilewalk::wave_scan;
+using vcftext::base_or_n;
+using vcftext::block_scan;
+using vcftext::digits;
+using vcftext::length_of;
+using vcftext::line_begins;
+using vcftext::put;
+using vcftext::put_span;
+using vcftext::upper;
 
 constexpr int kTileBlocksMax = 2048;  // workgroups of the line table's passes: they stride over the tiles of bytes
 constexpr int kLaneBlocksMax = 1024;  // of the parse, the match and the text's passes: they stride over the lines
 static_assert(kCmpTile == 4 * kThreads, "a lane takes four bytes of a tile");
 static_assert(kCmpTextTile == kThreads, "a tile of the text is one workgroup's lines");
 static_assert(sizeof(CmpLine) == 80, "the host sizes the table by it");
-
-// the exclusive prefix sum of v over the workgroup and *all, the workgroup's sum; every lane of the workgroup calls it
-__device__ __forceinline__ u64 block_scan(u64 v, u64 *sh_wave, int wave, int lane, u64 *all) {
-  const u64 incl = wave_scan(v, lane);
-  __syncthreads();  // (the values of the call before have been read)
-  if (lane == 63) sh_wave[wave] = incl;
-  __syncthreads();
-  u64 before = 0, sum = 0;
-  for (int w = 0; w < kWaves; w++) {
-    if (w < wave) before += sh_wave[w];
-    sum += sh_wave[w];
-  }
-  *all = sum;
-  return before + incl - v;
-}
-
-__device__ __forceinline__ uint32_t upper(uint32_t c) { return c >= 'a' && c <= 'z' ? c - 32u : c; }
-__device__ __forceinline__ bool base_or_n(uint32_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T' || c == 'N'; }
 
 // ---------------------------------------------------------------- the line table
 template <bool kFill>
@@ -75,17 +65,8 @@ __global__ __launch_bounds__(kThreads) void k_cmp_lines(CmpText t, const int64_t
     const int w = tile >= t.tiles0;
     const int64_t lo = w ? t.tiles0 * kCmpTile : 0, hi = lo + t.n[w];
     const int64_t i0 = tile * kCmpTile + (int64_t)tid * 4;
-    const uint32_t word = *(const uint32_t *)(t.bytes + i0);       // (the buffer is aligned, and 64 bytes longer than its tiles)
-    const uint32_t six[6] = {i0 > 0 ? t.bytes[i0 - 1] : (uint32_t)'\n', word & 255u, (word >> 8) & 255u, (word >> 16) & 255u, word >> 24, t.bytes[i0 + 4]};
     bool begins[4];
-    u64 n = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int64_t i = i0 + k;
-      const uint32_t prev = six[k], c = six[k + 1], next = six[k + 2];
-      begins[k] = i >= lo && i < hi && (i == lo || prev == '\n') && c != '#' && c != '\n' && !(c == '\r' && i + 1 < hi && next == '\n');
-      n += begins[k];
-    }
+    const u64 n = line_begins(t.bytes, i0, lo, hi, begins);  // (the buffer is aligned, and 64 bytes longer than its tiles)
     u64 all;
     const u64 before = block_scan(n, sh_wave, wave, lane, &all);
     if (!kFill) {
@@ -283,25 +264,6 @@ __global__ __launch_bounds__(kThreads) void k_cmp_match(CmpText t, CmpLine *line
 }
 
 // ---------------------------------------------------------------- tally and text
-__device__ __forceinline__ int digits(u64 x) {
-  int n = 1;
-  while (x >= 10) x /= 10, n++;
-  return n;
-}
-__device__ __forceinline__ char *put(char *o, u64 x) {
-  const int n = digits(x);
-  for (int k = n - 1; k >= 0; k--, x /= 10) o[k] = (char)('0' + x % 10);
-  return o + n;
-}
-__device__ __forceinline__ char *put(char *o, const char *s) {
-  while (*s) *o++ = *s++;
-  return o;
-}
-__device__ __forceinline__ char *put_span(char *o, const uint8_t *p, uint32_t n) {
-  if (n == 0) *o++ = '.';
-  for (uint32_t k = 0; k < n; k++) *o++ = (char)p[k];
-  return o;
-}
 __device__ __forceinline__ const char *type_name(int x) { return x == kCtSnv ? "snv" : x == kCtIns ? "ins" : x == kCtDel ? "del" : "complex"; }
 // the verdict of a compared line, else the class
 __device__ __forceinline__ const char *word_of(const CmpLine &l) {
@@ -316,11 +278,6 @@ __device__ __forceinline__ const char *word_of(const CmpLine &l) {
     default: break;
   }
   return l.verdict == kCvFound ? "found" : l.verdict == kCvMissed ? "missed" : l.verdict == kCvTp ? "tp" : l.verdict == kCvFpSite ? "fp_site" : "fp";
-}
-__device__ __forceinline__ int length_of(const char *s) {
-  int n = 0;
-  while (s[n]) n++;
-  return n;
 }
 
 template <bool kFill>
