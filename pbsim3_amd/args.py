@@ -100,51 +100,23 @@ def truth_sort(a):
     return how
 
 
-def eval_bam(argv):
-    """`pbsim --eval-bam MAPPED.bam --truth-bam FILE [--truth-bam FILE ...] [--truth-ref-names a,b,..] [--eval-overlap 0.1]
-    [--eval-out FILE]` -> dict(query, truth=[...], ref_names=None or [...], overlap, out=None or FILE): the stand-alone mode
-    that scores a mapper's BAM against truth BAMs (pbsim_truth_bam_eval).  --truth-bam repeats, so argv is walked and not
-    zipped into a dict.  What pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
-    takes = ("--eval-bam", "--truth-bam", "--truth-ref-names", "--eval-overlap", "--eval-out", "--device")
-    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
-    got = dict(query=None, truth=[], ref_names=None, overlap=0.1, out=None)
-    if any(a.split("=")[0] in ranks for a in argv):
-        raise ValueError("--eval-bam runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
-    i = 0
-    while i < len(argv):
-        a = argv[i]
-        if a not in takes:
-            raise ValueError("(%s): --eval-bam takes --truth-bam, --truth-ref-names, --eval-overlap, --eval-out and --device, and no other option." % a)
-        if i + 1 >= len(argv):
-            raise ValueError("(%s): the option needs a value." % a)
-        v = argv[i + 1]
-        i += 2
-        if a == "--eval-bam":
-            got["query"] = v
-        elif a == "--truth-bam":
-            got["truth"].append(v)
-        elif a == "--truth-ref-names":
-            got["ref_names"] = v.split(",")
-        elif a == "--eval-out":
-            got["out"] = v
-        elif a == "--eval-overlap":
-            try:
-                got["overlap"] = float(v)
-            except ValueError:
-                got["overlap"] = -1.0
-            if not 0.0 < got["overlap"] <= 1.0:
-                raise ValueError("(eval-overlap: %s): the least intersection / union of a correct mapping, in (0, 1]." % v)
-    if not got["query"]:
-        raise ValueError("--eval-bam MAPPED.bam: name the mapper's BAM file.")
-    if not got["truth"]:
-        raise ValueError("--eval-bam needs the truth: --truth-bam FILE [--truth-bam FILE ...] (the .aln.bam files of --truth-format bam).")
-    if got["ref_names"] is not None:
-        if len(got["ref_names"]) != len(got["truth"]):
-            raise ValueError("(truth-ref-names): %d names for %d --truth-bam files: the k-th name goes to the k-th file."
-                             % (len(got["ref_names"]), len(got["truth"])))
-        if "" in got["ref_names"]:
-            raise ValueError("(truth-ref-names): an empty name.")
-    return got
+# ---------------------------------------------------------------- the stand-alone modes
+# The mirror of csrc/cli_stages.cpp, laid out like it: every mode states its options as a table of rows, one walker goes through
+# argv in order, and the checks the modes share are written once.  A row is (option, kind, key of the returned dict, lo, hi, words):
+# row 0 is the option that selects the mode, the rows behind it stand in the order of the "takes" sentence, which is made from them;
+# --device belongs to every mode and has no row.  words: what a refused value is told behind "(name: value): ".
+TEXT, TEXTS, NAMES, WHOLE, FLAGS, CHOICE, SWITCH, HOOK = range(8)
+#   TEXT    a value                                   NAMES   a comma-separated list of names
+#   TEXTS   a value, and the option repeats           WHOLE   a whole number of lo .. hi
+#   FLAGS   the same, decimal or 0x hexadecimal       CHOICE  one of the two words lo and hi
+#   SWITCH  no value: the key is set to lo            HOOK    a value the mode reads itself: lo(got, v)
+_RANKS = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
+_MAPQ = "a whole number, 0 .. 255."
+_FLAG_WORDS = "decimal or 0x hexadecimal, 0 .. 65535."
+_DEPTH_WORDS = "a whole number, 0 .. 1000000000000."
+_MAX_INS = "a whole number, 1 .. 65535."
+_LINE_WIDTH = "a whole number, 0 .. 1048576 (0: one line per record)."
+_PPM = "a whole number, 0 .. 1000000."
 
 
 def _whole(v, base=10):
@@ -156,55 +128,99 @@ def _whole(v, base=10):
     return int(body, base)
 
 
+def _walk(argv, rows, got):
+    """argv in order into got: the first unknown option or bad value raises"""
+    mode = rows[0][0]
+    if any(a.split("=")[0] in _RANKS for a in argv):
+        raise ValueError("%s runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it." % mode)
+    by_name = {row[0]: row for row in rows}
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a not in by_name and a != "--device":
+            raise ValueError("(%s): %s takes %s and --device, and no other option." % (a, mode, ", ".join(row[0] for row in rows[1:])))
+        row = by_name.get(a)            # (None: --device, which is the front's and not the mode's)
+        kind, key, lo, hi, words = (row[1:] + (None,) * 3)[:5] if row else (None,) * 5
+        if kind == SWITCH:
+            got[key] = lo
+            i += 1
+            continue
+        if i + 1 >= len(argv):
+            raise ValueError("(%s): the option needs a value." % a)
+        v = argv[i + 1]
+        i += 2
+        refused = "(%s: %s): %s" % (a[2:], v, words)
+        if kind == TEXT:
+            got[key] = v
+        elif kind == TEXTS:
+            got[key].append(v)
+        elif kind == NAMES:
+            got[key] = v.split(",")
+        elif kind in (WHOLE, FLAGS):
+            n = _whole(v, 16 if kind == FLAGS and v[:2] in ("0x", "0X") else 10)
+            if n is None or not lo <= n <= hi:
+                raise ValueError(refused)
+            got[key] = n
+        elif kind == CHOICE:
+            if v not in (lo, hi):
+                raise ValueError(refused)
+            got[key] = v
+        elif kind == HOOK:
+            lo(got, v)
+    return got
+
+
+def _need_file_names(option, names, file_option, n_files):
+    if names is not None and len(names) != n_files:
+        raise ValueError("(%s): %d names for %d %s files: the k-th name goes to the k-th file." % (option, len(names), n_files, file_option))
+
+
+def _refuse_empty_name(option, names):
+    if names is not None and "" in names:
+        raise ValueError("(%s): an empty name." % option)
+
+
+def eval_bam(argv):
+    """`pbsim --eval-bam MAPPED.bam --truth-bam FILE [--truth-bam FILE ...] [--truth-ref-names a,b,..] [--eval-overlap 0.1]
+    [--eval-out FILE]` -> dict(query, truth=[...], ref_names=None or [...], overlap, out=None or FILE): the stand-alone mode
+    that scores a mapper's BAM against truth BAMs (pbsim_truth_bam_eval).  --truth-bam repeats, so argv is walked and not
+    zipped into a dict.  What pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
+    def overlap(got, v):
+        try:
+            got["overlap"] = float(v)
+        except ValueError:
+            got["overlap"] = -1.0
+        if not 0.0 < got["overlap"] <= 1.0:
+            raise ValueError("(eval-overlap: %s): the least intersection / union of a correct mapping, in (0, 1]." % v)
+    rows = (("--eval-bam", TEXT, "query"),
+            ("--truth-bam", TEXTS, "truth"),
+            ("--truth-ref-names", NAMES, "ref_names"),
+            ("--eval-overlap", HOOK, None, overlap),
+            ("--eval-out", TEXT, "out"))
+    got = _walk(argv, rows, dict(query=None, truth=[], ref_names=None, overlap=0.1, out=None))
+    if not got["query"]:
+        raise ValueError("--eval-bam MAPPED.bam: name the mapper's BAM file.")
+    if not got["truth"]:
+        raise ValueError("--eval-bam needs the truth: --truth-bam FILE [--truth-bam FILE ...] (the .aln.bam files of --truth-format bam).")
+    _need_file_names("truth-ref-names", got["ref_names"], "--truth-bam", len(got["truth"]))
+    _refuse_empty_name("truth-ref-names", got["ref_names"])
+    return got
+
+
 def depth_bam(argv):
     """`pbsim --depth-bam FILE --depth-out FILE [--depth-format bedgraph|window] [--depth-window N] [--depth-min-mapq Q]
     [--depth-exclude-flags F] [--depth-no-deletions]` -> dict(bam, out, format, window, min_mapq, exclude_flags, deletions): the
     stand-alone mode that writes the depth of coverage of a BAM (pbsim_bam_depth).  F is decimal or 0x hexadecimal.  What
     pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
-    takes = ("--depth-bam", "--depth-out", "--depth-format", "--depth-window", "--depth-min-mapq", "--depth-exclude-flags", "--device")
-    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
-    got = dict(bam=None, out=None, format="bedgraph", window=0, min_mapq=0, exclude_flags=0x704, deletions=True)
-    if any(a.split("=")[0] in ranks for a in argv):
-        raise ValueError("--depth-bam runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
-    have_window = False
-    i = 0
-    while i < len(argv):
-        a = argv[i]
-        if a == "--depth-no-deletions":
-            got["deletions"] = False
-            i += 1
-            continue
-        if a not in takes:
-            raise ValueError("(%s): --depth-bam takes --depth-out, --depth-format, --depth-window, --depth-min-mapq, --depth-exclude-flags, "
-                             "--depth-no-deletions and --device, and no other option." % a)
-        if i + 1 >= len(argv):
-            raise ValueError("(%s): the option needs a value." % a)
-        v = argv[i + 1]
-        i += 2
-        if a == "--depth-bam":
-            got["bam"] = v
-        elif a == "--depth-out":
-            got["out"] = v
-        elif a == "--depth-format":
-            if v not in ("bedgraph", "window"):
-                raise ValueError("(depth-format: %s): bedgraph or window." % v)
-            got["format"] = v
-        elif a == "--depth-window":
-            have_window = True
-            n = _whole(v)
-            if n is None or not 1 <= n < 2 ** 63:
-                raise ValueError("(depth-window: %s): a whole number of at least 1." % v)
-            got["window"] = n
-        elif a == "--depth-min-mapq":
-            n = _whole(v)
-            if n is None or n > 255:
-                raise ValueError("(depth-min-mapq: %s): a whole number, 0 .. 255." % v)
-            got["min_mapq"] = n
-        elif a == "--depth-exclude-flags":
-            n = _whole(v, 16 if v[:2] in ("0x", "0X") else 10)
-            if n is None or n > 65535:
-                raise ValueError("(depth-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535." % v)
-            got["exclude_flags"] = n
+    rows = (("--depth-bam", TEXT, "bam"),
+            ("--depth-out", TEXT, "out"),
+            ("--depth-format", CHOICE, "format", "bedgraph", "window", "bedgraph or window."),
+            ("--depth-window", WHOLE, "window", 1, 2 ** 63 - 1, "a whole number of at least 1."),
+            ("--depth-min-mapq", WHOLE, "min_mapq", 0, 255, _MAPQ),
+            ("--depth-exclude-flags", FLAGS, "exclude_flags", 0, 65535, _FLAG_WORDS),
+            ("--depth-no-deletions", SWITCH, "deletions", False))
+    got = _walk(argv, rows, dict(bam=None, out=None, format="bedgraph", window=0, min_mapq=0, exclude_flags=0x704, deletions=True))
+    have_window = got["window"] != 0            # (a window that was given is 1 or more)
     if not got["bam"]:
         raise ValueError("--depth-bam FILE: name the BAM file.")
     if not got["out"]:
@@ -220,36 +236,27 @@ def stats_bam(argv):
     """`pbsim --stats-bam FILE [--stats-bam FILE ...] [--stats-out FILE] [--stats-min-mapq Q] [--stats-exclude-flags F]` ->
     dict(bams, out, min_mapq, exclude_flags): the stand-alone mode that summarises the reads of BAM files (pbsim_bam_stats).  F
     is decimal or 0x hexadecimal.  What pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
-    takes = ("--stats-bam", "--stats-out", "--stats-min-mapq", "--stats-exclude-flags", "--device")
-    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
-    got = dict(bams=[], out=None, min_mapq=0, exclude_flags=0x900)
-    if any(a.split("=")[0] in ranks for a in argv):
-        raise ValueError("--stats-bam runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
-    i = 0
-    while i < len(argv):
-        a = argv[i]
-        if a not in takes:
-            raise ValueError("(%s): --stats-bam takes --stats-out, --stats-min-mapq, --stats-exclude-flags and --device, and no other option." % a)
-        if i + 1 >= len(argv):
-            raise ValueError("(%s): the option needs a value." % a)
-        v = argv[i + 1]
-        i += 2
-        if a == "--stats-bam":
-            got["bams"].append(v)
-        elif a == "--stats-out":
-            got["out"] = v
-        elif a == "--stats-min-mapq":
-            n = _whole(v)
-            if n is None or n > 255:
-                raise ValueError("(stats-min-mapq: %s): a whole number, 0 .. 255." % v)
-            got["min_mapq"] = n
-        elif a == "--stats-exclude-flags":
-            n = _whole(v, 16 if v[:2] in ("0x", "0X") else 10)
-            if n is None or n > 65535:
-                raise ValueError("(stats-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535." % v)
-            got["exclude_flags"] = n
+    rows = (("--stats-bam", TEXTS, "bams"),
+            ("--stats-out", TEXT, "out"),
+            ("--stats-min-mapq", WHOLE, "min_mapq", 0, 255, _MAPQ),
+            ("--stats-exclude-flags", FLAGS, "exclude_flags", 0, 65535, _FLAG_WORDS))
+    got = _walk(argv, rows, dict(bams=[], out=None, min_mapq=0, exclude_flags=0x900))
     if not got["bams"]:
         raise ValueError("--stats-bam FILE: name the BAM file.")
+    return got
+
+
+def _pile_checks(mode, got, needs_out=None):
+    """what the four modes that read aligned BAM files against their genome need and check alike; needs_out: what the mode says
+    when it must have --<mode>-out and has none"""
+    if not got["bams"]:
+        raise ValueError("--%s-bam FILE: name the BAM file." % mode)
+    if not got["genome"]:
+        raise ValueError("--%s-bam needs --%s-genome FASTA: the genome the reads were aligned to." % (mode, mode))
+    if needs_out and not got["out"]:
+        raise ValueError(needs_out)
+    _need_file_names(mode + "-ref-names", got["ref_names"], "--%s-bam" % mode, len(got["bams"]))
+    _refuse_empty_name(mode + "-ref-names", got["ref_names"])
     return got
 
 
@@ -258,50 +265,13 @@ def errors_bam(argv):
     [--errors-min-mapq Q] [--errors-exclude-flags F]` -> dict(bams, genome, ref_names, out, min_mapq, exclude_flags): the stand-alone
     mode that profiles the errors of aligned reads against their genome (pbsim_bam_errors).  F is decimal or 0x hexadecimal.  What
     pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
-    takes = ("--errors-bam", "--errors-genome", "--errors-ref-names", "--errors-out", "--errors-min-mapq", "--errors-exclude-flags", "--device")
-    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
-    got = dict(bams=[], genome=None, ref_names=None, out=None, min_mapq=0, exclude_flags=0x900)
-    if any(a.split("=")[0] in ranks for a in argv):
-        raise ValueError("--errors-bam runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
-    i = 0
-    while i < len(argv):
-        a = argv[i]
-        if a not in takes:
-            raise ValueError("(%s): --errors-bam takes --errors-genome, --errors-ref-names, --errors-out, --errors-min-mapq, --errors-exclude-flags "
-                             "and --device, and no other option." % a)
-        if i + 1 >= len(argv):
-            raise ValueError("(%s): the option needs a value." % a)
-        v = argv[i + 1]
-        i += 2
-        if a == "--errors-bam":
-            got["bams"].append(v)
-        elif a == "--errors-genome":
-            got["genome"] = v
-        elif a == "--errors-ref-names":
-            got["ref_names"] = v.split(",")
-        elif a == "--errors-out":
-            got["out"] = v
-        elif a == "--errors-min-mapq":
-            n = _whole(v)
-            if n is None or n > 255:
-                raise ValueError("(errors-min-mapq: %s): a whole number, 0 .. 255." % v)
-            got["min_mapq"] = n
-        elif a == "--errors-exclude-flags":
-            n = _whole(v, 16 if v[:2] in ("0x", "0X") else 10)
-            if n is None or n > 65535:
-                raise ValueError("(errors-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535." % v)
-            got["exclude_flags"] = n
-    if not got["bams"]:
-        raise ValueError("--errors-bam FILE: name the BAM file.")
-    if not got["genome"]:
-        raise ValueError("--errors-bam needs --errors-genome FASTA: the genome the reads were aligned to.")
-    if got["ref_names"] is not None:
-        if len(got["ref_names"]) != len(got["bams"]):
-            raise ValueError("(errors-ref-names): %d names for %d --errors-bam files: the k-th name goes to the k-th file."
-                             % (len(got["ref_names"]), len(got["bams"])))
-        if "" in got["ref_names"]:
-            raise ValueError("(errors-ref-names): an empty name.")
-    return got
+    rows = (("--errors-bam", TEXTS, "bams"),
+            ("--errors-genome", TEXT, "genome"),
+            ("--errors-ref-names", NAMES, "ref_names"),
+            ("--errors-out", TEXT, "out"),
+            ("--errors-min-mapq", WHOLE, "min_mapq", 0, 255, _MAPQ),
+            ("--errors-exclude-flags", FLAGS, "exclude_flags", 0, 65535, _FLAG_WORDS))
+    return _pile_checks("errors", _walk(argv, rows, dict(bams=[], genome=None, ref_names=None, out=None, min_mapq=0, exclude_flags=0x900)))
 
 
 def pileup_bam(argv):
@@ -309,55 +279,15 @@ def pileup_bam(argv):
     [--pileup-format sites|all] [--pileup-min-mapq N] [--pileup-min-baseq N] [--pileup-min-depth N]` -> dict(bams, genome, ref_names,
     out, fmt, min_mapq, min_baseq, min_depth): the stand-alone mode that piles the aligned reads up against their genome
     (pbsim_bam_pileup).  What pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
-    takes = ("--pileup-bam", "--pileup-genome", "--pileup-ref-names", "--pileup-out", "--pileup-format", "--pileup-min-mapq", "--pileup-min-baseq",
-             "--pileup-min-depth", "--device")
-    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
-    got = dict(bams=[], genome=None, ref_names=None, out=None, fmt="sites", min_mapq=0, min_baseq=0, min_depth=1)
-    if any(a.split("=")[0] in ranks for a in argv):
-        raise ValueError("--pileup-bam runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
-    i = 0
-    while i < len(argv):
-        a = argv[i]
-        if a not in takes:
-            raise ValueError("(%s): --pileup-bam takes --pileup-genome, --pileup-ref-names, --pileup-out, --pileup-format, --pileup-min-mapq, "
-                             "--pileup-min-baseq, --pileup-min-depth and --device, and no other option." % a)
-        if i + 1 >= len(argv):
-            raise ValueError("(%s): the option needs a value." % a)
-        v = argv[i + 1]
-        i += 2
-        if a == "--pileup-bam":
-            got["bams"].append(v)
-        elif a == "--pileup-genome":
-            got["genome"] = v
-        elif a == "--pileup-ref-names":
-            got["ref_names"] = v.split(",")
-        elif a == "--pileup-out":
-            got["out"] = v
-        elif a == "--pileup-format":
-            if v not in ("sites", "all"):
-                raise ValueError("(pileup-format: %s): sites or all." % v)
-            got["fmt"] = v
-        elif a in ("--pileup-min-mapq", "--pileup-min-baseq"):
-            n = _whole(v)
-            if n is None or n > 255:
-                raise ValueError("(%s: %s): a whole number, 0 .. 255." % (a[2:], v))
-            got[a[9:].replace("-", "_")] = n
-        elif a == "--pileup-min-depth":
-            n = _whole(v)
-            if n is None or n > 1000000000000:
-                raise ValueError("(pileup-min-depth: %s): a whole number, 0 .. 1000000000000." % v)
-            got["min_depth"] = n
-    if not got["bams"]:
-        raise ValueError("--pileup-bam FILE: name the BAM file.")
-    if not got["genome"]:
-        raise ValueError("--pileup-bam needs --pileup-genome FASTA: the genome the reads were aligned to.")
-    if got["ref_names"] is not None:
-        if len(got["ref_names"]) != len(got["bams"]):
-            raise ValueError("(pileup-ref-names): %d names for %d --pileup-bam files: the k-th name goes to the k-th file."
-                             % (len(got["ref_names"]), len(got["bams"])))
-        if "" in got["ref_names"]:
-            raise ValueError("(pileup-ref-names): an empty name.")
-    return got
+    rows = (("--pileup-bam", TEXTS, "bams"),
+            ("--pileup-genome", TEXT, "genome"),
+            ("--pileup-ref-names", NAMES, "ref_names"),
+            ("--pileup-out", TEXT, "out"),
+            ("--pileup-format", CHOICE, "fmt", "sites", "all", "sites or all."),
+            ("--pileup-min-mapq", WHOLE, "min_mapq", 0, 255, _MAPQ),
+            ("--pileup-min-baseq", WHOLE, "min_baseq", 0, 255, _MAPQ),
+            ("--pileup-min-depth", WHOLE, "min_depth", 0, 1000000000000, _DEPTH_WORDS))
+    return _pile_checks("pileup", _walk(argv, rows, dict(bams=[], genome=None, ref_names=None, out=None, fmt="sites", min_mapq=0, min_baseq=0, min_depth=1)))
 
 
 def consensus_bam(argv):
@@ -366,74 +296,20 @@ def consensus_bam(argv):
     [--consensus-max-ins N] [--consensus-line-width N]` -> dict(bams, genome, ref_names, out, min_mapq, min_baseq, min_depth,
     exclude_flags, fill, max_ins, line_width): the stand-alone mode that writes the consensus FASTA of the aligned reads
     (pbsim_bam_consensus).  What pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
-    takes = ("--consensus-bam", "--consensus-genome", "--consensus-ref-names", "--consensus-out", "--consensus-min-mapq", "--consensus-min-baseq",
-             "--consensus-min-depth", "--consensus-exclude-flags", "--consensus-fill", "--consensus-max-ins", "--consensus-line-width", "--device")
-    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
-    got = dict(bams=[], genome=None, ref_names=None, out=None, min_mapq=0, min_baseq=0, min_depth=1, exclude_flags=0x900, fill="n", max_ins=1024,
-               line_width=60)
-    if any(a.split("=")[0] in ranks for a in argv):
-        raise ValueError("--consensus-bam runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
-    i = 0
-    while i < len(argv):
-        a = argv[i]
-        if a not in takes:
-            raise ValueError("(%s): --consensus-bam takes --consensus-genome, --consensus-out, --consensus-ref-names, --consensus-min-mapq, "
-                             "--consensus-min-baseq, --consensus-min-depth, --consensus-exclude-flags, --consensus-fill, --consensus-max-ins, "
-                             "--consensus-line-width and --device, and no other option." % a)
-        if i + 1 >= len(argv):
-            raise ValueError("(%s): the option needs a value." % a)
-        v = argv[i + 1]
-        i += 2
-        if a == "--consensus-bam":
-            got["bams"].append(v)
-        elif a == "--consensus-genome":
-            got["genome"] = v
-        elif a == "--consensus-ref-names":
-            got["ref_names"] = v.split(",")
-        elif a == "--consensus-out":
-            got["out"] = v
-        elif a == "--consensus-fill":
-            if v not in ("n", "ref"):
-                raise ValueError("(consensus-fill: %s): n or ref." % v)
-            got["fill"] = v
-        elif a == "--consensus-exclude-flags":
-            n = _whole(v, 16 if v[:2] in ("0x", "0X") else 10)
-            if n is None or n > 65535:
-                raise ValueError("(consensus-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535." % v)
-            got["exclude_flags"] = n
-        elif a in ("--consensus-min-mapq", "--consensus-min-baseq"):
-            n = _whole(v)
-            if n is None or n > 255:
-                raise ValueError("(%s: %s): a whole number, 0 .. 255." % (a[2:], v))
-            got[a[12:].replace("-", "_")] = n
-        elif a == "--consensus-min-depth":
-            n = _whole(v)
-            if n is None or n > 1000000000000:
-                raise ValueError("(consensus-min-depth: %s): a whole number, 0 .. 1000000000000." % v)
-            got["min_depth"] = n
-        elif a == "--consensus-max-ins":
-            n = _whole(v)
-            if n is None or not 1 <= n <= 65535:
-                raise ValueError("(consensus-max-ins: %s): a whole number, 1 .. 65535." % v)
-            got["max_ins"] = n
-        elif a == "--consensus-line-width":
-            n = _whole(v)
-            if n is None or n > 1048576:
-                raise ValueError("(consensus-line-width: %s): a whole number, 0 .. 1048576 (0: one line per record)." % v)
-            got["line_width"] = n
-    if not got["bams"]:
-        raise ValueError("--consensus-bam FILE: name the BAM file.")
-    if not got["genome"]:
-        raise ValueError("--consensus-bam needs --consensus-genome FASTA: the genome the reads were aligned to.")
-    if not got["out"]:
-        raise ValueError("--consensus-bam needs --consensus-out FILE: where the consensus FASTA goes.")
-    if got["ref_names"] is not None:
-        if len(got["ref_names"]) != len(got["bams"]):
-            raise ValueError("(consensus-ref-names): %d names for %d --consensus-bam files: the k-th name goes to the k-th file."
-                             % (len(got["ref_names"]), len(got["bams"])))
-        if "" in got["ref_names"]:
-            raise ValueError("(consensus-ref-names): an empty name.")
-    return got
+    rows = (("--consensus-bam", TEXTS, "bams"),
+            ("--consensus-genome", TEXT, "genome"),
+            ("--consensus-out", TEXT, "out"),
+            ("--consensus-ref-names", NAMES, "ref_names"),
+            ("--consensus-min-mapq", WHOLE, "min_mapq", 0, 255, _MAPQ),
+            ("--consensus-min-baseq", WHOLE, "min_baseq", 0, 255, _MAPQ),
+            ("--consensus-min-depth", WHOLE, "min_depth", 0, 1000000000000, _DEPTH_WORDS),
+            ("--consensus-exclude-flags", FLAGS, "exclude_flags", 0, 65535, _FLAG_WORDS),
+            ("--consensus-fill", CHOICE, "fill", "n", "ref", "n or ref."),
+            ("--consensus-max-ins", WHOLE, "max_ins", 1, 65535, _MAX_INS),
+            ("--consensus-line-width", WHOLE, "line_width", 0, 1048576, _LINE_WIDTH))
+    got = _walk(argv, rows, dict(bams=[], genome=None, ref_names=None, out=None, min_mapq=0, min_baseq=0, min_depth=1, exclude_flags=0x900, fill="n",
+                                 max_ins=1024, line_width=60))
+    return _pile_checks("consensus", got, "--consensus-bam needs --consensus-out FILE: where the consensus FASTA goes.")
 
 
 def call_bam(argv):
@@ -441,63 +317,17 @@ def call_bam(argv):
     [--call-min-baseq N] [--call-min-depth N] [--call-exclude-flags F] [--call-max-ins N]` -> dict(bams, genome, ref_names, out,
     min_mapq, min_baseq, min_depth, exclude_flags, max_ins): the stand-alone mode that writes the variants the aligned reads support
     as VCF (pbsim_bam_call).  What pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
-    takes = ("--call-bam", "--call-genome", "--call-ref-names", "--call-out", "--call-min-mapq", "--call-min-baseq", "--call-min-depth",
-             "--call-exclude-flags", "--call-max-ins", "--device")
-    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
-    got = dict(bams=[], genome=None, ref_names=None, out=None, min_mapq=0, min_baseq=0, min_depth=1, exclude_flags=0x900, max_ins=1024)
-    if any(a.split("=")[0] in ranks for a in argv):
-        raise ValueError("--call-bam runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
-    i = 0
-    while i < len(argv):
-        a = argv[i]
-        if a not in takes:
-            raise ValueError("(%s): --call-bam takes --call-genome, --call-out, --call-ref-names, --call-min-mapq, --call-min-baseq, --call-min-depth, "
-                             "--call-exclude-flags, --call-max-ins and --device, and no other option." % a)
-        if i + 1 >= len(argv):
-            raise ValueError("(%s): the option needs a value." % a)
-        v = argv[i + 1]
-        i += 2
-        if a == "--call-bam":
-            got["bams"].append(v)
-        elif a == "--call-genome":
-            got["genome"] = v
-        elif a == "--call-ref-names":
-            got["ref_names"] = v.split(",")
-        elif a == "--call-out":
-            got["out"] = v
-        elif a == "--call-exclude-flags":
-            n = _whole(v, 16 if v[:2] in ("0x", "0X") else 10)
-            if n is None or n > 65535:
-                raise ValueError("(call-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535." % v)
-            got["exclude_flags"] = n
-        elif a in ("--call-min-mapq", "--call-min-baseq"):
-            n = _whole(v)
-            if n is None or n > 255:
-                raise ValueError("(%s: %s): a whole number, 0 .. 255." % (a[2:], v))
-            got[a[7:].replace("-", "_")] = n
-        elif a == "--call-min-depth":
-            n = _whole(v)
-            if n is None or n > 1000000000000:
-                raise ValueError("(call-min-depth: %s): a whole number, 0 .. 1000000000000." % v)
-            got["min_depth"] = n
-        elif a == "--call-max-ins":
-            n = _whole(v)
-            if n is None or not 1 <= n <= 65535:
-                raise ValueError("(call-max-ins: %s): a whole number, 1 .. 65535." % v)
-            got["max_ins"] = n
-    if not got["bams"]:
-        raise ValueError("--call-bam FILE: name the BAM file.")
-    if not got["genome"]:
-        raise ValueError("--call-bam needs --call-genome FASTA: the genome the reads were aligned to.")
-    if not got["out"]:
-        raise ValueError("--call-bam needs --call-out FILE: where the VCF goes.")
-    if got["ref_names"] is not None:
-        if len(got["ref_names"]) != len(got["bams"]):
-            raise ValueError("(call-ref-names): %d names for %d --call-bam files: the k-th name goes to the k-th file."
-                             % (len(got["ref_names"]), len(got["bams"])))
-        if "" in got["ref_names"]:
-            raise ValueError("(call-ref-names): an empty name.")
-    return got
+    rows = (("--call-bam", TEXTS, "bams"),
+            ("--call-genome", TEXT, "genome"),
+            ("--call-out", TEXT, "out"),
+            ("--call-ref-names", NAMES, "ref_names"),
+            ("--call-min-mapq", WHOLE, "min_mapq", 0, 255, _MAPQ),
+            ("--call-min-baseq", WHOLE, "min_baseq", 0, 255, _MAPQ),
+            ("--call-min-depth", WHOLE, "min_depth", 0, 1000000000000, _DEPTH_WORDS),
+            ("--call-exclude-flags", FLAGS, "exclude_flags", 0, 65535, _FLAG_WORDS),
+            ("--call-max-ins", WHOLE, "max_ins", 1, 65535, _MAX_INS))
+    got = _walk(argv, rows, dict(bams=[], genome=None, ref_names=None, out=None, min_mapq=0, min_baseq=0, min_depth=1, exclude_flags=0x900, max_ins=1024))
+    return _pile_checks("call", got, "--call-bam needs --call-out FILE: where the VCF goes.")
 
 
 def mutate_genome(argv):
@@ -505,49 +335,17 @@ def mutate_genome(argv):
     [--mutate-del-ppm N] [--mutate-ext-ppm N] [--mutate-max-indel N] [--mutate-line-width N]` -> dict(genome, out, vcf, seed, snv_ppm,
     ins_ppm, del_ppm, ext_ppm, max_indel, line_width): the stand-alone mode that draws a variant genome and its truth VCF
     (pbsim_genome_mutate).  What pbsim_cli_main refuses from the command line alone raises ValueError with its message."""
-    takes = ("--mutate-genome", "--mutate-out", "--mutate-vcf", "--mutate-seed", "--mutate-snv-ppm", "--mutate-ins-ppm", "--mutate-del-ppm",
-             "--mutate-ext-ppm", "--mutate-max-indel", "--mutate-line-width", "--device")
-    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
-    got = dict(genome=None, out=None, vcf=None, seed=1, snv_ppm=1000, ins_ppm=100, del_ppm=100, ext_ppm=500000, max_indel=50, line_width=60)
-    if any(a.split("=")[0] in ranks for a in argv):
-        raise ValueError("--mutate-genome runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
-    i = 0
-    while i < len(argv):
-        a = argv[i]
-        if a not in takes:
-            raise ValueError("(%s): --mutate-genome takes --mutate-out, --mutate-vcf, --mutate-seed, --mutate-snv-ppm, --mutate-ins-ppm, "
-                             "--mutate-del-ppm, --mutate-ext-ppm, --mutate-max-indel, --mutate-line-width and --device, and no other option." % a)
-        if i + 1 >= len(argv):
-            raise ValueError("(%s): the option needs a value." % a)
-        v = argv[i + 1]
-        i += 2
-        if a in ("--mutate-genome", "--mutate-out", "--mutate-vcf"):
-            got[a[9:]] = v
-        elif a == "--mutate-seed":
-            n = _whole(v)
-            if n is None or n > 4294967295:
-                raise ValueError("(mutate-seed: %s): a whole number, 0 .. 4294967295." % v)
-            got["seed"] = n
-        elif a in ("--mutate-snv-ppm", "--mutate-ins-ppm", "--mutate-del-ppm"):
-            n = _whole(v)
-            if n is None or n > 1000000:
-                raise ValueError("(%s: %s): a whole number, 0 .. 1000000." % (a[2:], v))
-            got[a[9:].replace("-", "_")] = n
-        elif a == "--mutate-ext-ppm":
-            n = _whole(v)
-            if n is None or n > 999999:
-                raise ValueError("(mutate-ext-ppm: %s): a whole number, 0 .. 999999." % v)
-            got["ext_ppm"] = n
-        elif a == "--mutate-max-indel":
-            n = _whole(v)
-            if n is None or not 1 <= n <= 65535:
-                raise ValueError("(mutate-max-indel: %s): a whole number, 1 .. 65535." % v)
-            got["max_indel"] = n
-        elif a == "--mutate-line-width":
-            n = _whole(v)
-            if n is None or n > 1048576:
-                raise ValueError("(mutate-line-width: %s): a whole number, 0 .. 1048576 (0: one line per record)." % v)
-            got["line_width"] = n
+    rows = (("--mutate-genome", TEXT, "genome"),
+            ("--mutate-out", TEXT, "out"),
+            ("--mutate-vcf", TEXT, "vcf"),
+            ("--mutate-seed", WHOLE, "seed", 0, 4294967295, "a whole number, 0 .. 4294967295."),
+            ("--mutate-snv-ppm", WHOLE, "snv_ppm", 0, 1000000, _PPM),
+            ("--mutate-ins-ppm", WHOLE, "ins_ppm", 0, 1000000, _PPM),
+            ("--mutate-del-ppm", WHOLE, "del_ppm", 0, 1000000, _PPM),
+            ("--mutate-ext-ppm", WHOLE, "ext_ppm", 0, 999999, "a whole number, 0 .. 999999."),
+            ("--mutate-max-indel", WHOLE, "max_indel", 1, 65535, _MAX_INS),
+            ("--mutate-line-width", WHOLE, "line_width", 0, 1048576, _LINE_WIDTH))
+    got = _walk(argv, rows, dict(genome=None, out=None, vcf=None, seed=1, snv_ppm=1000, ins_ppm=100, del_ppm=100, ext_ppm=500000, max_indel=50, line_width=60))
     if not got["genome"]:
         raise ValueError("--mutate-genome FASTA: name the genome.")
     if not got["out"]:
@@ -564,45 +362,21 @@ def compare_vcf(argv):
     [--compare-min-ms N] [--compare-ref-names a,b,..]` -> dict(calls, truth, genome, out, lines, min_ms, ref_names): the stand-alone
     mode that scores a call set against the truth variants (pbsim_vcf_compare).  What pbsim_cli_main refuses from the command line
     alone raises ValueError with its message."""
-    takes = ("--compare-vcf", "--compare-truth", "--compare-genome", "--compare-out", "--compare-lines", "--compare-min-ms", "--compare-ref-names",
-             "--device")
-    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
-    got = dict(calls=None, truth=None, genome=None, out=None, lines="discordant", min_ms=0, ref_names=None)
-    if any(a.split("=")[0] in ranks for a in argv):
-        raise ValueError("--compare-vcf runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
-    i = 0
-    while i < len(argv):
-        a = argv[i]
-        if a not in takes:
-            raise ValueError("(%s): --compare-vcf takes --compare-truth, --compare-genome, --compare-out, --compare-lines, --compare-min-ms, "
-                             "--compare-ref-names and --device, and no other option." % a)
-        if i + 1 >= len(argv):
-            raise ValueError("(%s): the option needs a value." % a)
-        v = argv[i + 1]
-        i += 2
-        if a == "--compare-vcf":
-            got["calls"] = v
-        elif a in ("--compare-truth", "--compare-genome", "--compare-out"):
-            got[a[10:]] = v
-        elif a == "--compare-ref-names":
-            got["ref_names"] = v.split(",")
-        elif a == "--compare-lines":
-            if v not in ("discordant", "all"):
-                raise ValueError("(compare-lines: %s): discordant or all." % v)
-            got["lines"] = v
-        elif a == "--compare-min-ms":
-            n = _whole(v)
-            if n is None or n > 2147483647:
-                raise ValueError("(compare-min-ms: %s): a whole number, 0 .. 2147483647." % v)
-            got["min_ms"] = n
+    rows = (("--compare-vcf", TEXT, "calls"),
+            ("--compare-truth", TEXT, "truth"),
+            ("--compare-genome", TEXT, "genome"),
+            ("--compare-out", TEXT, "out"),
+            ("--compare-lines", CHOICE, "lines", "discordant", "all", "discordant or all."),
+            ("--compare-min-ms", WHOLE, "min_ms", 0, 2147483647, "a whole number, 0 .. 2147483647."),
+            ("--compare-ref-names", NAMES, "ref_names"))
+    got = _walk(argv, rows, dict(calls=None, truth=None, genome=None, out=None, lines="discordant", min_ms=0, ref_names=None))
     if not got["calls"]:
         raise ValueError("--compare-vcf CALLS: name the call set.")
     if not got["truth"]:
         raise ValueError("--compare-vcf needs --compare-truth VCF: the truth variants.")
     if not got["genome"]:
         raise ValueError("--compare-vcf needs --compare-genome FASTA: the genome both files speak of.")
-    if got["ref_names"] is not None and "" in got["ref_names"]:
-        raise ValueError("(compare-ref-names): an empty name.")
+    _refuse_empty_name("compare-ref-names", got["ref_names"])
     return got
 
 
@@ -612,51 +386,28 @@ def apply_vcf(argv):
     ref_names, haplotype, sample, report, lines, line_width, origin): the stand-alone mode that applies the lines of a VCF to a genome
     (pbsim_vcf_apply); sample is a column (int) or a name (str).  What pbsim_cli_main refuses from the command line alone raises
     ValueError with its message."""
-    takes = ("--apply-vcf", "--apply-genome", "--apply-out", "--apply-ref-names", "--apply-haplotype", "--apply-sample", "--apply-report",
-             "--apply-lines", "--apply-line-width", "--apply-origin", "--device")
-    ranks = ("--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest")
-    got = dict(vcf=None, genome=None, out=None, ref_names=None, haplotype=0, sample=0, report=None, lines="discordant", line_width=60, origin=None)
-    if any(a.split("=")[0] in ranks for a in argv):
-        raise ValueError("--apply-vcf runs on one GPU (--device N): no --devices / --processes / --rank / --world / --rendezvous / --comm beside it.")
-    i = 0
-    while i < len(argv):
-        a = argv[i]
-        if a not in takes:
-            raise ValueError("(%s): --apply-vcf takes --apply-genome, --apply-out, --apply-ref-names, --apply-haplotype, --apply-sample, "
-                             "--apply-report, --apply-lines, --apply-line-width, --apply-origin and --device, and no other option." % a)
-        if i + 1 >= len(argv):
-            raise ValueError("(%s): the option needs a value." % a)
-        v = argv[i + 1]
-        i += 2
-        if a in ("--apply-vcf", "--apply-genome", "--apply-out", "--apply-report", "--apply-origin"):
-            got[a[8:]] = v
-        elif a == "--apply-ref-names":
-            got["ref_names"] = v.split(",")
-        elif a == "--apply-haplotype":
-            n = _whole(v)
-            if n is None or n > 2:
-                raise ValueError("(apply-haplotype: %s): 0 (the first ALT of every line), 1 or 2." % v)
-            got["haplotype"] = n
-        elif a == "--apply-sample":
-            if not v:
-                raise ValueError("(apply-sample): a 0-based sample column or a sample's name.")
-            n = _whole(v)
-            got["sample"] = v if n is None or n > 2147483647 else n
-        elif a == "--apply-lines":
-            if v not in ("discordant", "all"):
-                raise ValueError("(apply-lines: %s): discordant or all." % v)
-            got["lines"] = v
-        elif a == "--apply-line-width":
-            n = _whole(v)
-            if n is None or n > 1048576:
-                raise ValueError("(apply-line-width: %s): a whole number, 0 .. 1048576 (0: one line per record)." % v)
-            got["line_width"] = n
+    def sample(got, v):
+        if not v:
+            raise ValueError("(apply-sample): a 0-based sample column or a sample's name.")
+        n = _whole(v)
+        got["sample"] = v if n is None or n > 2147483647 else n
+    rows = (("--apply-vcf", TEXT, "vcf"),
+            ("--apply-genome", TEXT, "genome"),
+            ("--apply-out", TEXT, "out"),
+            ("--apply-ref-names", NAMES, "ref_names"),
+            ("--apply-haplotype", WHOLE, "haplotype", 0, 2, "0 (the first ALT of every line), 1 or 2."),
+            ("--apply-sample", HOOK, None, sample),
+            ("--apply-report", TEXT, "report"),
+            ("--apply-lines", CHOICE, "lines", "discordant", "all", "discordant or all."),
+            ("--apply-line-width", WHOLE, "line_width", 0, 1048576, _LINE_WIDTH),
+            ("--apply-origin", TEXT, "origin"))
+    got = _walk(argv, rows, dict(vcf=None, genome=None, out=None, ref_names=None, haplotype=0, sample=0, report=None, lines="discordant", line_width=60,
+                                 origin=None))
     if not got["vcf"]:
         raise ValueError("--apply-vcf VCF: name the variants.")
     if not got["genome"]:
         raise ValueError("--apply-vcf needs --apply-genome FASTA: the genome the file speaks of.")
     if not got["out"]:
         raise ValueError("--apply-vcf needs --apply-out FASTA: where the spliced genome goes.")
-    if got["ref_names"] is not None and "" in got["ref_names"]:
-        raise ValueError("(apply-ref-names): an empty name.")
+    _refuse_empty_name("apply-ref-names", got["ref_names"])
     return got

@@ -1,6 +1,6 @@
 // bam_consensus.cpp -- pbsim_bam_consensus: the consensus FASTA of the aligned reads of BAM files against their genome (the rule:
 // include/pbsim3_amd.h, tests/consensus_model.py).  The host's part has the flow of pbsim_bam_pileup (bam_pileup.cpp): the genome
-// into HBM, the table zeroed, then per file its front half (bam_pileup_front.h) and the column pass, which here also logs the
+// into HBM, the table zeroed, then per file its front half (bam_file_front.h) and the column pass, which here also logs the
 // inserted bases of the anchored I ops; the logs outlive their files, the streams do not.  Then once the site pass; the ins_sites
 // compacted into slots, the logs tallied into the slots' cells; the base pass, the FASTA and its way to the sink.  The kernels are
 // bam_errors.hip's, bam_pileup.hip's and bam_consensus.hip's.  Everything up to the base pass's first half is consensus_front
@@ -17,7 +17,7 @@
 #include "bam_consensus.h"
 #include "bam_consensus_front.h"
 #include "bam_genome.h"
-#include "bam_pileup_front.h"
+#include "bam_file_front.h"
 #include "kernels.h"
 
 namespace pbsim {
@@ -65,8 +65,8 @@ int consensus_front(pbsim_ctx *c, const BamStage &stage, BamPhases &ph, const pb
   int64_t &n_all = fr.n_all, &inflated = fr.inflated, &segments = fr.segments, &logged = fr.logged;
   std::deque<FileLog> logs;
   for (int f = 0; f < n_files; f++) {
-    PileFile pf;
-    if (!pileup_file_front(c, stage, ph, refs, n_refs, genome, files, f, n_files, exclude_flags, min_mapq, cells, &pf)) return PBSIM_FAILED;
+    BamFileFront pf;
+    if (!bam_file_front(c, stage, ph, refs, n_refs, genome, files, f, n_files, exclude_flags, min_mapq, cells, false, &pf)) return PBSIM_FAILED;
     inflated += pf.s.N, n_all += pf.n_rec, segments += pf.n_seg;
     if (pf.n_seg > 0) {
       // the log, sized from the CIGAR sums of the scored records: every inserted base can leave one entry

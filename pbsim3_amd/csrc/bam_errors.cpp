@@ -1,6 +1,7 @@
 // bam_errors.cpp -- pbsim_bam_errors: the error profile of the aligned reads of BAM files against their genome (the rule:
-// include/pbsim3_amd.h, tests/errors_model.py).  The host's part: the genome into HBM (bam_genome.cpp), each file's stream and
-// its records (bam_stream.cpp), the references by name (bam_errors_rule.cpp), the buffers, and the text's way to the sink
+// include/pbsim3_amd.h, tests/errors_model.py).  The host's part: the genome into HBM (bam_genome.cpp), per file the front half
+// it shares with the pileup and the consensus stages (bam_file_front.h: the stream, its records, the references by name, the
+// record pass, the segments), here with the records' column counts, then the column pass, the reads and the text's way to the sink
 // (bam_genome.cpp); the kernels are inflate.hip's, bam_scan.hip's and bam_errors.hip's.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "bam_errors.h"
+#include "bam_file_front.h"
 #include "bam_genome.h"
 #include "bam_scan.h"
 #include "bam_stream.h"
@@ -44,88 +46,17 @@ int errors_bam(pbsim_ctx *c, const pbsim_errors_ref *refs, int n_refs, const pbs
   std::deque<FileText> texts;
   int64_t n_all = 0, inflated = 0, n_text = 0, segments = 0;
   for (int f = 0; f < n_files; f++) {
-    // ---- 1. the stream into HBM, and its records
-    BamStream s;
-    s.a_what = "a file";
-    if (n_files > 1) s.what = "file " + std::to_string(f);
-    const std::string where = kStage.who + s.what + (s.what.empty() ? "" : ": ");
-    if (!bam_inflate_stream(c, kStage, (const uint8_t *)files[f].bam, files[f].n, &s)) return PBSIM_FAILED;
-    ph.mark("inflate");
-    {
-      BamScan scan;
-      if (!bam_locate(c, kStage, &s, &scan, kBamScanAny, kBamSamplePacking)) return PBSIM_FAILED;
-    }
-    ph.mark("locate");
-    const int64_t n_rec = (int64_t)s.rec.size();
-    inflated += s.N;
-    n_all += n_rec;
-    if (n_rec >= ((int64_t)1 << 32) - 1) return fail(where + std::to_string(n_rec) + " records: a file of 2^32 - 1 records or more is not taken (a segment names its record in 32 bits)");
-    // ---- 2. its references, by name
-    std::vector<int32_t> map;
-    {
-      std::string err;
-      if (!errors_ref_map(refs, n_refs, s.ref_names, files[f].ref_name, "file " + std::to_string(f), &map, &err)) return fail(kWho + err);
-    }
-    std::vector<int64_t> ref_at(std::max<size_t>(map.size(), 1), -1), ref_len(std::max<size_t>(map.size(), 1), 0);
-    for (size_t r = 0; r < map.size(); r++) {
-      if (map[r] < 0) continue;
-      const int64_t have = genome.len[(size_t)map[r]];
-      if (s.hd.ref_len[r] != have)
-        return fail(where + "the reference \"" + (files[f].ref_name ? std::string(files[f].ref_name) : s.ref_names[r]) + "\" has l_ref " +
-                    std::to_string(s.hd.ref_len[r]) + " in the file's header, and the genome's record of that name has " + std::to_string(have) +
-                    " bases: this is not the genome the reads were aligned to");
-      ref_at[r] = genome.at[(size_t)map[r]];
-      ref_len[r] = have;
-    }
+    // ---- 1. - 4. the stream, its records, its references by name, the record pass and the segments
+    BamFileFront ff;
+    if (!bam_file_front(c, kStage, ph, refs, n_refs, genome, files, f, n_files, o.exclude_flags, o.min_mapq, cells, true, &ff)) return PBSIM_FAILED;
+    const int64_t n_rec = ff.n_rec;
+    const ErrRecs &recs = ff.recs;
+    inflated += ff.s.N, n_all += n_rec, segments += ff.n_seg;
     texts.emplace_back();
     if (n_rec == 0) continue;
-    DevBuf d_ref_at, d_ref_len, d_rec, d_st, d_cig_at, d_n_ops, d_sums, d_nm, d_n_seg, d_col, d_scan_tmp, d_seg;
-    if (!alloc(d_ref_at, (int64_t)ref_at.size() * 8, "the references' places") || !alloc(d_ref_len, (int64_t)ref_len.size() * 8, "the references' lengths") ||
-        !alloc(d_rec, n_rec * 8, "the record list") || !alloc(d_st, n_rec, "the records' classes") || !alloc(d_cig_at, n_rec * 8, "the records' CIGARs") ||
-        !alloc(d_n_ops, n_rec * 4, "the records' op counts") || !alloc(d_sums, n_rec * 32, "the records' CIGAR sums") ||
-        !alloc(d_nm, n_rec * 8, "the records' NM values") || !alloc(d_n_seg, (n_rec + 1) * 8, "the records' segment counts") ||
-        !alloc(d_col, n_rec * 24, "the records' column counts") || !alloc(d_scan_tmp, (n_rec / 1024 + 8) * 8, "the scan's scratch"))
-      return PBSIM_FAILED;
-    HIP_OK(hipMemcpyAsync(d_ref_at.p, ref_at.data(), ref_at.size() * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_ref_len.p, ref_len.data(), ref_len.size() * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_rec.p, s.rec.data(), (size_t)n_rec * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemsetAsync(d_col.p, 0, (size_t)n_rec * 24, st));
-    HIP_OK(hipMemsetAsync(d_sums.p, 0, (size_t)n_rec * 32, st));
-    HIP_OK(hipMemsetAsync(d_nm.p, 0, (size_t)n_rec * 8, st));
-    const ErrRefs er = {(int32_t)map.size(), d_ref_at.as<int64_t>(), d_ref_len.as<int64_t>()};
-    const ErrRecs recs = {s.bytes(),
-                          d_rec.as<uint64_t>(),
-                          n_rec,
-                          d_st.as<uint8_t>(),
-                          d_cig_at.as<int64_t>(),
-                          d_n_ops.as<uint32_t>(),
-                          d_sums.as<int64_t>(),
-                          d_nm.as<int64_t>(),
-                          d_n_seg.as<int64_t>(),
-                          d_col.as<unsigned long long>()};
-    // ---- 3. the records
-    launch_errors_records(recs, er, o.exclude_flags, o.min_mapq, nullptr, cells, st);
-    HIP_OK(hipGetLastError());
-    uint64_t fault = 0;
-    HIP_OK(hipMemcpyAsync(&fault, cells + kErrCellFault, 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    ph.mark("records");
-    if (fault != ~(uint64_t)0)
-      return fail(where + "the record at inflated byte offset " + std::to_string(fault) +
-                  " is malformed: a CIGAR op code above 8, or an aux field that runs past the record or has an unknown type");
-    // ---- 4. the segments and their columns
-    int64_t n_seg = 0;
-    launch_exclusive_scan_i64(recs.n_seg, recs.n_seg, n_rec, d_scan_tmp.as<int64_t>(), recs.n_seg + n_rec, st);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(&n_seg, recs.n_seg + n_rec, 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    segments += n_seg;
-    if (n_seg > 0) {
-      if (!alloc(d_seg, n_seg * (int64_t)sizeof(ErrSegment), "the segments")) return PBSIM_FAILED;
-      launch_errors_records(recs, er, o.exclude_flags, o.min_mapq, d_seg.as<ErrSegment>(), cells, st);
-      HIP_OK(hipGetLastError());
-      ph.mark("segments");
-      launch_errors_columns(recs, er, g, d_seg.as<ErrSegment>(), n_seg, cells, st);
+    // ---- the segments' columns, into the records' column counts
+    if (ff.n_seg > 0) {
+      launch_errors_columns(recs, ff.er, g, ff.d_seg.as<ErrSegment>(), ff.n_seg, cells, st);
       HIP_OK(hipGetLastError());
       ph.mark("columns");
     }
@@ -140,7 +71,7 @@ int errors_bam(pbsim_ctx *c, const pbsim_errors_ref *refs, int n_refs, const pbs
       int64_t *len = d_len.as<int64_t>();
       launch_errors_line_sizes(recs, len, st);
       HIP_OK(hipGetLastError());
-      launch_exclusive_scan_i64(len, len, n_rec, d_scan_tmp.as<int64_t>(), len + n_rec, st);
+      launch_exclusive_scan_i64(len, len, n_rec, ff.d_scan_tmp.as<int64_t>(), len + n_rec, st);
       HIP_OK(hipGetLastError());
       HIP_OK(hipMemcpyAsync(&t.n, len + n_rec, 8, hipMemcpyDeviceToHost, st));
       HIP_OK(hipStreamSynchronize(st));

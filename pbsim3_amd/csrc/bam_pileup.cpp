@@ -1,8 +1,8 @@
 // bam_pileup.cpp -- pbsim_bam_pileup: the pileup of the aligned reads of BAM files against their genome (the rule:
 // include/pbsim3_amd.h, tests/pileup_model.py).  The host's part has the flow of pbsim_bam_errors (bam_errors.cpp): the genome into
-// HBM (bam_genome.cpp), the table zeroed, then per file its stream and records (bam_stream.cpp), the references by name
-// (bam_errors_rule.cpp), the record pass and the segments (bam_errors.hip) and the column pass; then once the site pass, the text
-// and its way to the sink; the per-file part up to the segments is pbsim_bam_consensus's too (bam_pileup_front.h); the kernels are inflate.hip's, bam_scan.hip's, bam_errors.hip's and bam_pileup.hip's.
+// HBM (bam_genome.cpp), the table zeroed, then per file the front half the three stages share (bam_file_front.h: its stream and
+// records, the references by name, the record pass and the segments) and the column pass; then once the site pass, the text and
+// its way to the sink; the kernels are inflate.hip's, bam_scan.hip's, bam_errors.hip's and bam_pileup.hip's.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -14,100 +14,13 @@
 
 #include "bam_genome.h"
 #include "bam_pileup.h"
-#include "bam_pileup_front.h"
+#include "bam_file_front.h"
 #include "bam_scan.h"
 #include "bam_stream.h"
 #include "ctx.h"
 #include "kernels.h"
 
 namespace pbsim {
-
-// One file up to its segments (bam_pileup_front.h): the flow of pbsim_bam_errors's first half.
-int pileup_file_front(pbsim_ctx *c, const BamStage &stage, BamPhases &ph, const pbsim_errors_ref *refs, int n_refs, const Genome &genome,
-                      const pbsim_errors_file *files, int f, int n_files, int32_t exclude_flags, int32_t min_mapq, unsigned long long *cells,
-                      PileFile *pf) {
-  hipStream_t st = c->stream;
-  auto alloc = [&](DevBuf &b, int64_t n, const char *what) { return bam_stage_alloc(stage, b, n, what); };
-  // ---- 1. the stream into HBM, and its records
-  BamStream &s = pf->s;
-  s.a_what = "a file";
-  if (n_files > 1) s.what = "file " + std::to_string(f);
-  const std::string where = stage.who + s.what + (s.what.empty() ? "" : ": ");
-  if (!bam_inflate_stream(c, stage, (const uint8_t *)files[f].bam, files[f].n, &s)) return PBSIM_FAILED;
-  ph.mark("inflate");
-  {
-    BamScan scan;
-    if (!bam_locate(c, stage, &s, &scan, kBamScanAny, kBamSamplePacking)) return PBSIM_FAILED;
-  }
-  ph.mark("locate");
-  const int64_t n_rec = pf->n_rec = (int64_t)s.rec.size();
-  if (n_rec >= ((int64_t)1 << 32) - 1) return fail(where + std::to_string(n_rec) + " records: a file of 2^32 - 1 records or more is not taken (a segment names its record in 32 bits)");
-  // ---- 2. its references, by name
-  std::vector<int32_t> map;
-  {
-    std::string err;
-    if (!errors_ref_map(refs, n_refs, s.ref_names, files[f].ref_name, "file " + std::to_string(f), &map, &err)) return fail(stage.who + err);
-  }
-  std::vector<int64_t> ref_at(std::max<size_t>(map.size(), 1), -1), ref_len(std::max<size_t>(map.size(), 1), 0);
-  for (size_t r = 0; r < map.size(); r++) {
-    if (map[r] < 0) continue;
-    const int64_t have = genome.len[(size_t)map[r]];
-    if (s.hd.ref_len[r] != have)
-      return fail(where + "the reference \"" + (files[f].ref_name ? std::string(files[f].ref_name) : s.ref_names[r]) + "\" has l_ref " +
-                  std::to_string(s.hd.ref_len[r]) + " in the file's header, and the genome's record of that name has " + std::to_string(have) +
-                  " bases: this is not the genome the reads were aligned to");
-    ref_at[r] = genome.at[(size_t)map[r]];
-    ref_len[r] = have;
-  }
-  if (n_rec == 0) return PBSIM_SUCCEEDED;
-  DevBuf &d_ref_at = pf->d_ref_at, &d_ref_len = pf->d_ref_len, &d_rec = pf->d_rec, &d_st = pf->d_st, &d_cig_at = pf->d_cig_at, &d_n_ops = pf->d_n_ops,
-         &d_sums = pf->d_sums, &d_nm = pf->d_nm, &d_n_seg = pf->d_n_seg, &d_scan_tmp = pf->d_scan_tmp, &d_seg = pf->d_seg;
-  if (!alloc(d_ref_at, (int64_t)ref_at.size() * 8, "the references' places") || !alloc(d_ref_len, (int64_t)ref_len.size() * 8, "the references' lengths") ||
-      !alloc(d_rec, n_rec * 8, "the record list") || !alloc(d_st, n_rec, "the records' classes") || !alloc(d_cig_at, n_rec * 8, "the records' CIGARs") ||
-      !alloc(d_n_ops, n_rec * 4, "the records' op counts") || !alloc(d_sums, n_rec * 32, "the records' CIGAR sums") ||
-      !alloc(d_nm, n_rec * 8, "the records' NM values") || !alloc(d_n_seg, (n_rec + 1) * 8, "the records' segment counts") ||
-      !alloc(d_scan_tmp, (n_rec / 1024 + 8) * 8, "the scan's scratch"))
-    return PBSIM_FAILED;
-  HIP_OK(hipMemcpyAsync(d_ref_at.p, ref_at.data(), ref_at.size() * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_ref_len.p, ref_len.data(), ref_len.size() * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_rec.p, s.rec.data(), (size_t)n_rec * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemsetAsync(d_sums.p, 0, (size_t)n_rec * 32, st));
-  HIP_OK(hipMemsetAsync(d_nm.p, 0, (size_t)n_rec * 8, st));
-  const ErrRefs er = pf->er = {(int32_t)map.size(), d_ref_at.as<int64_t>(), d_ref_len.as<int64_t>()};
-  const ErrRecs recs = pf->recs = {s.bytes(),
-                                   d_rec.as<uint64_t>(),
-                                   n_rec,
-                                   d_st.as<uint8_t>(),
-                                   d_cig_at.as<int64_t>(),
-                                   d_n_ops.as<uint32_t>(),
-                                   d_sums.as<int64_t>(),
-                                   d_nm.as<int64_t>(),
-                                   d_n_seg.as<int64_t>(),
-                                   nullptr};  // (the records' column counts are the errors stage's column pass's alone)
-  // ---- 3. the records
-  launch_errors_records(recs, er, exclude_flags, min_mapq, nullptr, cells, st);
-  HIP_OK(hipGetLastError());
-  uint64_t fault = 0;
-  HIP_OK(hipMemcpyAsync(&fault, cells + kErrCellFault, 8, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  ph.mark("records");
-  if (fault != ~(uint64_t)0)
-    return fail(where + "the record at inflated byte offset " + std::to_string(fault) +
-                " is malformed: a CIGAR op code above 8, or an aux field that runs past the record or has an unknown type");
-  // ---- 4. the segments and their columns
-  int64_t &n_seg = pf->n_seg;
-  launch_exclusive_scan_i64(recs.n_seg, recs.n_seg, n_rec, d_scan_tmp.as<int64_t>(), recs.n_seg + n_rec, st);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(&n_seg, recs.n_seg + n_rec, 8, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  if (n_seg > 0) {
-    if (!alloc(d_seg, n_seg * (int64_t)sizeof(ErrSegment), "the segments")) return PBSIM_FAILED;
-    launch_errors_records(recs, er, exclude_flags, min_mapq, d_seg.as<ErrSegment>(), cells, st);
-    HIP_OK(hipGetLastError());
-    ph.mark("segments");
-  }
-  return PBSIM_SUCCEEDED;
-}
 
 namespace {
 
@@ -140,8 +53,8 @@ int pileup_bam(pbsim_ctx *c, const pbsim_errors_ref *refs, int n_refs, const pbs
   ph.mark("zero");
   int64_t n_all = 0, inflated = 0, segments = 0;
   for (int f = 0; f < n_files; f++) {
-    PileFile pf;
-    if (!pileup_file_front(c, kStage, ph, refs, n_refs, genome, files, f, n_files, o.exclude_flags, o.min_mapq, cells, &pf)) return PBSIM_FAILED;
+    BamFileFront pf;
+    if (!bam_file_front(c, kStage, ph, refs, n_refs, genome, files, f, n_files, o.exclude_flags, o.min_mapq, cells, false, &pf)) return PBSIM_FAILED;
     inflated += pf.s.N, n_all += pf.n_rec, segments += pf.n_seg;
     if (pf.n_seg > 0) {
       launch_pileup_columns(pf.recs, pf.er, g, pf.d_seg.as<ErrSegment>(), pf.n_seg, (uint32_t)o.min_baseq, table, pile, st);

@@ -8,7 +8,8 @@
 // compressed bytes cross PCIe) and written here; --gzip host uses the in-process multi-threaded zlib writer (gzout.h);
 // --samtools pipes SAM text into `samtools view -b` like the reference.  --truth-format bam writes the truth as aligned BAM;
 // --truth-sort coordinate then sorts and indexes each finished <prefix>[_NNNN].aln.bam on the GPU (pbsim_truth_bam_sort), and
-// `pbsim --sort-truth-bam FILE ...` does that alone for files made earlier.
+// `pbsim --sort-truth-bam FILE ...` does that alone for files made earlier.  The other stand-alone modes (--eval-bam .. --apply-vcf)
+// are cli_stages.cpp's: pbsim_cli_main hands the line to the first of them it names.
 //
 // wgs (errhmm / qshmm) runs as ONE job over all records (pbsim_job_run): the records are resident in HBM, and on several
 // ranks every rank pwrite()s its own byte ranges of the final files.  Rank 0 alone prints and creates files.
@@ -43,6 +44,8 @@
 #include <vector>
 
 #include "../../include/pbsim3_amd.h"
+#include "cli_common.h"
+#include "cli_stages.h"
 #include "gzout.h"
 #include "input_file.h"
 #include "unit_io.h"
@@ -63,19 +66,9 @@ struct Cli {
   bool truth_sort = false;  // --truth-sort coordinate: each finished .aln.bam sorted by coordinate, with a .csi beside it
 };
 
-// the reference's exit(-1).  Other ranks of the process may be inside HIP calls on their own threads: leave without running
-// static destructors under them (everything buffered is flushed first)
-[[noreturn]] void quit(int status) {
-  fflush(NULL);
-  _exit(status & 255);
-}
-
-[[noreturn]] void die(const char *fmt, const char *a = "", const char *b = "") {
-  fprintf(stderr, "ERROR");
-  fprintf(stderr, fmt, a, b);
-  fprintf(stderr, "\n");
-  quit(-1);
-}
+using pbsim::cli::check;
+using pbsim::cli::die;
+using pbsim::cli::quit;
 
 // an empty BGZF block: the EOF marker of a BAM file (SAMv1 4.1.2), and a valid empty gzip member
 const unsigned char kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -384,15 +377,6 @@ void print_help() {
           "  origin map (int32 per written base, little-endian) to --apply-origin; both inputs may be gzip-compressed\n"
           "  --genome, --transcript, --template and --sample may be gzip-compressed (recognised by content): BGZF is\n"
           "  inflated on the GPU, other gzip by zlib on the host; the whole inflated file is held in host memory\n\n");
-}
-
-void check(int ok) {
-  if (!ok) {
-    // a rank that only learnt of another rank's failure lets that rank report first (they share this process's stderr and exit)
-    if (!strncmp(pbsim_last_error(), "another rank", 12)) usleep(300000);
-    fprintf(stderr, "ERROR: %s\n", pbsim_last_error());
-    quit(-1);
-  }
 }
 
 // options + set_sim_param (pbsim.cpp:286-530, 1451-1688); exits like the reference on a bad value
@@ -1022,1170 +1006,15 @@ void sort_truth_files(pbsim_ctx *ctx, const std::vector<std::string> &names, boo
   }
 }
 
-// `pbsim --eval-bam MAPPED.bam --truth-bam FILE ...`: a mapper's BAM scored against finished truth BAMs (pbsim_truth_bam_eval),
-// the report to stdout or --eval-out.  What can be refused from the command line alone is refused before a GPU is touched.
-struct MappedFile {
-  void *map = MAP_FAILED;
-  size_t n = 0;
-  ~MappedFile() {
-    if (map != MAP_FAILED) munmap(map, n);
-  }
-  bool open_file(const std::string &name) {
-    const int fd = open(name.c_str(), O_RDONLY);
-    struct stat sb;
-    if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size <= 0) {
-      if (fd >= 0) close(fd);
-      return false;
-    }
-    n = (size_t)sb.st_size;
-    map = mmap(NULL, n, PROT_READ, MAP_PRIVATE, fd, 0);
-    close(fd);
-    if (map == MAP_FAILED) return false;
-    (void)madvise(map, n, MADV_SEQUENTIAL);
-    return true;
-  }
-};
-
-int eval_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
-  if (comm && comm->world > 1) die(": --eval-bam runs on one GPU.");
-  std::string query, names_arg, out_name;
-  std::vector<std::string> truth;
-  bool have_names = false;
-  double overlap = 0.1;
-  for (int i = 1; i < argc; i++) {
-    const std::string a = argv[i];
-    const bool takes = a == "--eval-bam" || a == "--truth-bam" || a == "--truth-ref-names" || a == "--eval-overlap" || a == "--eval-out" ||
-                       a == "--device";
-    if (!takes)
-      die(" (%s): --eval-bam takes --truth-bam, --truth-ref-names, --eval-overlap, --eval-out and --device, and no other option.", argv[i]);
-    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
-    const char *v = argv[++i];
-    if (a == "--eval-bam") query = v;
-    else if (a == "--truth-bam") truth.push_back(v);
-    else if (a == "--truth-ref-names") names_arg = v, have_names = true;
-    else if (a == "--eval-out") out_name = v;
-    else if (a == "--device") device = device >= 0 ? device : atoi(v);
-    else {
-      char *e = NULL;
-      overlap = strtod(v, &e);
-      if (e == v || *e || !(overlap > 0.0 && overlap <= 1.0)) die(" (eval-overlap: %s): the least intersection / union of a correct mapping, in (0, 1].", v);
-    }
-  }
-  if (query.empty()) die(": --eval-bam MAPPED.bam: name the mapper's BAM file.");
-  if (truth.empty()) die(": --eval-bam needs the truth: --truth-bam FILE [--truth-bam FILE ...] (the .aln.bam files of --truth-format bam).");
-  std::vector<std::string> names;
-  if (have_names) {
-    for (size_t at = 0;;) {
-      const size_t comma = names_arg.find(',', at);
-      names.push_back(names_arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
-      if (comma == std::string::npos) break;
-      at = comma + 1;
-    }
-    char got[32], want[32];
-    snprintf(got, sizeof got, "%zu", names.size());
-    snprintf(want, sizeof want, "%zu", truth.size());
-    if (names.size() != truth.size()) die(" (truth-ref-names): %s names for %s --truth-bam files: the k-th name goes to the k-th file.", got, want);
-    for (const std::string &n : names)
-      if (n.empty()) die(" (truth-ref-names: %s): an empty name.", names_arg.c_str());
-  }
-  std::vector<MappedFile> files(truth.size() + 1);
-  for (size_t f = 0; f <= truth.size(); f++) {
-    const std::string &name = f < truth.size() ? truth[f] : query;
-    if (!files[f].open_file(name)) die(": Cannot open file: %s", name.c_str());
-  }
-  pbsim_params p;
-  pbsim_params_default(&p);
-  p.strategy = PBSIM_STRATEGY_WGS;
-  p.method = PBSIM_METHOD_ERR;
-  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
-  if (!ctx) check(0);
-  std::vector<pbsim_eval_truth> tr(truth.size());
-  for (size_t f = 0; f < truth.size(); f++) tr[f] = pbsim_eval_truth{files[f].map, (int64_t)files[f].n, have_names ? names[f].c_str() : NULL};
-  pbsim_eval_opts opts = {(int32_t)std::min(1000L, std::max(1L, lround(overlap * 1000))), 0};
-  int64_t counts[12], hist[512];
-  if (!pbsim_truth_bam_eval(ctx, tr.data(), (int)tr.size(), files.back().map, (int64_t)files.back().n, &opts, NULL, counts, hist)) {
-    fprintf(stderr, "ERROR: %s\n", pbsim_last_error());
-    for (size_t f = 0; f < truth.size(); f++) fprintf(stderr, "ERROR: truth file %zu is %s\n", f, truth[f].c_str());
-    quit(-1);
-  }
-  std::string text((size_t)pbsim_eval_report(counts, hist, NULL, 0), '\0');
-  pbsim_eval_report(counts, hist, &text[0], (int64_t)text.size());
-  FILE *fp = out_name.empty() ? stdout : fopen(out_name.c_str(), "wb");
-  if (!fp) die(": Cannot open output file: %s", out_name.c_str());
-  const bool wrote = fwrite(text.data(), 1, text.size(), fp) == text.size();
-  if ((fp == stdout ? fflush(fp) : fclose(fp)) != 0 || !wrote) die(": write error on %s", out_name.empty() ? "the standard output" : out_name.c_str());
-  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
-  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
-  return 0;
-}
-
-// `pbsim --depth-bam FILE --depth-out FILE ...`: the depth of coverage of a BAM (pbsim_bam_depth), the text to --depth-out, the
-// report to stdout.  What can be refused from the command line alone is refused before a GPU is touched.
-bool whole_number(const char *v, int base, long long lo, long long hi, long long *out) {
-  char *e = NULL;
-  errno = 0;
-  const long long x = strtoll(v, &e, base);
-  if (e == v || *e || errno || x < lo || x > hi || !(isdigit((unsigned char)v[0]))) return false;
-  *out = x;
-  return true;
-}
-
-int depth_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
-  if (comm && comm->world > 1) die(": --depth-bam runs on one GPU.");
-  std::string in_name, out_name, format = "bedgraph";
-  long long window = 0, min_mapq = 0, exclude = 0x704;
-  bool have_window = false, deletions = true;
-  for (int i = 1; i < argc; i++) {
-    const std::string a = argv[i];
-    if (a == "--depth-no-deletions") {
-      deletions = false;
-      continue;
-    }
-    const bool takes = a == "--depth-bam" || a == "--depth-out" || a == "--depth-format" || a == "--depth-window" || a == "--depth-min-mapq" ||
-                       a == "--depth-exclude-flags" || a == "--device";
-    if (!takes)
-      die(" (%s): --depth-bam takes --depth-out, --depth-format, --depth-window, --depth-min-mapq, --depth-exclude-flags, --depth-no-deletions "
-          "and --device, and no other option.",
-          argv[i]);
-    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
-    const char *v = argv[++i];
-    if (a == "--depth-bam") in_name = v;
-    else if (a == "--depth-out") out_name = v;
-    else if (a == "--device") device = device >= 0 ? device : atoi(v);
-    else if (a == "--depth-format") {
-      format = v;
-      if (format != "bedgraph" && format != "window") die(" (depth-format: %s): bedgraph or window.", v);
-    } else if (a == "--depth-window") {
-      have_window = true;
-      if (!whole_number(v, 10, 1, LLONG_MAX, &window)) die(" (depth-window: %s): a whole number of at least 1.", v);
-    } else if (a == "--depth-min-mapq") {
-      if (!whole_number(v, 10, 0, 255, &min_mapq)) die(" (depth-min-mapq: %s): a whole number, 0 .. 255.", v);
-    } else {
-      const bool hex = v[0] == '0' && (v[1] == 'x' || v[1] == 'X');
-      if (!whole_number(v, hex ? 16 : 10, 0, 65535, &exclude)) die(" (depth-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535.", v);
-    }
-  }
-  if (in_name.empty()) die(": --depth-bam FILE: name the BAM file.");
-  if (out_name.empty()) die(": --depth-bam needs --depth-out FILE: the bedGraph or window text goes there (the report goes to the standard output).");
-  if (format == "window" && !have_window) die(": --depth-format window needs --depth-window N.");
-  if (format != "window" && have_window) die(": --depth-window N goes with --depth-format window.");
-  MappedFile file;
-  if (!file.open_file(in_name)) die(": Cannot open file: %s", in_name.c_str());
-  pbsim_params p;
-  pbsim_params_default(&p);
-  p.strategy = PBSIM_STRATEGY_WGS;
-  p.method = PBSIM_METHOD_ERR;
-  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
-  if (!ctx) check(0);
-  struct Result {
-    FILE *fp = NULL;
-    bool write_failed = false;
-    std::vector<std::string> names;
-    std::vector<int64_t> rows;
-  } res;
-  res.fp = fopen(out_name.c_str(), "wb");
-  if (!res.fp) die(": Cannot open output file: %s", out_name.c_str());
-  pbsim_depth_opts opts = {(int32_t)exclude, (int32_t)min_mapq, deletions ? 1 : 0, format == "window" ? 1 : 0, (int64_t)window, 0};
-  pbsim_depth_sink sink = {&res,
-                           [](void *u, const char *z, int64_t k, int64_t) {
-                             Result *x = (Result *)u;
-                             if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
-                             return x->write_failed ? 0 : 1;
-                           },
-                           [](void *u, int32_t n_ref, const char *const *names, const int64_t *rows) {
-                             Result *x = (Result *)u;
-                             x->names.assign(names, names + n_ref);
-                             x->rows.assign(rows, rows + 4 * (size_t)n_ref);
-                             return 1;
-                           },
-                           NULL};
-  int64_t counts[6], hist[256];
-  const bool ok = pbsim_bam_depth(ctx, file.map, (int64_t)file.n, &opts, &sink, counts, hist) != 0;
-  if (fclose(res.fp) != 0) res.write_failed = true;
-  if (!ok || res.write_failed) {
-    fprintf(stderr, "ERROR: %s\n", res.write_failed ? ("write error on " + out_name).c_str() : pbsim_last_error());
-    unlink(out_name.c_str());
-    quit(-1);
-  }
-  std::vector<const char *> name_ptr;
-  for (const std::string &nm : res.names) name_ptr.push_back(nm.c_str());
-  const int32_t n_ref = (int32_t)name_ptr.size();
-  std::string text((size_t)pbsim_depth_report(counts, n_ref, name_ptr.data(), res.rows.data(), hist, NULL, 0), '\0');
-  pbsim_depth_report(counts, n_ref, name_ptr.data(), res.rows.data(), hist, &text[0], (int64_t)text.size());
-  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
-  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
-  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
-  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
-  return 0;
-}
-
-// `pbsim --stats-bam FILE [--stats-bam FILE ...] ...`: a summary of the reads of BAM files (pbsim_bam_stats), the report to
-// stdout, the per-read text to --stats-out.  What can be refused from the command line alone is refused before a GPU is touched.
-int stats_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
-  if (comm && comm->world > 1) die(": --stats-bam runs on one GPU.");
-  std::vector<std::string> in_names;
-  std::string out_name;
-  long long min_mapq = 0, exclude = 0x900;
-  for (int i = 1; i < argc; i++) {
-    const std::string a = argv[i];
-    const bool takes = a == "--stats-bam" || a == "--stats-out" || a == "--stats-min-mapq" || a == "--stats-exclude-flags" || a == "--device";
-    if (!takes) die(" (%s): --stats-bam takes --stats-out, --stats-min-mapq, --stats-exclude-flags and --device, and no other option.", argv[i]);
-    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
-    const char *v = argv[++i];
-    if (a == "--stats-bam") in_names.push_back(v);
-    else if (a == "--stats-out") out_name = v;
-    else if (a == "--device") device = device >= 0 ? device : atoi(v);
-    else if (a == "--stats-min-mapq") {
-      if (!whole_number(v, 10, 0, 255, &min_mapq)) die(" (stats-min-mapq: %s): a whole number, 0 .. 255.", v);
-    } else {
-      const bool hex = v[0] == '0' && (v[1] == 'x' || v[1] == 'X');
-      if (!whole_number(v, hex ? 16 : 10, 0, 65535, &exclude)) die(" (stats-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535.", v);
-    }
-  }
-  if (in_names.empty()) die(": --stats-bam FILE: name the BAM file.");
-  std::vector<MappedFile> files(in_names.size());
-  for (size_t f = 0; f < files.size(); f++)
-    if (!files[f].open_file(in_names[f])) die(": Cannot open file: %s", in_names[f].c_str());
-  pbsim_params p;
-  pbsim_params_default(&p);
-  p.strategy = PBSIM_STRATEGY_WGS;
-  p.method = PBSIM_METHOD_ERR;
-  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
-  if (!ctx) check(0);
-  struct Result {
-    FILE *fp = NULL;
-    bool write_failed = false;
-  } res;
-  if (!out_name.empty()) {
-    res.fp = fopen(out_name.c_str(), "wb");
-    if (!res.fp) die(": Cannot open output file: %s", out_name.c_str());
-  }
-  std::vector<pbsim_stats_file> in(files.size());
-  for (size_t f = 0; f < files.size(); f++) in[f] = pbsim_stats_file{files[f].map, (int64_t)files[f].n};
-  pbsim_stats_opts opts = {(int32_t)exclude, (int32_t)min_mapq, 0};
-  pbsim_stats_sink sink = {&res, [](void *u, const char *z, int64_t k, int64_t) {
-                             Result *x = (Result *)u;
-                             if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
-                             return x->write_failed ? 0 : 1;
-                           }};
-  if (!res.fp) sink.on_text = NULL;
-  int64_t counts[10], len_row[16], totals[12], hist_q[128], hist_identity[1001], hist_qacc[1001];
-  const bool ok = pbsim_bam_stats(ctx, in.data(), (int)in.size(), &opts, &sink, counts, len_row, totals, hist_q, hist_identity, hist_qacc) != 0;
-  if (res.fp && fclose(res.fp) != 0) res.write_failed = true;
-  if (!ok || res.write_failed) {
-    fprintf(stderr, "ERROR: %s\n", res.write_failed ? ("write error on " + out_name).c_str() : pbsim_last_error());
-    if (in_names.size() > 1)
-      for (size_t f = 0; f < in_names.size(); f++) fprintf(stderr, "ERROR: file %zu is %s\n", f, in_names[f].c_str());
-    if (!out_name.empty()) unlink(out_name.c_str());
-    quit(-1);
-  }
-  std::string text((size_t)pbsim_stats_report(counts, len_row, totals, hist_q, hist_identity, hist_qacc, NULL, 0), '\0');
-  pbsim_stats_report(counts, len_row, totals, hist_q, hist_identity, hist_qacc, &text[0], (int64_t)text.size());
-  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
-  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
-  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
-  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
-  return 0;
-}
-
-// `pbsim --errors-bam FILE [--errors-bam FILE ...] --errors-genome FASTA ...`: the error profile of aligned reads against their
-// genome (pbsim_bam_errors), the report to stdout, the per-read text to --errors-out.  What can be refused from the command line
-// alone is refused before a GPU is touched.
-int errors_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
-  if (comm && comm->world > 1) die(": --errors-bam runs on one GPU.");
-  std::vector<std::string> in_names, names;
-  std::string out_name, genome_name, names_arg;
-  bool have_names = false;
-  long long min_mapq = 0, exclude = 0x900;
-  for (int i = 1; i < argc; i++) {
-    const std::string a = argv[i];
-    const bool takes = a == "--errors-bam" || a == "--errors-genome" || a == "--errors-ref-names" || a == "--errors-out" || a == "--errors-min-mapq" ||
-                       a == "--errors-exclude-flags" || a == "--device";
-    if (!takes)
-      die(" (%s): --errors-bam takes --errors-genome, --errors-ref-names, --errors-out, --errors-min-mapq, --errors-exclude-flags and --device, "
-          "and no other option.",
-          argv[i]);
-    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
-    const char *v = argv[++i];
-    if (a == "--errors-bam") in_names.push_back(v);
-    else if (a == "--errors-genome") genome_name = v;
-    else if (a == "--errors-ref-names") names_arg = v, have_names = true;
-    else if (a == "--errors-out") out_name = v;
-    else if (a == "--device") device = device >= 0 ? device : atoi(v);
-    else if (a == "--errors-min-mapq") {
-      if (!whole_number(v, 10, 0, 255, &min_mapq)) die(" (errors-min-mapq: %s): a whole number, 0 .. 255.", v);
-    } else {
-      const bool hex = v[0] == '0' && (v[1] == 'x' || v[1] == 'X');
-      if (!whole_number(v, hex ? 16 : 10, 0, 65535, &exclude)) die(" (errors-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535.", v);
-    }
-  }
-  if (in_names.empty()) die(": --errors-bam FILE: name the BAM file.");
-  if (genome_name.empty()) die(": --errors-bam needs --errors-genome FASTA: the genome the reads were aligned to.");
-  if (have_names) {
-    for (size_t at = 0;;) {
-      const size_t comma = names_arg.find(',', at);
-      names.push_back(names_arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
-      if (comma == std::string::npos) break;
-      at = comma + 1;
-    }
-    char got[32], want[32];
-    snprintf(got, sizeof got, "%zu", names.size());
-    snprintf(want, sizeof want, "%zu", in_names.size());
-    if (names.size() != in_names.size()) die(" (errors-ref-names): %s names for %s --errors-bam files: the k-th name goes to the k-th file.", got, want);
-    for (const std::string &n : names)
-      if (n.empty()) die(" (errors-ref-names): an empty name.");
-  }
-  std::vector<MappedFile> files(in_names.size());
-  for (size_t f = 0; f < files.size(); f++)
-    if (!files[f].open_file(in_names[f])) die(": Cannot open file: %s", in_names[f].c_str());
-  // the genome: each record's sequence lines as they lie in the file, its name the id up to the first white space
-  pbsim::FastaMap fm;
-  {
-    pbsim::GenomeInfo gm;
-    bool fallback = false;
-    std::string err;
-    if (!pbsim::map_genome(genome_name.c_str(), &fm, &gm, false, &fallback, &err))
-      die(": --errors-genome %s: %s", genome_name.c_str(),
-          fallback ? "not a FASTA file that can be mapped (a regular file that begins with '>' and holds no NUL byte)" : err.c_str());
-  }
-  std::vector<std::string> ref_names;
-  for (const pbsim::FastaRecord &r : fm.recs) ref_names.push_back(r.id.substr(0, r.id.find_first_of(" \t\r\n\v\f")));
-  std::vector<pbsim_errors_ref> refs;
-  for (size_t r = 0; r < fm.recs.size(); r++) refs.push_back(pbsim_errors_ref{ref_names[r].c_str(), fm.recs[r].lines, fm.recs[r].bytes});
-  pbsim_params p;
-  pbsim_params_default(&p);
-  p.strategy = PBSIM_STRATEGY_WGS;
-  p.method = PBSIM_METHOD_ERR;
-  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
-  if (!ctx) check(0);
-  struct Result {
-    FILE *fp = NULL;
-    bool write_failed = false;
-  } res;
-  if (!out_name.empty()) {
-    res.fp = fopen(out_name.c_str(), "wb");
-    if (!res.fp) die(": Cannot open output file: %s", out_name.c_str());
-  }
-  std::vector<pbsim_errors_file> in(files.size());
-  for (size_t f = 0; f < files.size(); f++) in[f] = pbsim_errors_file{files[f].map, (int64_t)files[f].n, have_names ? names[f].c_str() : NULL};
-  pbsim_errors_opts opts = {(int32_t)exclude, (int32_t)min_mapq, 0};
-  pbsim_errors_sink sink = {&res, [](void *u, const char *z, int64_t k, int64_t) {
-                              Result *x = (Result *)u;
-                              if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
-                              return x->write_failed ? 0 : 1;
-                            }};
-  if (!res.fp) sink.on_text = NULL;
-  std::vector<pbsim_errors_result> result(1);
-  const bool ok = pbsim_bam_errors(ctx, refs.data(), (int)refs.size(), in.data(), (int)in.size(), &opts, &sink, result.data()) != 0;
-  if (res.fp && fclose(res.fp) != 0) res.write_failed = true;
-  if (!ok || res.write_failed) {
-    fprintf(stderr, "ERROR: %s\n", res.write_failed ? ("write error on " + out_name).c_str() : pbsim_last_error());
-    if (in_names.size() > 1)
-      for (size_t f = 0; f < in_names.size(); f++) fprintf(stderr, "ERROR: file %zu is %s\n", f, in_names[f].c_str());
-    if (!out_name.empty()) unlink(out_name.c_str());
-    quit(-1);
-  }
-  std::string text((size_t)pbsim_errors_report(result.data(), NULL, 0), '\0');
-  pbsim_errors_report(result.data(), &text[0], (int64_t)text.size());
-  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
-  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
-  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
-  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
-  return 0;
-}
-
-// `pbsim --pileup-bam FILE [--pileup-bam FILE ...] --pileup-genome FASTA ...`: the pileup of aligned reads against their genome
-// (pbsim_bam_pileup), the report to stdout, the sites' text to --pileup-out.  What can be refused from the command line alone is
-// refused before a GPU is touched.
-int pileup_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
-  if (comm && comm->world > 1) die(": --pileup-bam runs on one GPU.");
-  std::vector<std::string> in_names, names;
-  std::string out_name, genome_name, names_arg;
-  bool have_names = false;
-  long long min_mapq = 0, min_baseq = 0, min_depth = 1, format = 0;
-  for (int i = 1; i < argc; i++) {
-    const std::string a = argv[i];
-    const bool takes = a == "--pileup-bam" || a == "--pileup-genome" || a == "--pileup-ref-names" || a == "--pileup-out" || a == "--pileup-format" ||
-                       a == "--pileup-min-mapq" || a == "--pileup-min-baseq" || a == "--pileup-min-depth" || a == "--device";
-    if (!takes)
-      die(" (%s): --pileup-bam takes --pileup-genome, --pileup-ref-names, --pileup-out, --pileup-format, --pileup-min-mapq, --pileup-min-baseq, "
-          "--pileup-min-depth and --device, and no other option.",
-          argv[i]);
-    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
-    const char *v = argv[++i];
-    if (a == "--pileup-bam") in_names.push_back(v);
-    else if (a == "--pileup-genome") genome_name = v;
-    else if (a == "--pileup-ref-names") names_arg = v, have_names = true;
-    else if (a == "--pileup-out") out_name = v;
-    else if (a == "--device") device = device >= 0 ? device : atoi(v);
-    else if (a == "--pileup-format") {
-      if (!strcmp(v, "sites")) format = 0;
-      else if (!strcmp(v, "all")) format = 1;
-      else die(" (pileup-format: %s): sites or all.", v);
-    } else if (a == "--pileup-min-mapq") {
-      if (!whole_number(v, 10, 0, 255, &min_mapq)) die(" (pileup-min-mapq: %s): a whole number, 0 .. 255.", v);
-    } else if (a == "--pileup-min-baseq") {
-      if (!whole_number(v, 10, 0, 255, &min_baseq)) die(" (pileup-min-baseq: %s): a whole number, 0 .. 255.", v);
-    } else {
-      if (!whole_number(v, 10, 0, 1000000000000LL, &min_depth)) die(" (pileup-min-depth: %s): a whole number, 0 .. 1000000000000.", v);
-    }
-  }
-  if (in_names.empty()) die(": --pileup-bam FILE: name the BAM file.");
-  if (genome_name.empty()) die(": --pileup-bam needs --pileup-genome FASTA: the genome the reads were aligned to.");
-  if (have_names) {
-    for (size_t at = 0;;) {
-      const size_t comma = names_arg.find(',', at);
-      names.push_back(names_arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
-      if (comma == std::string::npos) break;
-      at = comma + 1;
-    }
-    char got[32], want[32];
-    snprintf(got, sizeof got, "%zu", names.size());
-    snprintf(want, sizeof want, "%zu", in_names.size());
-    if (names.size() != in_names.size()) die(" (pileup-ref-names): %s names for %s --pileup-bam files: the k-th name goes to the k-th file.", got, want);
-    for (const std::string &n : names)
-      if (n.empty()) die(" (pileup-ref-names): an empty name.");
-  }
-  std::vector<MappedFile> files(in_names.size());
-  for (size_t f = 0; f < files.size(); f++)
-    if (!files[f].open_file(in_names[f])) die(": Cannot open file: %s", in_names[f].c_str());
-  // the genome, through the input path of --errors-genome: each record's sequence lines, its name the id up to the first white space
-  pbsim::FastaMap fm;
-  {
-    pbsim::GenomeInfo gm;
-    bool fallback = false;
-    std::string err;
-    if (!pbsim::map_genome(genome_name.c_str(), &fm, &gm, false, &fallback, &err))
-      die(": --pileup-genome %s: %s", genome_name.c_str(),
-          fallback ? "not a FASTA file that can be mapped (a regular file that begins with '>' and holds no NUL byte)" : err.c_str());
-  }
-  std::vector<std::string> ref_names;
-  for (const pbsim::FastaRecord &r : fm.recs) ref_names.push_back(r.id.substr(0, r.id.find_first_of(" \t\r\n\v\f")));
-  std::vector<pbsim_errors_ref> refs;
-  for (size_t r = 0; r < fm.recs.size(); r++) refs.push_back(pbsim_errors_ref{ref_names[r].c_str(), fm.recs[r].lines, fm.recs[r].bytes});
-  pbsim_params p;
-  pbsim_params_default(&p);
-  p.strategy = PBSIM_STRATEGY_WGS;
-  p.method = PBSIM_METHOD_ERR;
-  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
-  if (!ctx) check(0);
-  struct Result {
-    FILE *fp = NULL;
-    bool write_failed = false;
-  } res;
-  if (!out_name.empty()) {
-    res.fp = fopen(out_name.c_str(), "wb");
-    if (!res.fp) die(": Cannot open output file: %s", out_name.c_str());
-  }
-  std::vector<pbsim_errors_file> in(files.size());
-  for (size_t f = 0; f < files.size(); f++) in[f] = pbsim_errors_file{files[f].map, (int64_t)files[f].n, have_names ? names[f].c_str() : NULL};
-  pbsim_pileup_opts opts = {0x900, (int32_t)min_mapq, (int32_t)min_baseq, (int32_t)format, (int64_t)min_depth, 0};
-  pbsim_pileup_sink sink = {&res,
-                            [](void *u, const char *z, int64_t k, int64_t) {
-                              Result *x = (Result *)u;
-                              if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
-                              return x->write_failed ? 0 : 1;
-                            },
-                            NULL};
-  if (!res.fp) sink.on_text = NULL;
-  pbsim_pileup_result result;
-  const bool ok = pbsim_bam_pileup(ctx, refs.data(), (int)refs.size(), in.data(), (int)in.size(), &opts, &sink, &result) != 0;
-  if (res.fp && fclose(res.fp) != 0) res.write_failed = true;
-  if (!ok || res.write_failed) {
-    fprintf(stderr, "ERROR: %s\n", res.write_failed ? ("write error on " + out_name).c_str() : pbsim_last_error());
-    if (in_names.size() > 1)
-      for (size_t f = 0; f < in_names.size(); f++) fprintf(stderr, "ERROR: file %zu is %s\n", f, in_names[f].c_str());
-    if (!out_name.empty()) unlink(out_name.c_str());
-    quit(-1);
-  }
-  std::string text((size_t)pbsim_pileup_report(&result, NULL, 0), '\0');
-  pbsim_pileup_report(&result, &text[0], (int64_t)text.size());
-  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
-  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
-  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
-  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
-  return 0;
-}
-
-// `pbsim --consensus-bam FILE [--consensus-bam FILE ...] --consensus-genome FASTA --consensus-out FILE ...`: the consensus of the
-// aligned reads against their genome (pbsim_bam_consensus), the report to stdout, the FASTA to --consensus-out.  What can be
-// refused from the command line alone is refused before a GPU is touched.
-int consensus_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
-  if (comm && comm->world > 1) die(": --consensus-bam runs on one GPU.");
-  std::vector<std::string> in_names, names;
-  std::string out_name, genome_name, names_arg;
-  bool have_names = false;
-  long long min_mapq = 0, min_baseq = 0, min_depth = 1, fill = 0, exclude = 0x900, max_ins = 1024, line_width = 60;
-  for (int i = 1; i < argc; i++) {
-    const std::string a = argv[i];
-    const bool takes = a == "--consensus-bam" || a == "--consensus-genome" || a == "--consensus-ref-names" || a == "--consensus-out" ||
-                       a == "--consensus-min-mapq" || a == "--consensus-min-baseq" || a == "--consensus-min-depth" || a == "--consensus-exclude-flags" ||
-                       a == "--consensus-fill" || a == "--consensus-max-ins" || a == "--consensus-line-width" || a == "--device";
-    if (!takes)
-      die(" (%s): --consensus-bam takes --consensus-genome, --consensus-out, --consensus-ref-names, --consensus-min-mapq, --consensus-min-baseq, "
-          "--consensus-min-depth, --consensus-exclude-flags, --consensus-fill, --consensus-max-ins, --consensus-line-width and --device, and no other "
-          "option.",
-          argv[i]);
-    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
-    const char *v = argv[++i];
-    if (a == "--consensus-bam") in_names.push_back(v);
-    else if (a == "--consensus-genome") genome_name = v;
-    else if (a == "--consensus-ref-names") names_arg = v, have_names = true;
-    else if (a == "--consensus-out") out_name = v;
-    else if (a == "--device") device = device >= 0 ? device : atoi(v);
-    else if (a == "--consensus-fill") {
-      if (!strcmp(v, "n")) fill = 0;
-      else if (!strcmp(v, "ref")) fill = 1;
-      else die(" (consensus-fill: %s): n or ref.", v);
-    } else if (a == "--consensus-exclude-flags") {
-      const bool hex = v[0] == '0' && (v[1] == 'x' || v[1] == 'X');
-      if (!whole_number(v, hex ? 16 : 10, 0, 65535, &exclude)) die(" (consensus-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535.", v);
-    } else if (a == "--consensus-max-ins") {
-      if (!whole_number(v, 10, 1, 65535, &max_ins)) die(" (consensus-max-ins: %s): a whole number, 1 .. 65535.", v);
-    } else if (a == "--consensus-line-width") {
-      if (!whole_number(v, 10, 0, 1048576, &line_width)) die(" (consensus-line-width: %s): a whole number, 0 .. 1048576 (0: one line per record).", v);
-    } else if (a == "--consensus-min-mapq") {
-      if (!whole_number(v, 10, 0, 255, &min_mapq)) die(" (consensus-min-mapq: %s): a whole number, 0 .. 255.", v);
-    } else if (a == "--consensus-min-baseq") {
-      if (!whole_number(v, 10, 0, 255, &min_baseq)) die(" (consensus-min-baseq: %s): a whole number, 0 .. 255.", v);
-    } else {
-      if (!whole_number(v, 10, 0, 1000000000000LL, &min_depth)) die(" (consensus-min-depth: %s): a whole number, 0 .. 1000000000000.", v);
-    }
-  }
-  if (in_names.empty()) die(": --consensus-bam FILE: name the BAM file.");
-  if (genome_name.empty()) die(": --consensus-bam needs --consensus-genome FASTA: the genome the reads were aligned to.");
-  if (out_name.empty()) die(": --consensus-bam needs --consensus-out FILE: where the consensus FASTA goes.");
-  if (have_names) {
-    for (size_t at = 0;;) {
-      const size_t comma = names_arg.find(',', at);
-      names.push_back(names_arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
-      if (comma == std::string::npos) break;
-      at = comma + 1;
-    }
-    char got[32], want[32];
-    snprintf(got, sizeof got, "%zu", names.size());
-    snprintf(want, sizeof want, "%zu", in_names.size());
-    if (names.size() != in_names.size()) die(" (consensus-ref-names): %s names for %s --consensus-bam files: the k-th name goes to the k-th file.", got, want);
-    for (const std::string &n : names)
-      if (n.empty()) die(" (consensus-ref-names): an empty name.");
-  }
-  std::vector<MappedFile> files(in_names.size());
-  for (size_t f = 0; f < files.size(); f++)
-    if (!files[f].open_file(in_names[f])) die(": Cannot open file: %s", in_names[f].c_str());
-  // the genome, through the input path of --errors-genome: each record's sequence lines, its name the id up to the first white space
-  pbsim::FastaMap fm;
-  {
-    pbsim::GenomeInfo gm;
-    bool fallback = false;
-    std::string err;
-    if (!pbsim::map_genome(genome_name.c_str(), &fm, &gm, false, &fallback, &err))
-      die(": --consensus-genome %s: %s", genome_name.c_str(),
-          fallback ? "not a FASTA file that can be mapped (a regular file that begins with '>' and holds no NUL byte)" : err.c_str());
-  }
-  std::vector<std::string> ref_names;
-  for (const pbsim::FastaRecord &r : fm.recs) ref_names.push_back(r.id.substr(0, r.id.find_first_of(" \t\r\n\v\f")));
-  std::vector<pbsim_errors_ref> refs;
-  for (size_t r = 0; r < fm.recs.size(); r++) refs.push_back(pbsim_errors_ref{ref_names[r].c_str(), fm.recs[r].lines, fm.recs[r].bytes});
-  pbsim_params p;
-  pbsim_params_default(&p);
-  p.strategy = PBSIM_STRATEGY_WGS;
-  p.method = PBSIM_METHOD_ERR;
-  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
-  if (!ctx) check(0);
-  struct Result {
-    FILE *fp = NULL;
-    bool write_failed = false;
-  } res;
-  if (!out_name.empty()) {
-    res.fp = fopen(out_name.c_str(), "wb");
-    if (!res.fp) die(": Cannot open output file: %s", out_name.c_str());
-  }
-  std::vector<pbsim_errors_file> in(files.size());
-  for (size_t f = 0; f < files.size(); f++) in[f] = pbsim_errors_file{files[f].map, (int64_t)files[f].n, have_names ? names[f].c_str() : NULL};
-  pbsim_consensus_opts opts = {(int32_t)exclude, (int32_t)min_mapq, (int32_t)min_baseq, (int32_t)fill, (int64_t)min_depth, (int32_t)max_ins, (int32_t)line_width, 0};
-  pbsim_consensus_sink sink = {&res,
-                            [](void *u, const char *z, int64_t k, int64_t) {
-                              Result *x = (Result *)u;
-                              if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
-                              return x->write_failed ? 0 : 1;
-                            },
-                            NULL};
-  if (!res.fp) sink.on_text = NULL;
-  pbsim_consensus_result result;
-  const bool ok = pbsim_bam_consensus(ctx, refs.data(), (int)refs.size(), in.data(), (int)in.size(), &opts, &sink, &result) != 0;
-  if (res.fp && fclose(res.fp) != 0) res.write_failed = true;
-  if (!ok || res.write_failed) {
-    fprintf(stderr, "ERROR: %s\n", res.write_failed ? ("write error on " + out_name).c_str() : pbsim_last_error());
-    if (in_names.size() > 1)
-      for (size_t f = 0; f < in_names.size(); f++) fprintf(stderr, "ERROR: file %zu is %s\n", f, in_names[f].c_str());
-    if (!out_name.empty()) unlink(out_name.c_str());
-    quit(-1);
-  }
-  std::string text((size_t)pbsim_consensus_report(&result, NULL, 0), '\0');
-  pbsim_consensus_report(&result, &text[0], (int64_t)text.size());
-  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
-  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
-  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
-  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
-  return 0;
-}
-
-// `pbsim --call-bam FILE [--call-bam FILE ...] --call-genome FASTA --call-out FILE ...`: the variants the aligned reads support
-// against their genome (pbsim_bam_call), the report to stdout, the VCF to --call-out.  What can be refused from the command
-// line alone is refused before a GPU is touched.
-int call_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
-  if (comm && comm->world > 1) die(": --call-bam runs on one GPU.");
-  std::vector<std::string> in_names, names;
-  std::string out_name, genome_name, names_arg;
-  bool have_names = false;
-  long long min_mapq = 0, min_baseq = 0, min_depth = 1, exclude = 0x900, max_ins = 1024;
-  for (int i = 1; i < argc; i++) {
-    const std::string a = argv[i];
-    const bool takes = a == "--call-bam" || a == "--call-genome" || a == "--call-ref-names" || a == "--call-out" || a == "--call-min-mapq" ||
-                       a == "--call-min-baseq" || a == "--call-min-depth" || a == "--call-exclude-flags" || a == "--call-max-ins" || a == "--device";
-    if (!takes)
-      die(" (%s): --call-bam takes --call-genome, --call-out, --call-ref-names, --call-min-mapq, --call-min-baseq, --call-min-depth, "
-          "--call-exclude-flags, --call-max-ins and --device, and no other option.",
-          argv[i]);
-    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
-    const char *v = argv[++i];
-    if (a == "--call-bam") in_names.push_back(v);
-    else if (a == "--call-genome") genome_name = v;
-    else if (a == "--call-ref-names") names_arg = v, have_names = true;
-    else if (a == "--call-out") out_name = v;
-    else if (a == "--device") device = device >= 0 ? device : atoi(v);
-    else if (a == "--call-exclude-flags") {
-      const bool hex = v[0] == '0' && (v[1] == 'x' || v[1] == 'X');
-      if (!whole_number(v, hex ? 16 : 10, 0, 65535, &exclude)) die(" (call-exclude-flags: %s): decimal or 0x hexadecimal, 0 .. 65535.", v);
-    } else if (a == "--call-max-ins") {
-      if (!whole_number(v, 10, 1, 65535, &max_ins)) die(" (call-max-ins: %s): a whole number, 1 .. 65535.", v);
-    } else if (a == "--call-min-mapq") {
-      if (!whole_number(v, 10, 0, 255, &min_mapq)) die(" (call-min-mapq: %s): a whole number, 0 .. 255.", v);
-    } else if (a == "--call-min-baseq") {
-      if (!whole_number(v, 10, 0, 255, &min_baseq)) die(" (call-min-baseq: %s): a whole number, 0 .. 255.", v);
-    } else {
-      if (!whole_number(v, 10, 0, 1000000000000LL, &min_depth)) die(" (call-min-depth: %s): a whole number, 0 .. 1000000000000.", v);
-    }
-  }
-  if (in_names.empty()) die(": --call-bam FILE: name the BAM file.");
-  if (genome_name.empty()) die(": --call-bam needs --call-genome FASTA: the genome the reads were aligned to.");
-  if (out_name.empty()) die(": --call-bam needs --call-out FILE: where the VCF goes.");
-  if (have_names) {
-    for (size_t at = 0;;) {
-      const size_t comma = names_arg.find(',', at);
-      names.push_back(names_arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
-      if (comma == std::string::npos) break;
-      at = comma + 1;
-    }
-    char got[32], want[32];
-    snprintf(got, sizeof got, "%zu", names.size());
-    snprintf(want, sizeof want, "%zu", in_names.size());
-    if (names.size() != in_names.size()) die(" (call-ref-names): %s names for %s --call-bam files: the k-th name goes to the k-th file.", got, want);
-    for (const std::string &n : names)
-      if (n.empty()) die(" (call-ref-names): an empty name.");
-  }
-  std::vector<MappedFile> files(in_names.size());
-  for (size_t f = 0; f < files.size(); f++)
-    if (!files[f].open_file(in_names[f])) die(": Cannot open file: %s", in_names[f].c_str());
-  // the genome, through the input path of --errors-genome: each record's sequence lines, its name the id up to the first white space
-  pbsim::FastaMap fm;
-  {
-    pbsim::GenomeInfo gm;
-    bool fallback = false;
-    std::string err;
-    if (!pbsim::map_genome(genome_name.c_str(), &fm, &gm, false, &fallback, &err))
-      die(": --call-genome %s: %s", genome_name.c_str(),
-          fallback ? "not a FASTA file that can be mapped (a regular file that begins with '>' and holds no NUL byte)" : err.c_str());
-  }
-  std::vector<std::string> ref_names;
-  for (const pbsim::FastaRecord &r : fm.recs) ref_names.push_back(r.id.substr(0, r.id.find_first_of(" \t\r\n\v\f")));
-  std::vector<pbsim_errors_ref> refs;
-  for (size_t r = 0; r < fm.recs.size(); r++) refs.push_back(pbsim_errors_ref{ref_names[r].c_str(), fm.recs[r].lines, fm.recs[r].bytes});
-  pbsim_params p;
-  pbsim_params_default(&p);
-  p.strategy = PBSIM_STRATEGY_WGS;
-  p.method = PBSIM_METHOD_ERR;
-  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
-  if (!ctx) check(0);
-  struct Result {
-    FILE *fp = NULL;
-    bool write_failed = false;
-  } res;
-  if (!out_name.empty()) {
-    res.fp = fopen(out_name.c_str(), "wb");
-    if (!res.fp) die(": Cannot open output file: %s", out_name.c_str());
-  }
-  std::vector<pbsim_errors_file> in(files.size());
-  for (size_t f = 0; f < files.size(); f++) in[f] = pbsim_errors_file{files[f].map, (int64_t)files[f].n, have_names ? names[f].c_str() : NULL};
-  pbsim_call_opts opts = {(int32_t)exclude, (int32_t)min_mapq, (int32_t)min_baseq, (int32_t)max_ins, (int64_t)min_depth, 0};
-  pbsim_call_sink sink = {&res,
-                            [](void *u, const char *z, int64_t k, int64_t) {
-                              Result *x = (Result *)u;
-                              if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
-                              return x->write_failed ? 0 : 1;
-                            },
-                            NULL};
-  if (!res.fp) sink.on_text = NULL;
-  pbsim_call_result result;
-  const bool ok = pbsim_bam_call(ctx, refs.data(), (int)refs.size(), in.data(), (int)in.size(), &opts, &sink, &result) != 0;
-  if (res.fp && fclose(res.fp) != 0) res.write_failed = true;
-  if (!ok || res.write_failed) {
-    fprintf(stderr, "ERROR: %s\n", res.write_failed ? ("write error on " + out_name).c_str() : pbsim_last_error());
-    if (in_names.size() > 1)
-      for (size_t f = 0; f < in_names.size(); f++) fprintf(stderr, "ERROR: file %zu is %s\n", f, in_names[f].c_str());
-    if (!out_name.empty()) unlink(out_name.c_str());
-    quit(-1);
-  }
-  std::string text((size_t)pbsim_call_report(&result, NULL, 0), '\0');
-  pbsim_call_report(&result, &text[0], (int64_t)text.size());
-  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
-  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
-  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
-  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
-  return 0;
-}
-
-// `pbsim --mutate-genome FASTA --mutate-out FASTA --mutate-vcf FILE ...`: a variant genome and its truth variants drawn from the
-// genome and a seed (pbsim_genome_mutate), the report to stdout, the variant genome to --mutate-out, the VCF to --mutate-vcf.  What
-// can be refused from the command line alone is refused before a GPU is touched.
-int mutate_genome_main(int argc, char **argv, const pbsim_comm *comm, int device) {
-  if (comm && comm->world > 1) die(": --mutate-genome runs on one GPU.");
-  std::string genome_name, out_name, vcf_name;
-  long long seed = 1, snv = 1000, ins = 100, del = 100, ext = 500000, max_indel = 50, line_width = 60;
-  for (int i = 1; i < argc; i++) {
-    const std::string a = argv[i];
-    const bool takes = a == "--mutate-genome" || a == "--mutate-out" || a == "--mutate-vcf" || a == "--mutate-seed" || a == "--mutate-snv-ppm" ||
-                       a == "--mutate-ins-ppm" || a == "--mutate-del-ppm" || a == "--mutate-ext-ppm" || a == "--mutate-max-indel" ||
-                       a == "--mutate-line-width" || a == "--device";
-    if (!takes)
-      die(" (%s): --mutate-genome takes --mutate-out, --mutate-vcf, --mutate-seed, --mutate-snv-ppm, --mutate-ins-ppm, --mutate-del-ppm, "
-          "--mutate-ext-ppm, --mutate-max-indel, --mutate-line-width and --device, and no other option.",
-          argv[i]);
-    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
-    const char *v = argv[++i];
-    if (a == "--mutate-genome") genome_name = v;
-    else if (a == "--mutate-out") out_name = v;
-    else if (a == "--mutate-vcf") vcf_name = v;
-    else if (a == "--device") device = device >= 0 ? device : atoi(v);
-    else if (a == "--mutate-seed") {
-      if (!whole_number(v, 10, 0, 4294967295LL, &seed)) die(" (mutate-seed: %s): a whole number, 0 .. 4294967295.", v);
-    } else if (a == "--mutate-ext-ppm") {
-      if (!whole_number(v, 10, 0, 999999, &ext)) die(" (mutate-ext-ppm: %s): a whole number, 0 .. 999999.", v);
-    } else if (a == "--mutate-max-indel") {
-      if (!whole_number(v, 10, 1, 65535, &max_indel)) die(" (mutate-max-indel: %s): a whole number, 1 .. 65535.", v);
-    } else if (a == "--mutate-line-width") {
-      if (!whole_number(v, 10, 0, 1048576, &line_width)) die(" (mutate-line-width: %s): a whole number, 0 .. 1048576 (0: one line per record).", v);
-    } else {
-      long long *to = a == "--mutate-snv-ppm" ? &snv : a == "--mutate-ins-ppm" ? &ins : &del;
-      if (!whole_number(v, 10, 0, 1000000, to)) die(" (%s: %s): a whole number, 0 .. 1000000.", a.c_str() + 2, v);
-    }
-  }
-  if (genome_name.empty()) die(": --mutate-genome FASTA: name the genome.");
-  if (out_name.empty()) die(": --mutate-genome needs --mutate-out FASTA: where the variant genome goes.");
-  if (vcf_name.empty()) die(": --mutate-genome needs --mutate-vcf FILE: where the truth variants go.");
-  if (snv + ins + del > 1000000) die(" (mutate-snv-ppm + mutate-ins-ppm + mutate-del-ppm): the three rates sum to more than 1000000.");
-  if (access(genome_name.c_str(), R_OK) != 0) die(": --mutate-genome %s: Cannot open file: %s", genome_name.c_str(), genome_name.c_str());
-  pbsim_params p;
-  pbsim_params_default(&p);
-  p.strategy = PBSIM_STRATEGY_WGS;
-  p.method = PBSIM_METHOD_ERR;
-  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
-  if (!ctx) check(0);
-  // the genome, through the input path of --errors-genome: each record's sequence lines, its name the id up to the first white
-  // space; the context is there first, since a BGZF file is inflated on its device
-  pbsim::FastaMap fm;
-  {
-    pbsim::GenomeInfo gm;
-    bool fallback = false;
-    std::string err;
-    pbsim::set_input_context(ctx);
-    const bool mapped = pbsim::map_genome(genome_name.c_str(), &fm, &gm, false, &fallback, &err);
-    pbsim::set_input_context(nullptr);
-    if (!mapped)
-      die(": --mutate-genome %s: %s", genome_name.c_str(),
-          fallback ? "not a FASTA file that can be mapped (a regular file that begins with '>' and holds no NUL byte)" : err.c_str());
-  }
-  std::vector<std::string> ref_names;
-  for (const pbsim::FastaRecord &r : fm.recs) ref_names.push_back(r.id.substr(0, r.id.find_first_of(" \t\r\n\v\f")));
-  std::vector<pbsim_errors_ref> refs;
-  for (size_t r = 0; r < fm.recs.size(); r++) refs.push_back(pbsim_errors_ref{ref_names[r].c_str(), fm.recs[r].lines, fm.recs[r].bytes});
-  struct Out {
-    FILE *fp = NULL;
-    bool write_failed = false;
-  } fasta, vcf;
-  fasta.fp = fopen(out_name.c_str(), "wb");
-  if (!fasta.fp) die(": Cannot open output file: %s", out_name.c_str());
-  vcf.fp = fopen(vcf_name.c_str(), "wb");
-  if (!vcf.fp) {
-    fclose(fasta.fp);
-    unlink(out_name.c_str());
-    die(": Cannot open output file: %s", vcf_name.c_str());
-  }
-  struct Both {
-    Out *fasta, *vcf;
-  } both = {&fasta, &vcf};
-  pbsim_mutate_opts opts = {(uint32_t)seed, (int32_t)snv, (int32_t)ins, (int32_t)del, (int32_t)ext, (int32_t)max_indel, (int32_t)line_width, 0};
-  pbsim_mutate_sink sink = {&both,
-                            [](void *u, const char *z, int64_t k, int64_t) {
-                              Out *x = ((Both *)u)->fasta;
-                              if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
-                              return x->write_failed ? 0 : 1;
-                            },
-                            [](void *u, const char *z, int64_t k, int64_t) {
-                              Out *x = ((Both *)u)->vcf;
-                              if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
-                              return x->write_failed ? 0 : 1;
-                            },
-                            NULL, NULL};
-  pbsim_mutate_result result;
-  const bool ok = pbsim_genome_mutate(ctx, refs.data(), (int)refs.size(), &opts, &sink, &result) != 0;
-  if (fclose(fasta.fp) != 0) fasta.write_failed = true;
-  if (fclose(vcf.fp) != 0) vcf.write_failed = true;
-  if (!ok || fasta.write_failed || vcf.write_failed) {
-    fprintf(stderr, "ERROR: %s\n",
-            fasta.write_failed ? ("write error on " + out_name).c_str() : vcf.write_failed ? ("write error on " + vcf_name).c_str() : pbsim_last_error());
-    unlink(out_name.c_str());
-    unlink(vcf_name.c_str());
-    quit(-1);
-  }
-  std::string text((size_t)pbsim_mutate_report(&result, NULL, 0), '\0');
-  pbsim_mutate_report(&result, &text[0], (int64_t)text.size());
-  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
-  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
-  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
-  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
-  return 0;
-}
-
-// `pbsim --compare-vcf CALLS --compare-truth TRUTH --compare-genome FASTA ...`: a call set scored against the truth variants
-// (pbsim_vcf_compare), the report to stdout, the annotated lines to --compare-out.  What can be refused from the command line
-// alone is refused before a GPU is touched.  The context is made before the files are read: a BGZF file is inflated on its device.
-int compare_vcf_main(int argc, char **argv, const pbsim_comm *comm, int device) {
-  if (comm && comm->world > 1) die(": --compare-vcf runs on one GPU.");
-  std::string calls_name, truth_name, genome_name, out_name, names_arg;
-  std::vector<std::string> names;
-  bool have_names = false;
-  long long lines = 0, min_ms = 0;
-  for (int i = 1; i < argc; i++) {
-    const std::string a = argv[i];
-    const bool takes = a == "--compare-vcf" || a == "--compare-truth" || a == "--compare-genome" || a == "--compare-out" || a == "--compare-lines" ||
-                       a == "--compare-min-ms" || a == "--compare-ref-names" || a == "--device";
-    if (!takes)
-      die(" (%s): --compare-vcf takes --compare-truth, --compare-genome, --compare-out, --compare-lines, --compare-min-ms, --compare-ref-names "
-          "and --device, and no other option.",
-          argv[i]);
-    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
-    const char *v = argv[++i];
-    if (a == "--compare-vcf") calls_name = v;
-    else if (a == "--compare-truth") truth_name = v;
-    else if (a == "--compare-genome") genome_name = v;
-    else if (a == "--compare-out") out_name = v;
-    else if (a == "--compare-ref-names") names_arg = v, have_names = true;
-    else if (a == "--device") device = device >= 0 ? device : atoi(v);
-    else if (a == "--compare-lines") {
-      if (strcmp(v, "discordant") && strcmp(v, "all")) die(" (compare-lines: %s): discordant or all.", v);
-      lines = !strcmp(v, "all");
-    } else {
-      if (!whole_number(v, 10, 0, 2147483647LL, &min_ms)) die(" (compare-min-ms: %s): a whole number, 0 .. 2147483647.", v);
-    }
-  }
-  if (calls_name.empty()) die(": --compare-vcf CALLS: name the call set.");
-  if (truth_name.empty()) die(": --compare-vcf needs --compare-truth VCF: the truth variants.");
-  if (genome_name.empty()) die(": --compare-vcf needs --compare-genome FASTA: the genome both files speak of.");
-  if (have_names) {
-    for (size_t at = 0;;) {
-      const size_t comma = names_arg.find(',', at);
-      names.push_back(names_arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
-      if (comma == std::string::npos) break;
-      at = comma + 1;
-    }
-    for (const std::string &n : names)
-      if (n.empty()) die(" (compare-ref-names): an empty name.");
-  }
-  for (const std::string *name : {&calls_name, &truth_name, &genome_name})
-    if (access(name->c_str(), R_OK) != 0) die(": Cannot open file: %s", name->c_str());
-  pbsim_params p;
-  pbsim_params_default(&p);
-  p.strategy = PBSIM_STRATEGY_WGS;
-  p.method = PBSIM_METHOD_ERR;
-  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
-  if (!ctx) check(0);
-  pbsim::set_input_context(ctx);
-  // a VCF: the inflated bytes of a gzip file, else the file as it is (an empty one has no lines)
-  struct Vcf {
-    pbsim::InputBytes gz;
-    MappedFile plain;
-    const void *bytes = NULL;
-    int64_t n = 0;
-  } vcf[2];
-  const std::string *vcf_name[2] = {&truth_name, &calls_name};
-  for (int w = 0; w < 2; w++) {
-    std::string err;
-    const int g = pbsim::open_input(vcf_name[w]->c_str(), &vcf[w].gz, &err);
-    if (g < 0) die(": %s", err.c_str());
-    if (g > 0) {
-      vcf[w].bytes = vcf[w].gz.map, vcf[w].n = (int64_t)vcf[w].gz.size;
-      continue;
-    }
-    struct stat sb;
-    if (stat(vcf_name[w]->c_str(), &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size == 0) continue;
-    if (!vcf[w].plain.open_file(*vcf_name[w])) die(": Cannot open file: %s", vcf_name[w]->c_str());
-    vcf[w].bytes = vcf[w].plain.map, vcf[w].n = (int64_t)vcf[w].plain.n;
-  }
-  pbsim::FastaMap fm;
-  {
-    pbsim::GenomeInfo gm;
-    bool fallback = false;
-    std::string err;
-    const bool mapped = pbsim::map_genome(genome_name.c_str(), &fm, &gm, false, &fallback, &err);
-    if (!mapped)
-      die(": --compare-genome %s: %s", genome_name.c_str(),
-          fallback ? "not a FASTA file that can be mapped (a regular file that begins with '>' and holds no NUL byte)" : err.c_str());
-  }
-  pbsim::set_input_context(nullptr);
-  std::vector<std::string> own_names;
-  for (const pbsim::FastaRecord &r : fm.recs) own_names.push_back(r.id.substr(0, r.id.find_first_of(" \t\r\n\v\f")));
-  std::vector<pbsim_errors_ref> refs;
-  for (size_t r = 0; r < fm.recs.size(); r++) refs.push_back(pbsim_errors_ref{own_names[r].c_str(), fm.recs[r].lines, fm.recs[r].bytes});
-  std::vector<const char *> used;
-  if (have_names) {
-    char got[32], want[32];
-    snprintf(got, sizeof got, "%zu", names.size());
-    snprintf(want, sizeof want, "%zu", refs.size());
-    if (names.size() != refs.size()) die(" (compare-ref-names): %s names for %s genome records: the k-th name goes to the k-th record.", got, want);
-    for (const std::string &n : names) used.push_back(n.c_str());
-  }
-  struct Result {
-    FILE *fp = NULL;
-    bool write_failed = false;
-  } res;
-  if (!out_name.empty()) {
-    res.fp = fopen(out_name.c_str(), "wb");
-    if (!res.fp) die(": Cannot open output file: %s", out_name.c_str());
-  }
-  pbsim_compare_opts opts = {(int32_t)lines, (int32_t)min_ms, 0};
-  pbsim_compare_sink sink = {&res, [](void *u, const char *z, int64_t k, int64_t) {
-                               Result *x = (Result *)u;
-                               if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
-                               return x->write_failed ? 0 : 1;
-                             }};
-  if (!res.fp) sink.on_text = NULL;
-  pbsim_compare_result result;
-  const bool ok = pbsim_vcf_compare(ctx, refs.data(), (int)refs.size(), have_names ? used.data() : NULL, vcf[0].bytes, vcf[0].n, vcf[1].bytes, vcf[1].n, &opts,
-                                    &sink, &result) != 0;
-  if (res.fp && fclose(res.fp) != 0) res.write_failed = true;
-  if (!ok || res.write_failed) {
-    fprintf(stderr, "ERROR: %s\n", res.write_failed ? ("write error on " + out_name).c_str() : pbsim_last_error());
-    if (!out_name.empty()) unlink(out_name.c_str());
-    quit(-1);
-  }
-  std::string text((size_t)pbsim_compare_report(&result, NULL, 0), '\0');
-  pbsim_compare_report(&result, &text[0], (int64_t)text.size());
-  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
-  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
-  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
-  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
-  return 0;
-}
-
-// `pbsim --apply-vcf VCF --apply-genome FASTA --apply-out FASTA ...`: the lines of a VCF applied to the genome (pbsim_vcf_apply),
-// the summary to stdout, the spliced genome to --apply-out, the annotated lines to --apply-report, the origin map to
-// --apply-origin.  What can be refused from the command line alone is refused before a GPU is touched.  The context is made before
-// the files are read: a BGZF file is inflated on its device.
-int apply_vcf_main(int argc, char **argv, const pbsim_comm *comm, int device) {
-  if (comm && comm->world > 1) die(": --apply-vcf runs on one GPU.");
-  std::string vcf_name, genome_name, out_name, report_name, origin_name, names_arg, sample_name;
-  std::vector<std::string> names;
-  bool have_names = false;
-  long long haplotype = 0, sample = 0, lines = 0, line_width = 60;
-  for (int i = 1; i < argc; i++) {
-    const std::string a = argv[i];
-    const bool takes = a == "--apply-vcf" || a == "--apply-genome" || a == "--apply-out" || a == "--apply-ref-names" || a == "--apply-haplotype" ||
-                       a == "--apply-sample" || a == "--apply-report" || a == "--apply-lines" || a == "--apply-line-width" || a == "--apply-origin" ||
-                       a == "--device";
-    if (!takes)
-      die(" (%s): --apply-vcf takes --apply-genome, --apply-out, --apply-ref-names, --apply-haplotype, --apply-sample, --apply-report, --apply-lines, "
-          "--apply-line-width, --apply-origin and --device, and no other option.",
-          argv[i]);
-    if (i + 1 >= argc) die(" (%s): the option needs a value.", argv[i]);
-    const char *v = argv[++i];
-    if (a == "--apply-vcf") vcf_name = v;
-    else if (a == "--apply-genome") genome_name = v;
-    else if (a == "--apply-out") out_name = v;
-    else if (a == "--apply-report") report_name = v;
-    else if (a == "--apply-origin") origin_name = v;
-    else if (a == "--apply-ref-names") names_arg = v, have_names = true;
-    else if (a == "--device") device = device >= 0 ? device : atoi(v);
-    else if (a == "--apply-haplotype") {
-      if (!whole_number(v, 10, 0, 2, &haplotype)) die(" (apply-haplotype: %s): 0 (the first ALT of every line), 1 or 2.", v);
-    } else if (a == "--apply-sample") {
-      if (!*v) die(" (apply-sample): a 0-based sample column or a sample's name.");
-      sample_name.clear();
-      if (!whole_number(v, 10, 0, 2147483647LL, &sample)) sample_name = v, sample = 0;
-    } else if (a == "--apply-lines") {
-      if (strcmp(v, "discordant") && strcmp(v, "all")) die(" (apply-lines: %s): discordant or all.", v);
-      lines = !strcmp(v, "all");
-    } else {
-      if (!whole_number(v, 10, 0, 1048576, &line_width)) die(" (apply-line-width: %s): a whole number, 0 .. 1048576 (0: one line per record).", v);
-    }
-  }
-  if (vcf_name.empty()) die(": --apply-vcf VCF: name the variants.");
-  if (genome_name.empty()) die(": --apply-vcf needs --apply-genome FASTA: the genome the file speaks of.");
-  if (out_name.empty()) die(": --apply-vcf needs --apply-out FASTA: where the spliced genome goes.");
-  if (have_names) {
-    for (size_t at = 0;;) {
-      const size_t comma = names_arg.find(',', at);
-      names.push_back(names_arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
-      if (comma == std::string::npos) break;
-      at = comma + 1;
-    }
-    for (const std::string &n : names)
-      if (n.empty()) die(" (apply-ref-names): an empty name.");
-  }
-  for (const std::string *name : {&vcf_name, &genome_name})
-    if (access(name->c_str(), R_OK) != 0) die(": Cannot open file: %s", name->c_str());
-  pbsim_params p;
-  pbsim_params_default(&p);
-  p.strategy = PBSIM_STRATEGY_WGS;
-  p.method = PBSIM_METHOD_ERR;
-  pbsim_ctx *ctx = pbsim_create(&p, device >= 0 ? device : 0);
-  if (!ctx) check(0);
-  pbsim::set_input_context(ctx);
-  // the VCF: the inflated bytes of a gzip file, else the file as it is (an empty one has no lines)
-  struct Vcf {
-    pbsim::InputBytes gz;
-    MappedFile plain;
-    const void *bytes = NULL;
-    int64_t n = 0;
-  } vcf;
-  {
-    std::string err;
-    const int g = pbsim::open_input(vcf_name.c_str(), &vcf.gz, &err);
-    if (g < 0) die(": %s", err.c_str());
-    struct stat sb;
-    if (g > 0) {
-      vcf.bytes = vcf.gz.map, vcf.n = (int64_t)vcf.gz.size;
-    } else if (!(stat(vcf_name.c_str(), &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size == 0)) {
-      if (!vcf.plain.open_file(vcf_name)) die(": Cannot open file: %s", vcf_name.c_str());
-      vcf.bytes = vcf.plain.map, vcf.n = (int64_t)vcf.plain.n;
-    }
-  }
-  pbsim::FastaMap fm;
-  {
-    pbsim::GenomeInfo gm;
-    bool fallback = false;
-    std::string err;
-    const bool mapped = pbsim::map_genome(genome_name.c_str(), &fm, &gm, false, &fallback, &err);
-    if (!mapped)
-      die(": --apply-genome %s: %s", genome_name.c_str(),
-          fallback ? "not a FASTA file that can be mapped (a regular file that begins with '>' and holds no NUL byte)" : err.c_str());
-  }
-  pbsim::set_input_context(nullptr);
-  if (!sample_name.empty()) {
-    const int32_t column = pbsim_apply_sample(vcf.bytes, vcf.n, sample_name.c_str());
-    if (column < 0) die(" (apply-sample: %s): the #CHROM line of %s names no such sample.", sample_name.c_str(), vcf_name.c_str());
-    sample = column;
-  }
-  std::vector<std::string> own_names;
-  for (const pbsim::FastaRecord &r : fm.recs) own_names.push_back(r.id.substr(0, r.id.find_first_of(" \t\r\n\v\f")));
-  std::vector<pbsim_errors_ref> refs;
-  for (size_t r = 0; r < fm.recs.size(); r++) refs.push_back(pbsim_errors_ref{own_names[r].c_str(), fm.recs[r].lines, fm.recs[r].bytes});
-  std::vector<const char *> used;
-  if (have_names) {
-    char got[32], want[32];
-    snprintf(got, sizeof got, "%zu", names.size());
-    snprintf(want, sizeof want, "%zu", refs.size());
-    if (names.size() != refs.size()) die(" (apply-ref-names): %s names for %s genome records: the k-th name goes to the k-th record.", got, want);
-    for (const std::string &n : names) used.push_back(n.c_str());
-  }
-  struct Out {
-    FILE *fp = NULL;
-    bool write_failed = false;
-    const std::string *name = NULL;
-  } fasta, report, origin;
-  fasta.name = &out_name, report.name = &report_name, origin.name = &origin_name;
-  Out *outs[3] = {&fasta, &report, &origin};
-  auto drop = [&]() {
-    for (Out *x : outs)
-      if (!x->name->empty()) unlink(x->name->c_str());
-  };
-  for (Out *x : outs) {
-    if (x->name->empty()) continue;
-    x->fp = fopen(x->name->c_str(), "wb");
-    if (x->fp) continue;
-    for (Out *y : outs)
-      if (y->fp) fclose(y->fp), unlink(y->name->c_str());
-    die(": Cannot open output file: %s", x->name->c_str());
-  }
-  struct All {
-    Out *fasta, *report, *origin;
-  } all = {&fasta, &report, &origin};
-  pbsim_apply_opts opts = {(int32_t)haplotype, (int32_t)sample, (int32_t)lines, (int32_t)line_width, 0};
-  pbsim_apply_sink sink = {&all,
-                           [](void *u, const char *z, int64_t k, int64_t) {
-                             Out *x = ((All *)u)->fasta;
-                             if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
-                             return x->write_failed ? 0 : 1;
-                           },
-                           [](void *u, const char *z, int64_t k, int64_t) {
-                             Out *x = ((All *)u)->report;
-                             if (fwrite(z, 1, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
-                             return x->write_failed ? 0 : 1;
-                           },
-                           NULL,
-                           [](void *u, int32_t, const int32_t *z, int64_t k) {
-                             Out *x = ((All *)u)->origin;
-                             if (fwrite(z, 4, (size_t)k, x->fp) != (size_t)k) x->write_failed = true;
-                             return x->write_failed ? 0 : 1;
-                           }};
-  if (!report.fp) sink.on_text = NULL;
-  if (!origin.fp) sink.on_origin = NULL;
-  pbsim_apply_result result;
-  const bool ok = pbsim_vcf_apply(ctx, refs.data(), (int)refs.size(), have_names ? used.data() : NULL, vcf.bytes, vcf.n, &opts, &sink, &result) != 0;
-  const Out *failed = NULL;
-  for (Out *x : outs) {
-    if (x->fp && fclose(x->fp) != 0) x->write_failed = true;
-    if (x->write_failed && !failed) failed = x;
-  }
-  if (!ok || failed) {
-    fprintf(stderr, "ERROR: %s\n", failed ? ("write error on " + *failed->name).c_str() : pbsim_last_error());
-    drop();
-    quit(-1);
-  }
-  std::string text((size_t)pbsim_apply_report(&result, NULL, 0), '\0');
-  pbsim_apply_report(&result, &text[0], (int64_t)text.size());
-  const bool wrote = fwrite(text.data(), 1, text.size(), stdout) == text.size();
-  if (fflush(stdout) != 0 || !wrote) die(": write error on the standard output");
-  const char *leave = getenv("PBSIM_CLI_LEAVE_CONTEXT");
-  if (!(leave && *leave == '1')) pbsim_destroy(ctx);
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int pbsim_cli_main(int argc, char **argv, const pbsim_comm *comm, int device) {
   struct timeval tv0;
   gettimeofday(&tv0, NULL);
-  for (int i = 1; i < argc; i++)
-    if (!strcmp(argv[i], "--eval-bam")) return eval_bam_main(argc, argv, comm, device);
-  for (int i = 1; i < argc; i++)
-    if (!strcmp(argv[i], "--depth-bam")) return depth_bam_main(argc, argv, comm, device);
-  for (int i = 1; i < argc; i++)
-    if (!strcmp(argv[i], "--stats-bam")) return stats_bam_main(argc, argv, comm, device);
-  for (int i = 1; i < argc; i++)
-    if (!strcmp(argv[i], "--errors-bam")) return errors_bam_main(argc, argv, comm, device);
-  for (int i = 1; i < argc; i++)
-    if (!strcmp(argv[i], "--pileup-bam")) return pileup_bam_main(argc, argv, comm, device);
-  for (int i = 1; i < argc; i++)
-    if (!strcmp(argv[i], "--consensus-bam")) return consensus_bam_main(argc, argv, comm, device);
-  for (int i = 1; i < argc; i++)
-    if (!strcmp(argv[i], "--call-bam")) return call_bam_main(argc, argv, comm, device);
-  for (int i = 1; i < argc; i++)
-    if (!strcmp(argv[i], "--mutate-genome")) return mutate_genome_main(argc, argv, comm, device);
-  for (int i = 1; i < argc; i++)
-    if (!strcmp(argv[i], "--compare-vcf")) return compare_vcf_main(argc, argv, comm, device);
-  for (int i = 1; i < argc; i++)
-    if (!strcmp(argv[i], "--apply-vcf")) return apply_vcf_main(argc, argv, comm, device);
+  // a stand-alone mode (cli_stages.cpp): the first of the list that the line names
+  for (const pbsim::cli::StageMode *m = pbsim::cli::stage_modes(); m->option; m++)
+    for (int i = 1; i < argc; i++)
+      if (!strcmp(argv[i], m->option)) return m->run(argc, argv, comm, device);
   if (argc >= 2 && !strcmp(argv[1], "--sort-truth-bam")) {
     // the standalone mode: no simulation, the named files sorted and indexed in place on one GPU
     if (comm && comm->world > 1) die(": --sort-truth-bam runs on one GPU.");

@@ -15,16 +15,16 @@
 //                                     rendezvous file of the launch's own under /dev/shm (or $TMPDIR); exit status = the first
 //                                     child's that is not 0
 //   pbsim --sort-truth-bam FILE ..   no simulation: finished truth BAMs sorted by coordinate and indexed in place (cli.cpp)
-//   pbsim --eval-bam MAPPED.bam --truth-bam FILE ..   no simulation: a mapper's BAM scored against truth BAMs (cli.cpp)
-//   pbsim --depth-bam FILE --depth-out FILE ..   no simulation: the depth of coverage of a BAM (cli.cpp)
-//   pbsim --stats-bam FILE [--stats-bam FILE ..]   no simulation: the reads of BAM files summarised (cli.cpp)
-//   pbsim --errors-bam FILE [--errors-bam FILE ..] --errors-genome FASTA   no simulation: the aligned reads' errors against their genome (cli.cpp)
-//   pbsim --pileup-bam FILE [--pileup-bam FILE ..] --pileup-genome FASTA   no simulation: the pileup of the aligned reads against their genome (cli.cpp)
-//   pbsim --consensus-bam FILE [--consensus-bam FILE ..] --consensus-genome FASTA --consensus-out FILE   no simulation: the consensus FASTA of the aligned reads (cli.cpp)
-//   pbsim --call-bam FILE [--call-bam FILE ..] --call-genome FASTA --call-out FILE   no simulation: the variants the aligned reads support, as VCF (cli.cpp)
-//   pbsim --mutate-genome FASTA --mutate-out FASTA --mutate-vcf FILE   no simulation: a variant genome and its truth variants drawn from a seed (cli.cpp)
-//   pbsim --compare-vcf CALLS --compare-truth TRUTH --compare-genome FASTA   no simulation: a call set scored against the truth variants (cli.cpp)
-//   pbsim --apply-vcf VCF --apply-genome FASTA --apply-out FASTA   no simulation: the lines of a VCF applied to the genome, per haplotype (cli.cpp)
+//   pbsim --eval-bam MAPPED.bam --truth-bam FILE ..   no simulation: a mapper's BAM scored against truth BAMs (cli_stages.cpp)
+//   pbsim --depth-bam FILE --depth-out FILE ..   no simulation: the depth of coverage of a BAM (cli_stages.cpp)
+//   pbsim --stats-bam FILE [--stats-bam FILE ..]   no simulation: the reads of BAM files summarised (cli_stages.cpp)
+//   pbsim --errors-bam FILE [--errors-bam FILE ..] --errors-genome FASTA   no simulation: the aligned reads' errors against their genome (cli_stages.cpp)
+//   pbsim --pileup-bam FILE [--pileup-bam FILE ..] --pileup-genome FASTA   no simulation: the pileup of the aligned reads against their genome (cli_stages.cpp)
+//   pbsim --consensus-bam FILE [--consensus-bam FILE ..] --consensus-genome FASTA --consensus-out FILE   no simulation: the consensus FASTA of the aligned reads (cli_stages.cpp)
+//   pbsim --call-bam FILE [--call-bam FILE ..] --call-genome FASTA --call-out FILE   no simulation: the variants the aligned reads support, as VCF (cli_stages.cpp)
+//   pbsim --mutate-genome FASTA --mutate-out FASTA --mutate-vcf FILE   no simulation: a variant genome and its truth variants drawn from a seed (cli_stages.cpp)
+//   pbsim --compare-vcf CALLS --compare-truth TRUTH --compare-genome FASTA   no simulation: a call set scored against the truth variants (cli_stages.cpp)
+//   pbsim --apply-vcf VCF --apply-genome FASTA --apply-out FASTA   no simulation: the lines of a VCF applied to the genome, per haplotype (cli_stages.cpp)
 // Every rank runs the same pbsim_cli_main(argv): the job is deterministic in the values the ranks exchange, so they stay
 // in lockstep; rank 0 prints the report and creates the files, every rank writes its own byte ranges.
 #include <hip/hip_runtime.h>
@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "../../include/pbsim3_amd.h"
+#include "cli_stages.h"
 #include "rccl_comm.h"
 #include "thread_comm.h"
 
@@ -95,14 +96,15 @@ int main(int argc, char **argv) {
     }
   }
   {
-    // --eval-bam, --depth-bam, --stats-bam, --errors-bam, --pileup-bam, --consensus-bam, --call-bam, --mutate-genome, --compare-vcf and --apply-vcf are modes of one GPU: the options that start several ranks are refused beside them
+    // the stand-alone modes (cli_stages.h: --eval-bam .. --apply-vcf) are modes of one GPU: the options that start several ranks are
+    // refused beside them
+#define PBSIM_STAGE_OPTION(option, run) option,
+    const char *const stage_options[] = {PBSIM_STAGE_MODES(PBSIM_STAGE_OPTION)};
     const char *mode = nullptr;
     bool ranks = false;
     for (int i = 1; i < argc; i++) {
-      if (!mode && (!strcmp(argv[i], "--eval-bam") || !strcmp(argv[i], "--depth-bam") || !strcmp(argv[i], "--stats-bam") || !strcmp(argv[i], "--errors-bam") ||
-                    !strcmp(argv[i], "--pileup-bam") || !strcmp(argv[i], "--consensus-bam") || !strcmp(argv[i], "--call-bam") ||
-                    !strcmp(argv[i], "--mutate-genome") || !strcmp(argv[i], "--compare-vcf") || !strcmp(argv[i], "--apply-vcf")))
-        mode = argv[i];
+      for (const char *o : stage_options)
+        if (!mode && !strcmp(argv[i], o)) mode = argv[i];
       for (const char *o : {"--devices", "--processes", "--rank", "--world", "--rendezvous", "--comm", "--comm-selftest"})
         if (!strcmp(argv[i], o) || (!strncmp(argv[i], o, strlen(o)) && argv[i][strlen(o)] == '=')) ranks = true;
     }
