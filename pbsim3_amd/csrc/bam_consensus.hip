@@ -32,6 +32,7 @@ using namespace pilewalk;
 
 constexpr int kLogBlocksMax = 4096;   // workgroups over a log: their lanes stride over the entries
 constexpr int kBaseBlocksMax = 2048;  // workgroups of the base pass: they stride over the tiles
+constexpr int kLogSizeBlocksMax = 1024;  // workgroups of the log-size pass: their lanes stride over the records
 static_assert(kConsTile == kThreads, "a tile is one workgroup's positions");
 
 __device__ __forceinline__ bool ins_site(uint32_t c) { return c != (uint32_t)kPileNoSite && (c & kPileInsBit) != 0; }
@@ -227,7 +228,7 @@ inline int64_t tiles_of(const PileGenome &g) { return (g.total + kConsTile - 1) 
 
 void launch_consensus_log_size(ErrRecs r, unsigned long long *out, hipStream_t s) {
   if (r.n_rec <= 0) return;
-  const int64_t blocks = std::min<int64_t>((r.n_rec + kThreads - 1) / kThreads, 1024);
+  const int64_t blocks = std::min<int64_t>((r.n_rec + kThreads - 1) / kThreads, kLogSizeBlocksMax);
   hipLaunchKernelGGL(k_cons_log_size, dim3((unsigned)blocks), dim3(kThreads), 0, s, r, out);
 }
 

@@ -34,6 +34,7 @@ constexpr int kFastBits = 9;      // first-level table: codes of up to 9 bits in
 constexpr int kFast = 1 << kFastBits;
 constexpr uint32_t kPoly = 0xEDB88320u;
 constexpr int kCrcSeg = 1024;     // CRC bytes per lane: 64 x 1024 = the largest member
+constexpr int kInflateBlocksMax = 16384;  // workgroups of a launch: beyond that they stride over the members
 
 __constant__ uint16_t kLenBase[29] = {3,  4,  5,  6,  7,  8,  9,  10, 11,  13,  15,  17,  19,  23, 27,
                                       31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
@@ -467,7 +468,7 @@ void launch_inflate(const uint8_t *in, const InflateMember *members, int64_t n_m
   if (n_members <= 0) return;
   // enough workgroups to fill every CU many times over (a member's decode is one serial chain of dependent loads);
   // beyond that they stride, and the CRC tables are loaded once per workgroup
-  const int64_t grid = n_members < 16384 ? n_members : 16384;
+  const int64_t grid = n_members < kInflateBlocksMax ? n_members : kInflateBlocksMax;
   hipLaunchKernelGGL(k_inflate, dim3((unsigned)grid), dim3(kThreads), 0, s, in, members, n_members, out, status, d_crc_table,
                      d_pow128);
 }

@@ -354,6 +354,7 @@ void launch_inflate(const uint8_t *in, const InflateMember *members, int64_t n_m
 // first byte).  Tiles of kSpTile bytes from the kSpTile boundary at or below b0; buf is readable up to the end of the last tile
 // and 16 bytes further.
 constexpr int kSpTile = 1024;  // one 16-byte load per lane of a wave
+constexpr int kSpBlocksMax = 4096;  // workgroups (four waves each) of a pass here or in sample_bam.hip: beyond that the waves stride
 inline int64_t sp_tiles(int64_t b0, int64_t b1) { return b1 > b0 ? (b1 - (b0 & ~(int64_t)(kSpTile - 1)) + kSpTile - 1) / kSpTile : 0; }
 // tile_count[t] = line feeds of tile t; *nul |= 1 when the window holds a NUL byte
 void launch_sp_count(const uint8_t *buf, int64_t b0, int64_t b1, int64_t *tile_count, int32_t *nul, hipStream_t s);

@@ -157,7 +157,7 @@ void launch_sb_sums(const uint8_t *buf, const uint64_t *rec, int64_t n_rec, int3
 void launch_sb_pool(const uint8_t *buf, const uint64_t *rec, const uint32_t *qual_at, const int32_t *rec_len, const int64_t *padded,
                     const int64_t *off, int64_t n_rec, uint8_t *pool, hipStream_t s) {
   if (n_rec <= 0) return;
-  const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>((n_rec + 3) / 4, 1), 4096);
+  const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>((n_rec + 3) / 4, 1), kSpBlocksMax);
   hipLaunchKernelGGL(k_sb_pool, dim3(grid), dim3(256), 0, s, buf, rec, qual_at, rec_len, padded, off, n_rec, pool);
 }
 

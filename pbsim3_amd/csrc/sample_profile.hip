@@ -195,7 +195,7 @@ __global__ __launch_bounds__(256) void k_sp_pool(const uint8_t *buf, const uint3
   }
 }
 
-unsigned grid_for_waves(int64_t n_waves) { return (unsigned)std::min<int64_t>(std::max<int64_t>((n_waves + 3) / 4, 1), 4096); }
+unsigned grid_for_waves(int64_t n_waves) { return (unsigned)std::min<int64_t>(std::max<int64_t>((n_waves + 3) / 4, 1), kSpBlocksMax); }
 
 }  // namespace
 

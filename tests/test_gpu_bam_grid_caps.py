@@ -17,8 +17,9 @@ The tests here failed for each of the six.
 Each input goes once through the command line with PBSIM_TRACE, and the stage's own summary line has to say that it passed its cap: a
 changed cap that leaves an input in one trip fails here, and one that makes an input huge fails the size limits below.
 
-Not reached: column_blocks' `least` branch (more than 2^21 segments), the record-strided log-size kernel (more than a million
-records), a 32-bit cell's wrap, and a text of more than the default piece of 8 MiB."""
+Not reached: column_blocks' `least` branch (more than 2^21 segments), the record-strided log-size kernel (more than
+kLogSizeBlocksMax * kThreads = 262 144 records: a BAM of 262 444 minimal records has 15.6 MB, twice MAX_STREAM below, and
+consensus_model.consensus took 42 s on it), a 32-bit cell's wrap, and a text of more than the default piece of 8 MiB."""
 import functools
 import os
 import random
