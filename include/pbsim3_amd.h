@@ -1018,6 +1018,66 @@ int64_t pbsim_apply_report(const pbsim_apply_result *result, char *buf, int64_t 
 /* The 0-based sample column that `name` has in the first line of the VCF text that begins with `#CHROM` (its columns behind
  * FORMAT), no device needed; -1: no such line or no such name. */
 int32_t pbsim_apply_sample(const void *vcf, int64_t n_vcf, const char *name);
+/* An aligned BAM whose records lie on a variant genome, placed on the original genome on the GPU: the link between the truth BAM
+ * of reads simulated from pbsim_genome_mutate's or pbsim_vcf_apply's FASTA and the stages that work against the original genome
+ * (a mapper, pbsim_truth_bam_eval, pbsim_bam_errors).  refs are the ORIGINAL genome's records as pbsim_bam_errors takes them;
+ * origins holds one origin map per genome record, as the on_origin of those two stages delivers it; file is the BAM (BGZF, gzip
+ * or uncompressed), ref_name as in pbsim_bam_errors.  pos, bin, CIGAR and NM are made anew; every other byte of a record stays.
+ * 1. References.  The file's reference k goes by its name (or by ref_name, for a file with exactly one reference) to a genome
+ * record; a name the genome lacks fails the call.  Its l_ref must be the length of that record's origin map, else the call fails
+ * with both numbers: "not the genome these reads came from".  In the lifted header every l_ref, and the LN: of the @SQ line whose
+ * SN: is the reference's name, is the original record's length; an SO: value of a leading @HD line becomes `unsorted`; nothing
+ * else of the text changes.
+ * 2. Origin map.  One int32 per variant base: o >= 0 a kept or substituted base of original position o; -1 - p a base inserted
+ * behind p; -2^31 a base inserted in front of position 0.  Checked on the device before use: kept values rise strictly and stay
+ * below the original length; an inserted base names the last kept value in front of it, or -2^31 where there is none.  A violation
+ * fails the call with the reference's name and the first faulty variant position.
+ * 3. `unaligned`, copied unchanged: flag & 4, refID outside [0, n_ref), pos < 0, or no CIGAR.
+ * 4. `unsupported`, dropped: the resolved CIGAR (the CG:B,I array where the field is the <l_seq>S<span>N placeholder) holds an N
+ * or P op.  A record with an op code above 8, with aux fields that run past it or have an unknown type, with a CIGAR that runs
+ * past its reference or, where l_seq != 0, a query length that is not l_seq fails the call with its inflated offset.
+ * Columns, in order; M stands for M, = and X; v is the variant base, o = origin[v].
+ * 5. An M column with o >= 0 becomes M at o; with o < 0 it becomes I.   6. An I column stays I.
+ * 7. A D column with o >= 0 becomes D; with o < 0 it vanishes.
+ * 8. In front of an M or D column with o >= 0, once an M column has been emitted, o - 1 - o_prev D columns stand for the original
+ * bases the variant genome deleted; o_prev is the origin of the nearest kept variant base below v, -1 without one.
+ * 9. In front of the first emitted M column and behind the last every I column becomes S and every D column is dropped, gap
+ * columns included.  H ops in front of the CIGAR's first column stay as one H at the left end, the others as one at the right end;
+ * S likewise inside them, merged with the new S.
+ * 10. A record without an M column left is dropped: `unplaced`.   11. pos is the origin of the first M column.
+ * 12. Adjacent equal ops merge; nothing else is canonicalised (2D1I3D may stand).  Output ops are M, I, D, S, H.
+ * 13. bin = reg2bin(pos, pos + span), span the M and D columns.
+ * 14. NM = sub + ins + del against the original genome: sub per M column as pbsim_bam_errors counts it (the prepared bytes; a column
+ * with a code outside ACGT on either side is no sub; `=` in SEQ agrees).  A record with l_seq = 0 gets no NM: `no_seq`.
+ * 15. Aux fields: NM first; with more than 65535 ops the field is <l_seq>S<span>N and CG:B,I follows NM (SAMv1 4.2.2), so an input
+ * placeholder whose lifted CIGAR fits comes back as a real CIGAR; then every field of the input in order except those tagged NM or CG.
+ * 16. Records keep their order.   17. The file leaves as BGZF as pbsim_truth_bam_sort writes it: the header in members of its own,
+ * the EOF block at the end, through sink->on_bam in offset order.
+ * Result.  counts: records, unaligned, unsupported, unplaced, lifted, moved (pos or the resolved CIGAR differs), no_seq,
+ * long_cigar_in, long_cigar_out (the last three among the lifted).  totals over the lifted records: cols_in, cols_out (M + I + D
+ * of the lifted core), m, ins, del, soft, sub, gap_del (rule 8's columns that stayed), bases_to_ins (M columns with o < 0),
+ * dels_vanished (D columns with o < 0), bytes_in, bytes_out.
+ * tests/lift_model.py states the rule in plain Python.  The stage holds the inflated stream, the lifted stream, their compressed
+ * pieces, the genome at 2 bytes per base, 8 bytes per variant base (origin and the max-scan of its kept values), 4 bytes per
+ * lifted op and 181 bytes per record in HBM at once and does not chunk: an allocation that does not fit fails with the bytes it
+ * needed.  One wave takes a whole record, 64 columns at a time.  After any failure the context stays usable and the result is zeroed. */
+typedef struct pbsim_lift_origin {
+  const int32_t *origin;
+  int64_t n;
+} pbsim_lift_origin;
+typedef struct pbsim_lift_sink {
+  void *user;
+  int (*on_bam)(void *user, const char *bytes, int64_t n, int64_t offset); /* in offset order; may be NULL */
+} pbsim_lift_sink;
+typedef struct pbsim_lift_result {
+  int64_t counts[9];
+  int64_t totals[12];
+} pbsim_lift_result;
+int pbsim_bam_lift(pbsim_ctx *ctx, const pbsim_errors_ref *refs, int n_refs, const pbsim_lift_origin *origins /* one per genome record */,
+                   const pbsim_errors_file *file, const pbsim_lift_sink *sink, pbsim_lift_result *result);
+/* The report text, no device needed: a "#" line with the names and an "L" line with the values of the result in its order,
+ * tab-separated.  Returns the text's length, and writes it (no NUL) where buf holds cap >= that many bytes; -1: bad argument. */
+int64_t pbsim_lift_report(const pbsim_lift_result *result, char *buf, int64_t cap);
 
 /* ---- batch primitives (used by the drivers above, bench.py, multi-GPU) ------
  * pbsim_batch_walk     header draw + bucketing + HMM walk of reads

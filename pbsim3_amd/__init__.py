@@ -371,6 +371,25 @@ class ApplyResult(C.Structure):
                 ("deleted", C.c_int64), ("substituted", C.c_int64), ("longest_cluster", C.c_int64), ("fasta_bytes", C.c_int64),
                 ("text_bytes", C.c_int64)]
 
+class LiftOrigin(C.Structure):
+    _fields_ = [("origin", C.c_void_p), ("n", C.c_int64)]
+
+
+LIFT_BAM_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64)
+
+
+class LiftSink(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("on_bam", LIFT_BAM_CB)]
+
+
+LIFT_COUNTS = ["records", "unaligned", "unsupported", "unplaced", "lifted", "moved", "no_seq", "long_cigar_in", "long_cigar_out"]
+LIFT_TOTALS = ["cols_in", "cols_out", "m", "ins", "del", "soft", "sub", "gap_del", "bases_to_ins", "dels_vanished", "bytes_in", "bytes_out"]
+
+
+class LiftResult(C.Structure):
+    _fields_ = [("counts", C.c_int64 * 9), ("totals", C.c_int64 * 12)]
+
+
 # every symbol include/pbsim3_amd.h declares: (name, restype, argtypes)
 API = [
     ("pbsim_job_add_record", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
@@ -485,6 +504,9 @@ API = [
                                   C.POINTER(ApplySink), C.POINTER(ApplyResult)]),
     ("pbsim_apply_report", C.c_int64, [C.POINTER(ApplyResult), C.c_char_p, C.c_int64]),
     ("pbsim_apply_sample", C.c_int32, [C.c_char_p, C.c_int64, C.c_char_p]),
+    ("pbsim_bam_lift", C.c_int, [C.c_void_p, C.POINTER(ErrorsRef), C.c_int, C.POINTER(LiftOrigin), C.POINTER(ErrorsFile), C.POINTER(LiftSink),
+                                 C.POINTER(LiftResult)]),
+    ("pbsim_lift_report", C.c_int64, [C.POINTER(LiftResult), C.c_char_p, C.c_int64]),
     ("pbsim_batch_walk", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("pbsim_slot_count", C.c_int, []),
     ("pbsim_select_slot", C.c_int, [C.c_void_p, C.c_int]),
@@ -834,6 +856,26 @@ def apply_sample(vcf, name) -> int:
     """The 0-based sample column `name` has in the #CHROM line of the VCF text (pbsim_apply_sample, no device needed); -1: none."""
     vcf = bytes(vcf)
     return int(load().pbsim_apply_sample(vcf, len(vcf), name.encode() if isinstance(name, str) else bytes(name)))
+
+
+def _lift_dict(res) -> dict:
+    """a LiftResult as a dict by name: the counts, then the totals"""
+    out = dict(zip(LIFT_COUNTS, (int(v) for v in res.counts)))
+    out.update(zip(LIFT_TOTALS, (int(v) for v in res.totals)))
+    return out
+
+
+def lift_report(result) -> bytes:
+    """The report text of Context.lift_bam's result (the dict): pbsim_lift_report, no device needed."""
+    res = LiftResult()
+    res.counts = type(res.counts)(*[int(result.get(k, 0)) for k in LIFT_COUNTS])
+    res.totals = type(res.totals)(*[int(result.get(k, 0)) for k in LIFT_TOTALS])
+    n = load().pbsim_lift_report(C.byref(res), None, 0)
+    if n < 0:
+        raise PbsimError("pbsim_lift_report: bad argument")
+    buf = C.create_string_buffer(max(n, 1))
+    load().pbsim_lift_report(C.byref(res), buf, n)
+    return buf.raw[:n]
 
 
 def inflate_bound(data: bytes) -> int:
@@ -1724,6 +1766,43 @@ class Context:
         if text:
             got += (b"".join(texts[1]),)
         return got + (origins,) if origin else got
+
+    def lift_bam(self, bam, genome, origin, ref_names=None, ref_name=None):
+        """An aligned BAM whose records lie on a variant genome, placed on the original `genome` -- a list of (name, sequence lines)
+        -- through `origin`, the list of int32 arrays per genome record that mutate_genome(origin=True) or apply_vcf(origin=True)
+        returns (pbsim_bam_lift; the rule: include/pbsim3_amd.h).  ref_names: per genome record the name the BAM's header uses for it
+        (None: the records' own); ref_name: the genome name of the only reference of a file that calls it otherwise (`ref` in a wgs
+        truth BAM).  Returns (result, report, lifted_bytes): a dict of the counts and totals by name, the report text, and the lifted
+        file, BGZF."""
+        import numpy as np
+        bam = bytes(bam)
+        genome = [((nm.encode() if isinstance(nm, str) else bytes(nm)), bytes(ls)) for nm, ls in genome]
+        if ref_names is not None:
+            used = [nm.encode() if isinstance(nm, str) else bytes(nm) for nm in ref_names]
+            if len(used) != len(genome):
+                raise ValueError("ref_names: one entry per genome record (%d given for %d records)" % (len(used), len(genome)))
+            genome = [(nm, ls) for nm, (_, ls) in zip(used, genome)]
+        if len(origin) != len(genome):
+            raise ValueError("origin: one map per genome record (%d given for %d records)" % (len(origin), len(genome)))
+        maps = [np.ascontiguousarray(o, dtype=np.int32) for o in origin]
+        refs = (ErrorsRef * max(len(genome), 1))(*[ErrorsRef(nm, C.cast(C.c_char_p(ls), C.c_void_p), len(ls)) for nm, ls in genome])
+        origins = (LiftOrigin * max(len(maps), 1))(*[LiftOrigin(m.ctypes.data if m.size else None, m.size) for m in maps])
+        if ref_name is not None:
+            ref_name = ref_name.encode() if isinstance(ref_name, str) else bytes(ref_name)
+        file = ErrorsFile(C.cast(C.c_char_p(bam), C.c_void_p), len(bam), ref_name)
+        parts, at = [], [0]
+
+        def on_bam(user, ptr, n, offset):
+            if offset != at[0]:      # (the pieces come in offset order)
+                return 0
+            parts.append(C.string_at(ptr, n))
+            at[0] += n
+            return 1
+        sink = LiftSink(None, LIFT_BAM_CB(on_bam))
+        res = LiftResult()
+        _check(self.lib.pbsim_bam_lift(self.h, refs, len(genome), origins, C.byref(file), C.byref(sink), C.byref(res)))
+        out = _lift_dict(res)
+        return out, lift_report(out), b"".join(parts)
 
     def set_transcripts(self, ids, plus, minus, seqs):
         """ids: list[str]; plus/minus: expression counts; seqs: list[bytes]."""

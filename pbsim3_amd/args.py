@@ -411,3 +411,35 @@ def apply_vcf(argv):
         raise ValueError("--apply-vcf needs --apply-out FASTA: where the spliced genome goes.")
     _refuse_empty_name("apply-ref-names", got["ref_names"])
     return got
+
+
+def lift_bam(argv):
+    """`pbsim --lift-bam IN --lift-out OUT --lift-genome FASTA --lift-vcf VCF [--lift-haplotype 0|1|2] [--lift-sample N|NAME]
+    [--lift-ref-names a,b,..] [--lift-ref-name NAME]` -> dict(bam, out, genome, vcf, haplotype, sample, ref_names, ref_name): the
+    stand-alone mode that places a truth BAM of a variant genome on the original one (pbsim_vcf_apply for the origin maps, then
+    pbsim_bam_lift); sample is a column (int) or a name (str).  What pbsim_cli_main refuses from the command line alone raises
+    ValueError with its message."""
+    def sample(got, v):
+        if not v:
+            raise ValueError("(lift-sample): a 0-based sample column or a sample's name.")
+        n = _whole(v)
+        got["sample"] = v if n is None or n > 2147483647 else n
+    rows = (("--lift-bam", TEXT, "bam"),
+            ("--lift-out", TEXT, "out"),
+            ("--lift-genome", TEXT, "genome"),
+            ("--lift-vcf", TEXT, "vcf"),
+            ("--lift-haplotype", WHOLE, "haplotype", 0, 2, "0 (the first ALT of every line), 1 or 2."),
+            ("--lift-sample", HOOK, None, sample),
+            ("--lift-ref-names", NAMES, "ref_names"),
+            ("--lift-ref-name", TEXT, "ref_name"))
+    got = _walk(argv, rows, dict(bam=None, out=None, genome=None, vcf=None, haplotype=0, sample=0, ref_names=None, ref_name=None))
+    if not got["bam"]:
+        raise ValueError("--lift-bam IN: name the BAM file whose records lie on the variant genome.")
+    if not got["out"]:
+        raise ValueError("--lift-bam needs --lift-out FILE: where the lifted BAM goes.")
+    if not got["genome"]:
+        raise ValueError("--lift-bam needs --lift-genome FASTA: the original genome.")
+    if not got["vcf"]:
+        raise ValueError("--lift-bam needs --lift-vcf VCF: the variants the variant genome was made with (--mutate-vcf's file, or the file given to --apply-vcf).")
+    _refuse_empty_name("lift-ref-names", got["ref_names"])
+    return got

@@ -15,8 +15,8 @@ CLI = os.path.join(BIN_DIR, "pbsim")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-HIP_SOURCES = ["kernels.hip", "deflate.hip", "inflate.hip", "sample_profile.hip", "sample_bam.hip", "bam_scan.hip", "engine.cpp", "deflate_host.cpp", "units.cpp", "arrays.cpp", "sample.cpp", "job.cpp", "rccl_capi.cpp", "inflate_host.cpp", "sample_profile.cpp", "bam_sort.hip", "bam_sort.cpp", "bam_eval.hip", "bam_eval.cpp", "bam_stream.cpp", "bam_depth.hip", "bam_depth.cpp", "bam_stats.hip", "bam_stats.cpp", "bam_errors.hip", "bam_errors.cpp", "bam_file_front.cpp", "bam_genome.cpp", "bam_pileup.hip", "bam_pileup.cpp", "bam_consensus.hip", "bam_consensus.cpp", "bam_call.hip", "bam_call.cpp", "genome_mutate.hip", "genome_mutate.cpp", "vcf_compare.hip", "vcf_compare.cpp", "vcf_apply.hip", "vcf_apply.cpp"]
-CXX_SOURCES = ["host_tables.cpp", "unit_io.cpp", "stats.cpp", "cli.cpp", "cli_stages.cpp", "gzout.cpp", "numa_bind.cpp", "input_file.cpp", "bam_chain.cpp", "bam_eval_rule.cpp", "bam_depth_rule.cpp", "bam_stats_rule.cpp", "bam_errors_rule.cpp", "bam_pileup_rule.cpp", "bam_consensus_rule.cpp", "bam_call_rule.cpp", "genome_mutate_rule.cpp", "vcf_compare_rule.cpp", "vcf_apply_rule.cpp"]
+HIP_SOURCES = ["kernels.hip", "deflate.hip", "inflate.hip", "sample_profile.hip", "sample_bam.hip", "bam_scan.hip", "engine.cpp", "deflate_host.cpp", "units.cpp", "arrays.cpp", "sample.cpp", "job.cpp", "rccl_capi.cpp", "inflate_host.cpp", "sample_profile.cpp", "bam_sort.hip", "bam_sort.cpp", "bam_eval.hip", "bam_eval.cpp", "bam_stream.cpp", "bam_depth.hip", "bam_depth.cpp", "bam_stats.hip", "bam_stats.cpp", "bam_errors.hip", "bam_errors.cpp", "bam_file_front.cpp", "bam_genome.cpp", "bam_pileup.hip", "bam_pileup.cpp", "bam_consensus.hip", "bam_consensus.cpp", "bam_call.hip", "bam_call.cpp", "genome_mutate.hip", "genome_mutate.cpp", "vcf_compare.hip", "vcf_compare.cpp", "vcf_apply.hip", "vcf_apply.cpp", "bam_lift.hip", "bam_lift.cpp"]
+CXX_SOURCES = ["host_tables.cpp", "unit_io.cpp", "stats.cpp", "cli.cpp", "cli_stages.cpp", "gzout.cpp", "numa_bind.cpp", "input_file.cpp", "bam_chain.cpp", "bam_eval_rule.cpp", "bam_depth_rule.cpp", "bam_stats_rule.cpp", "bam_errors_rule.cpp", "bam_pileup_rule.cpp", "bam_consensus_rule.cpp", "bam_call_rule.cpp", "genome_mutate_rule.cpp", "vcf_compare_rule.cpp", "vcf_apply_rule.cpp", "bam_lift_rule.cpp"]
 CLI_SOURCES = ["main.cpp"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result"] + os.environ.get("PBSIM_EXTRA_CFLAGS", "").split()
 

@@ -8,7 +8,7 @@
 // compressed bytes cross PCIe) and written here; --gzip host uses the in-process multi-threaded zlib writer (gzout.h);
 // --samtools pipes SAM text into `samtools view -b` like the reference.  --truth-format bam writes the truth as aligned BAM;
 // --truth-sort coordinate then sorts and indexes each finished <prefix>[_NNNN].aln.bam on the GPU (pbsim_truth_bam_sort), and
-// `pbsim --sort-truth-bam FILE ...` does that alone for files made earlier.  The other stand-alone modes (--eval-bam .. --apply-vcf)
+// `pbsim --sort-truth-bam FILE ...` does that alone for files made earlier.  The other stand-alone modes (--eval-bam .. --lift-bam)
 // are cli_stages.cpp's: pbsim_cli_main hands the line to the first of them it names.
 //
 // wgs (errhmm / qshmm) runs as ONE job over all records (pbsim_job_run): the records are resident in HBM, and on several
@@ -375,6 +375,11 @@ void print_help() {
           "  the allele the sample's GT names for the haplotype, colliding lines resolved as bcftools consensus does: the spliced genome\n"
           "  as FASTA to --apply-out (simulate from it), the summary to stdout, one annotated line per data line to --apply-report, the\n"
           "  origin map (int32 per written base, little-endian) to --apply-origin; both inputs may be gzip-compressed\n"
+          "  pbsim --lift-bam IN --lift-out OUT --lift-genome FASTA --lift-vcf VCF [--lift-haplotype 0|1|2 (0)] [--lift-sample N|NAME (0)]\n"
+          "  [--lift-ref-names a,b,..] [--lift-ref-name NAME]: no simulation; a truth BAM whose records lie on the variant genome that\n"
+          "  VCF makes of FASTA (--mutate-vcf's file, or the file and haplotype given to --apply-vcf) placed on FASTA itself on the GPU:\n"
+          "  pos, bin, CIGAR and NM anew, every other byte kept, as BGZF to --lift-out, the summary to stdout; the inputs may be\n"
+          "  gzip-compressed\n"
           "  --genome, --transcript, --template and --sample may be gzip-compressed (recognised by content): BGZF is\n"
           "  inflated on the GPU, other gzip by zlib on the host; the whole inflated file is held in host memory\n\n");
 }

@@ -1,6 +1,6 @@
 // cli_stages.cpp -- the stand-alone modes of the `pbsim` binary: no simulation, one stage of the C ABI of include/pbsim3_amd.h on
 // one GPU (--eval-bam, --depth-bam, --stats-bam, --errors-bam, --pileup-bam, --consensus-bam, --call-bam, --mutate-genome,
-// --compare-vcf, --apply-vcf; cli_stages.h names them).  Every mode has the same frame, and each step of it is written once here:
+// --compare-vcf, --apply-vcf, --lift-bam; cli_stages.h names them).  Every mode has the same frame, and each step of it is written once here:
 // the options as a table of rows that one parser walks, the names list, the input files, the genome, the VCF bytes, the one-GPU
 // context, the output files with their ending, the report.  A mode's main is then its table, its "needs" refusals, its options
 // struct, its call and its report.  What can be refused from the command line alone is refused before a GPU is touched;
@@ -686,6 +686,74 @@ int apply_vcf_main(int argc, char **argv, const pbsim_comm *comm, int device) {
   const bool ok = pbsim_vcf_apply(ctx, g.refs.data(), (int)g.refs.size(), used.empty() ? NULL : used.data(), vcf.bytes, vcf.n, &opts, &sink, &result) != 0;
   finish_outputs(a.outs, 3, ok);
   print_report([&](char *to, int64_t cap) { return pbsim_apply_report(&result, to, cap); });
+  return leave(ctx);
+}
+
+// `pbsim --lift-bam IN --lift-out OUT --lift-genome FASTA --lift-vcf VCF ...`: a truth BAM whose records lie on the variant genome
+// that VCF makes of FASTA, placed on FASTA itself (pbsim_bam_lift), the summary to stdout.  The VCF is the chain: pbsim_vcf_apply
+// runs with on_origin alone -- no FASTA, no text --, and its origin maps go to the lift; no origin file and no variant FASTA is read.
+struct LiftArgs {
+  std::string bam, genome, vcf, ref_name, sample_name;
+  OutFile out;
+  std::vector<std::string> names;
+  long long haplotype = 0, sample = 0;
+};
+void lift_sample(const char *v, void *args) {
+  LiftArgs *a = (LiftArgs *)args;
+  if (!*v) die(" (lift-sample): a 0-based sample column or a sample's name.");
+  a->sample_name.clear();
+  if (!whole_number(v, 10, 0, 2147483647LL, &a->sample)) a->sample_name = v, a->sample = 0;
+}
+const Opt kLiftOpts[] = {{"--lift-bam", kText, offsetof(LiftArgs, bam)},
+                         {"--lift-out", kText, offsetof(LiftArgs, out.name)},
+                         {"--lift-genome", kText, offsetof(LiftArgs, genome)},
+                         {"--lift-vcf", kText, offsetof(LiftArgs, vcf)},
+                         {"--lift-haplotype", kWhole, offsetof(LiftArgs, haplotype), 0, 2, "0 (the first ALT of every line), 1 or 2."},
+                         {"--lift-sample", kHook, 0, 0, 0, nullptr, nullptr, nullptr, lift_sample},
+                         {"--lift-ref-names", kNames, offsetof(LiftArgs, names)},
+                         {"--lift-ref-name", kText, offsetof(LiftArgs, ref_name)}};
+
+int lift_bam_main(int argc, char **argv, const pbsim_comm *comm, int device) {
+  LiftArgs a;
+  PARSE_STAGE(kLiftOpts, a);
+  if (a.bam.empty()) die(": --lift-bam IN: name the BAM file whose records lie on the variant genome.");
+  if (a.out.name.empty()) die(": --lift-bam needs --lift-out FILE: where the lifted BAM goes.");
+  if (a.genome.empty()) die(": --lift-bam needs --lift-genome FASTA: the original genome.");
+  if (a.vcf.empty()) die(": --lift-bam needs --lift-vcf VCF: the variants the variant genome was made with (--mutate-vcf's file, or the file given to --apply-vcf).");
+  refuse_empty_name("lift-ref-names", a.names);
+  need_readable({&a.bam, &a.genome, &a.vcf});
+  pbsim_ctx *ctx = one_gpu_context(device);
+  VcfBytes vcf;
+  load_vcf(a.vcf, ctx, &vcf);
+  GenomeRefs g;
+  map_genome_refs("--lift-genome", a.genome, ctx, &g);
+  if (!a.sample_name.empty()) {
+    const int32_t column = pbsim_apply_sample(vcf.bytes, vcf.n, a.sample_name.c_str());
+    if (column < 0) die(" (lift-sample: %s): the #CHROM line of %s names no such sample.", a.sample_name.c_str(), a.vcf.c_str());
+    a.sample = column;
+  }
+  need_record_names("lift-ref-names", a.names, g.refs.size());
+  const std::vector<const char *> used = used_names(a.names);
+  std::vector<MappedFile> bam;
+  open_inputs({a.bam}, &bam);
+  // the chain: the origin map of every genome record
+  std::vector<std::vector<int32_t>> maps(g.refs.size());
+  pbsim_apply_opts opts = {(int32_t)a.haplotype, (int32_t)a.sample, 0, 60, 0};
+  pbsim_apply_sink chain = {&maps, NULL, NULL, NULL, [](void *u, int32_t ref, const int32_t *z, int64_t k) {
+                              (*(std::vector<std::vector<int32_t>> *)u)[(size_t)ref].assign(z, z + k);
+                              return 1;
+                            }};
+  pbsim_apply_result applied;
+  if (!pbsim_vcf_apply(ctx, g.refs.data(), (int)g.refs.size(), used.empty() ? NULL : used.data(), vcf.bytes, vcf.n, &opts, &chain, &applied)) check(0);
+  std::vector<pbsim_lift_origin> origins(maps.size());
+  for (size_t r = 0; r < maps.size(); r++) origins[r] = pbsim_lift_origin{maps[r].data(), (int64_t)maps[r].size()};
+  open_outputs(&a.out, 1);
+  const pbsim_errors_file file = {bam[0].map, (int64_t)bam[0].n, a.ref_name.empty() ? NULL : a.ref_name.c_str()};
+  pbsim_lift_sink sink = {&a.out, text_to_0};
+  pbsim_lift_result result;
+  const bool ok = pbsim_bam_lift(ctx, g.refs.data(), (int)g.refs.size(), origins.data(), &file, &sink, &result) != 0;
+  finish_outputs(&a.out, 1, ok);
+  print_report([&](char *to, int64_t cap) { return pbsim_lift_report(&result, to, cap); });
   return leave(ctx);
 }
 

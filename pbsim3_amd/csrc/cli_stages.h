@@ -14,7 +14,8 @@
   X("--call-bam", call_bam_main)           \
   X("--mutate-genome", mutate_genome_main) \
   X("--compare-vcf", compare_vcf_main)     \
-  X("--apply-vcf", apply_vcf_main)
+  X("--apply-vcf", apply_vcf_main)         \
+  X("--lift-bam", lift_bam_main)
 
 namespace pbsim {
 namespace cli {

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
+#include "bam_tags.h"
 #include "kernels.h"
 #include "philox.h"
 
@@ -2719,18 +2720,7 @@ __device__ __forceinline__ void task_text(const TextArgs &a, int64_t r, int pass
 // ---- BAM records (SAMv1 section 4.2) of the unaligned subreads the reference pipes into
 // `samtools view -b` (pbsim.cpp:4016-4027).  Integer tags take the smallest type that holds
 // the value, as htslib's SAM parser chooses them.
-__device__ __forceinline__ int bam_int_size(int64_t v) {
-  if (v < 0) return v >= -128 ? 1 : v >= -32768 ? 2 : 4;
-  return v < 256 ? 1 : v < 65536 ? 2 : 4;
-}
-__device__ __forceinline__ char *bam_put_int_tag(char *o, char t0, char t1, int64_t v) {
-  *o++ = t0;
-  *o++ = t1;
-  const int n = bam_int_size(v);
-  *o++ = (v < 0) ? (n == 1 ? 'c' : n == 2 ? 's' : 'i') : (n == 1 ? 'C' : n == 2 ? 'S' : 'I');
-  for (int i = 0; i < n; i++) *o++ = (char)((uint64_t)v >> (8 * i));
-  return o;
-}
+// (bam_int_size, bam_put_int_tag, kCigarMaxOps and aln_reg2bin: bam_tags.h, shared with bam_lift.hip)
 __device__ __forceinline__ char *bam_put_u32(char *o, uint32_t v) {
   for (int i = 0; i < 4; i++) *o++ = (char)(v >> (8 * i));
   return o;
@@ -2751,20 +2741,9 @@ __device__ __forceinline__ int64_t bam_record_size(int idl, int q, int64_t readn
 
 // ---- aligned BAM records of the truth stream (pbsim_set_truth_bam): one placed record per task, SAMv1 4.2.  A CIGAR of
 // more than 65535 operations moves into a CG:B,I tag behind NM and leaves <q>S<span>N in its place (SAMv1 4.2.2).
-constexpr int kCigarMaxOps = 65535;
 __device__ __forceinline__ int64_t aln_record_size(int idl, int q, int n_runs, int64_t nm) {
   const bool big = n_runs > kCigarMaxOps;
   return 4 + 32 + (idl + 1) + 4LL * (big ? 2 : n_runs) + (q + 1) / 2 + q + 3 + bam_int_size(nm) + (big ? 8 + 4LL * n_runs : 0);
-}
-// SAMv1 5.3, reg2bin(beg, end) as the specification writes it
-__device__ __forceinline__ int aln_reg2bin(int64_t beg, int64_t end) {
-  --end;
-  if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
-  if (beg >> 17 == end >> 17) return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
-  if (beg >> 20 == end >> 20) return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
-  if (beg >> 23 == end >> 23) return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
-  if (beg >> 26 == end >> 26) return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
-  return 0;
 }
 
 // kTruth (the MAF stream carries BAM records, a.truth_bam): an instance of its own, so that the MAF instance stays the kernel it was

@@ -25,6 +25,7 @@
 //   pbsim --mutate-genome FASTA --mutate-out FASTA --mutate-vcf FILE   no simulation: a variant genome and its truth variants drawn from a seed (cli_stages.cpp)
 //   pbsim --compare-vcf CALLS --compare-truth TRUTH --compare-genome FASTA   no simulation: a call set scored against the truth variants (cli_stages.cpp)
 //   pbsim --apply-vcf VCF --apply-genome FASTA --apply-out FASTA   no simulation: the lines of a VCF applied to the genome, per haplotype (cli_stages.cpp)
+//   pbsim --lift-bam IN --lift-out OUT --lift-genome FASTA --lift-vcf VCF   no simulation: a truth BAM on the variant genome placed on the original one (cli_stages.cpp)
 // Every rank runs the same pbsim_cli_main(argv): the job is deterministic in the values the ranks exchange, so they stay
 // in lockstep; rank 0 prints the report and creates the files, every rank writes its own byte ranges.
 #include <hip/hip_runtime.h>
@@ -96,7 +97,7 @@ int main(int argc, char **argv) {
     }
   }
   {
-    // the stand-alone modes (cli_stages.h: --eval-bam .. --apply-vcf) are modes of one GPU: the options that start several ranks are
+    // the stand-alone modes (cli_stages.h: --eval-bam .. --lift-bam) are modes of one GPU: the options that start several ranks are
     // refused beside them
 #define PBSIM_STAGE_OPTION(option, run) option,
     const char *const stage_options[] = {PBSIM_STAGE_MODES(PBSIM_STAGE_OPTION)};
