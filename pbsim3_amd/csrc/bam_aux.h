@@ -1,5 +1,5 @@
 // bam_aux.h -- the walk over a BAM record's aux fields (SAMv1 4.2.4) as device code does it, for the stages that read other
-// people's records (bam_depth.hip, bam_stats.hip): by type, field after field, until what is wanted has been found or the fields
+// people's records (through bam_cigar.h's resolve_cigar): by type, field after field, until what is wanted has been found or the fields
 // end.  What is wanted: the array of the CG tag of type B,I (SAMv1 4.2.2), the value of the first NM tag of an integer type, or
 // both.  A field that runs past the record or has an unknown type ends the walk with -1; fields behind the last wanted one are
 // not looked at.

@@ -36,57 +36,6 @@ static_assert(kCallTile == kThreads, "a tile is one workgroup's positions");
 // (a byte of the padding has 7 in its class bits: no del_site)
 __device__ __forceinline__ bool del_site(uint32_t c) { return (c & 7u) == (uint32_t)kPileDel; }
 
-// the exclusive prefix of v over the workgroup and *all, the workgroup's sum; every lane of the workgroup calls it
-// (as bam_consensus.hip's, whose kernels stay as they are)
-__device__ __forceinline__ u64 block_scan(u64 v, u64 *sh_wave, int wave, int lane, u64 *all) {
-  const u64 incl = wave_scan(v, lane);
-  __syncthreads();  // (the values of the call before have been read)
-  if (lane == 63) sh_wave[wave] = incl;
-  __syncthreads();
-  u64 before = 0, sum = 0;
-  for (int w = 0; w < kWaves; w++) {
-    if (w < wave) before += sh_wave[w];
-    sum += sh_wave[w];
-  }
-  *all = sum;
-  return before + incl - v;
-}
-
-// the slot of the ins_site at place i, -1 where it is none
-__device__ __forceinline__ int64_t slot_of(const ConsSlots &s, int64_t i) {
-  int64_t lo = 0, hi = s.n;  // the first slot whose place is not below i
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (s.pos[mid] < i) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < s.n && s.pos[lo] == i ? lo : -1;
-}
-
-// the base an insertion has at one offset: the largest of the A C G T cells, among equals the first; N where all four are 0
-__device__ __forceinline__ char ins_base(const uint32_t *c) {
-  uint32_t best = c[0], call = 0;
-#pragma unroll
-  for (uint32_t k = 1; k < 4; k++)
-    if (c[k] > best) best = c[k], call = k;
-  return best == 0 ? 'N' : "ACGT"[call];
-}
-
-__device__ __forceinline__ int digits(u64 x) {
-  int n = 1;
-  while (x >= 10) x /= 10, n++;
-  return n;
-}
-__device__ __forceinline__ char *put(char *o, u64 x) {
-  const int n = digits(x);
-  for (int k = n - 1; k >= 0; k--, x /= 10) o[k] = (char)('0' + x % 10);
-  return o + n;
-}
-__device__ __forceinline__ char *put(char *o, const char *s) {
-  while (*s) *o++ = *s++;
-  return o;
-}
-
 // What the positions lo .. hi spell, in order: byte(ch) per byte of E(lo) .. E(hi), and with kSupport support(n) per count
 // that stands behind a byte that is not the genome's or behind a deleted one.
 template <bool kSupport, class Byte, class Support>

@@ -67,6 +67,26 @@ struct ConsRecords {
 
 constexpr int kConsTile = kPileTile;
 
+// the slot of the ins_site at place i, -1 where it is none
+__device__ __forceinline__ int64_t slot_of(const ConsSlots &s, int64_t i) {
+  int64_t lo = 0, hi = s.n;  // the first slot whose place is not below i
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (s.pos[mid] < i) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < s.n && s.pos[lo] == i ? lo : -1;
+}
+
+// the base an insertion has at one offset: the largest of the A C G T cells, among equals the first; N where all four are 0
+__device__ __forceinline__ char ins_base(const uint32_t *c) {
+  uint32_t best = c[0], call = 0;
+#pragma unroll
+  for (uint32_t k = 1; k < 4; k++)
+    if (c[k] > best) best = c[k], call = k;
+  return best == 0 ? 'N' : "ACGT"[call];
+}
+
 // *out (zeroed) += the inserted bases of the file's scored records: the most entries its log can get
 void launch_consensus_log_size(ErrRecs r, unsigned long long *out, hipStream_t s);
 // the column pass with the log (the kernel is bam_pileup_walk.h's)

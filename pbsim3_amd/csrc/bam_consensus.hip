@@ -37,32 +37,6 @@ static_assert(kConsTile == kThreads, "a tile is one workgroup's positions");
 
 __device__ __forceinline__ bool ins_site(uint32_t c) { return c != (uint32_t)kPileNoSite && (c & kPileInsBit) != 0; }
 
-// the exclusive prefix of v over the workgroup and *all, the workgroup's sum; every lane of the workgroup calls it
-__device__ __forceinline__ u64 block_scan(u64 v, u64 *sh_wave, int wave, int lane, u64 *all) {
-  const u64 incl = wave_scan(v, lane);
-  __syncthreads();  // (the values of the call before have been read)
-  if (lane == 63) sh_wave[wave] = incl;
-  __syncthreads();
-  u64 before = 0, sum = 0;
-  for (int w = 0; w < kWaves; w++) {
-    if (w < wave) before += sh_wave[w];
-    sum += sh_wave[w];
-  }
-  *all = sum;
-  return before + incl - v;
-}
-
-// the slot of the ins_site at place i, -1 where it is none
-__device__ __forceinline__ int64_t slot_of(const ConsSlots &s, int64_t i) {
-  int64_t lo = 0, hi = s.n;  // the first slot whose place is not below i
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (s.pos[mid] < i) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < s.n && s.pos[lo] == i ? lo : -1;
-}
-
 // the inserted bases of a file's scored records, from the record pass's CIGAR sums: as many entries as the log can get at most
 __global__ __launch_bounds__(kThreads) void k_cons_log_size(ErrRecs a, u64 *out) {
   u64 sum = 0;
@@ -108,15 +82,6 @@ __global__ __launch_bounds__(kThreads) void k_cons_log(const u64 *entry, int64_t
 __global__ void k_cons_record_bases(int32_t n, const int64_t *at, const int64_t *part, const int64_t *tile_off, int64_t tiles, int64_t *base_at) {
   for (int r = blockIdx.x * blockDim.x + threadIdx.x; r <= n; r += gridDim.x * blockDim.x)
     base_at[r] = r < n ? tile_off[at[r] / kConsTile] + part[r] : tile_off[tiles];
-}
-
-// the base an insertion has at one offset: the largest of the A C G T cells, among equals the first; N where all four are 0
-__device__ __forceinline__ char ins_base(const uint32_t *c) {
-  uint32_t best = c[0], call = 0;
-#pragma unroll
-  for (uint32_t k = 1; k < 4; k++)
-    if (c[k] > best) best = c[k], call = k;
-  return best == 0 ? 'N' : "ACGT"[call];
 }
 
 // base idx of a record whose bases begin at o: its byte, and the line feed behind it where it ends a line or the record
@@ -236,8 +201,8 @@ void launch_consensus_columns(ErrRecs r, ErrRefs refs, ErrGenome g, const ErrSeg
                               unsigned long long *cells, ConsLog log, uint32_t max_ins, hipStream_t s) {
   if (n_seg <= 0) return;
   const InsLog to = {log.entry, log.count, (u64)log.cap, max_ins};
-  hipLaunchKernelGGL(k_pile_columns<true>, dim3((unsigned)column_blocks(n_seg)), dim3(kThreads), 0, s, r, refs, g.seq, kBamSamplePacking.size_bits, seg,
-                     n_seg, min_baseq, table, cells, to);
+  hipLaunchKernelGGL(k_pile_columns<true>, dim3((unsigned)column_blocks(n_seg, kWaves, kSegBlocksMax)), dim3(kThreads), 0, s, r, refs, g.seq, seg, n_seg,
+                     min_baseq, table, cells, to);
 }
 
 void launch_consensus_slot_sizes(PileGenome g, const uint8_t *cls, int64_t *tile_n, hipStream_t s) {

@@ -2,13 +2,15 @@
 // records located (bam_scan.hip, bam_chain.cpp).  The rule: include/pbsim3_amd.h.
 //
 //   events : one lane per record: its skip class, its CIGAR (the CG tag's array where the field is the <l_seq>S<span>N
-//            placeholder), and for each maximal covered interval +1 at its start and -1 at its end into a difference array of
-//            int32 over the concatenated references -- l_ref + 1 slots each, so that an end at l_ref has a place.  Adjacent
-//            covering ops merge, so a record without N (and, where deletions do not count, without D) is two atomics.  A record
-//            of more than 64 ops is taken by its whole wave, op k by lane k mod 64: a wave prefix sum of the reference
-//            advances gives each op its position, two ballots tell each lane whether an interval is open in front of it, and
-//            position and open interval are carried from one round of 64 to the next.  Clipping is min(position, l_ref): what
-//            lies wholly past the end puts its +1 and its -1 into the extra slot, where they cancel.
+//            placeholder: bam_cigar.h's resolve_cigar, which walks the aux fields of no other record here), and for each
+//            maximal covered interval +1 at its start and -1 at its end into a difference array of int32 over the
+//            concatenated references -- l_ref + 1 slots each, so that an end at l_ref has a place.  Adjacent covering ops
+//            merge, so a record without N (and, where deletions do not count, without D) is two atomics.  A record of more
+//            than 64 ops is taken by its whole wave (bam_cigar.h's each_long_cigar), op k by lane k mod 64: a wave prefix sum
+//            of the reference advances gives each op its position, two ballots tell each lane whether an interval is open in
+//            front of it, and position and open interval are carried from one round of 64 to the next.  Clipping is
+//            min(position, l_ref): what lies wholly past the end puts its +1 and its -1 into the extra slot, where they
+//            cancel.
 //   scan   : rocPRIM's inclusive scan in place.  Every reference's slots sum to zero, so nothing is segmented.
 //   runs   : one pass over the depths in tiles of kDepthTile slots, 16 consecutive slots per lane; the reference of a lane's
 //            first slot comes from a binary search in the offset table, the later ones by stepping.  The histogram and the
@@ -23,9 +25,8 @@
 
 #include <rocprim/device/device_scan.hpp>
 
-#include "bam_aux.h"
+#include "bam_cigar.h"
 #include "bam_depth.h"
-#include "bam_fields.h"
 
 namespace pbsim {
 
@@ -35,8 +36,6 @@ constexpr int kThreads = 256;
 constexpr int kPerLane = kDepthTile / kThreads;
 constexpr int kLdsRefs = 128;
 static_assert(kPerLane == 16, "a lane loads its slots as four int4");
-
-typedef unsigned long long u64;
 
 // MIDNSHP=X.  0: neither advances nor covers (I S H P, and any op of length 0); 1: covers; 2: advances only
 __device__ __forceinline__ int op_class(uint32_t v, bool deletions) {
@@ -81,19 +80,9 @@ __global__ __launch_bounds__(kThreads) void k_depth_events(const uint8_t *stream
       atomicAdd(&sh[kDepthCounted], 1u);
       base = refs.off[ref];
       l_ref = refs.off[ref + 1] - base - 1;
-      n_ops = ld16(p + kBamNCigarOp);
-      const uint32_t l_seq = ld32(p + kBamLSeq);
-      cig = p + kBamFixed + p[kBamLReadName];
-      if (n_ops == 2) {
-        const uint32_t op0 = ld32(cig), op1 = ld32(cig + 4);
-        if ((op0 & 15u) == 4 && (op0 >> 4) == l_seq && (op1 & 15u) == 3) {
-          const uint8_t *aux = cig + 8 + ((int64_t)l_seq + 1) / 2 + (int64_t)l_seq;
-          BamAux ax;
-          const int got = aux > end ? -1 : bam_aux_walk(aux, end, kAuxCg, &ax);
-          if (got < 0) bad = true;
-          else if (got & kAuxCg) cig = ax.cg, n_ops = ax.n_cg;
-        }
-      }
+      // (CG alone: the aux fields are walked only where the field is the placeholder)
+      const ResolvedCigar rc = resolve_cigar(p, end, ld32(p + kBamLSeq), kAuxCg);
+      cig = rc.ops, n_ops = rc.n_ops, bad = rc.bad;
     }
   }
   const bool mine = counted && !bad;
@@ -127,11 +116,7 @@ __global__ __launch_bounds__(kThreads) void k_depth_events(const uint8_t *stream
       atomicAdd(&diff[base + min(cur, l_ref)], -1);
     }
   }
-  // the records of more than 64 ops, one after the other, each by the whole wave
-  for (uint64_t big = __ballot(mine && n_ops > 64); big; big &= big - 1) {
-    const int src = __ffsll((long long)big) - 1;
-    const uint8_t *c_ops = (const uint8_t *)__shfl((int64_t)cig, src, 64);
-    const int64_t n = (int64_t)__shfl(n_ops, src, 64);
+  each_long_cigar(mine, cig, n_ops, [&](int src, const uint8_t *c_ops, int64_t n) {
     const int64_t r_base = __shfl(base, src, 64), r_len = __shfl(l_ref, src, 64);
     int64_t carry = __shfl(pos, src, 64);
     bool carry_open = false, any_bad = false, any_clip = false;
@@ -141,11 +126,7 @@ __global__ __launch_bounds__(kThreads) void k_depth_events(const uint8_t *stream
       if ((v & 15u) > 8) any_bad = true;
       const int c = op_class(v, deletions);
       const int64_t adv = c ? (int64_t)(v >> 4) : 0;
-      int64_t incl = adv;
-      for (int d = 1; d < 64; d <<= 1) {
-        const int64_t t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-      }
+      const int64_t incl = (int64_t)wave_scan((u64)adv, lane);
       const int64_t at = carry + incl - adv;
       const uint64_t cover = __ballot(c == 1), sig = cover | __ballot(c == 2);
       const uint64_t below = sig & (((uint64_t)1 << lane) - 1);
@@ -162,22 +143,11 @@ __global__ __launch_bounds__(kThreads) void k_depth_events(const uint8_t *stream
       bad = w_bad;
       clipped = w_clip;
     }
-  }
+  });
   if (clipped) atomicAdd(&sh[kDepthClipped], 1u);
   if (bad) atomicMin(&cells[kDepthCellFault], (u64)(p - stream));
   __syncthreads();
   if (threadIdx.x < kDepthCounts && sh[threadIdx.x]) atomicAdd(&cells[kDepthCellCounts + threadIdx.x], (u64)sh[threadIdx.x]);
-}
-
-// the last r in [0, n) with table[r] <= x (table ascending, table[0] <= x)
-__device__ __forceinline__ int32_t last_at_most(const int64_t *table, int32_t n, int64_t x) {
-  int32_t lo = 0, hi = n;  // table[lo] <= x, table[hi] > x (or hi == n)
-  while (hi - lo > 1) {
-    const int32_t mid = lo + ((hi - lo) >> 1);
-    if (table[mid] <= x) lo = mid;
-    else hi = mid;
-  }
-  return lo;
 }
 
 // what a lane has added up for one reference, into the workgroup's cells or, past them, into global memory
@@ -326,17 +296,6 @@ __global__ __launch_bounds__(kThreads) void k_depth_runs(const int32_t *depth, i
   if (tid == 0 && window == 0) tile_runs[blockIdx.x] = (int64_t)sh_runs;
 }
 
-__device__ __forceinline__ int digits(u64 x) {
-  int n = 1;
-  while (x >= 10) x /= 10, n++;
-  return n;
-}
-__device__ __forceinline__ char *put(char *o, u64 x) {
-  const int n = digits(x);
-  for (int k = n - 1; k >= 0; k--, x /= 10) o[k] = (char)('0' + x % 10);
-  return o + n;
-}
-
 // line k: its reference and the numbers behind the name (three for bedgraph, four for window)
 __device__ __forceinline__ int line_fields(int64_t k, int64_t n_lines, const DepthRefs &refs, int64_t window, const int32_t *run_ref,
                                            const int32_t *run_start, const int32_t *run_depth, const u64 *win_sum, int32_t *ref, u64 f[4]) {
@@ -367,9 +326,7 @@ __global__ __launch_bounds__(kThreads) void k_depth_line_sizes(int64_t n_lines, 
   int32_t r;
   u64 f[4];
   const int n = line_fields(k, n_lines, refs, window, run_ref, run_start, run_depth, win_sum, &r, f);
-  int64_t l = refs.name_at[r + 1] - refs.name_at[r] + n + 1;  // the name, a tab in front of each number, the line feed
-  for (int j = 0; j < n; j++) l += digits(f[j]);
-  len[k] = l;
+  len[k] = refs.name_at[r + 1] - refs.name_at[r] + fields_len(~0u, f, n) + 1;  // the name, a tab in front of each number, the line feed
 }
 
 __global__ __launch_bounds__(kThreads) void k_depth_line_fill(int64_t n_lines, DepthRefs refs, int64_t window, const int32_t *run_ref,
@@ -384,14 +341,8 @@ __global__ __launch_bounds__(kThreads) void k_depth_line_fill(int64_t n_lines, D
   const char *name = refs.names + refs.name_at[r];
   const int64_t l_name = refs.name_at[r + 1] - refs.name_at[r];
   for (int64_t j = 0; j < l_name; j++) *o++ = name[j];
-  for (int j = 0; j < n; j++) {
-    *o++ = '\t';
-    o = put(o, f[j]);
-  }
-  *o = '\n';
+  *put_fields(o, ~0u, f, n) = '\n';
 }
-
-inline unsigned blocks_of(int64_t n, int per = kThreads) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
 

@@ -17,6 +17,7 @@
 
 #include "bam_eval.h"
 #include "bam_fields.h"
+#include "device_util.h"
 
 namespace pbsim {
 
@@ -187,8 +188,6 @@ __global__ __launch_bounds__(kThreads) void k_eval_verdict(const uint64_t *t_ptr
     if (x) atomicAdd(k < 512 ? &hist[k] : &res[k - 512], (unsigned long long)x);
   }
 }
-
-inline unsigned blocks_of(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 }  // namespace
 

@@ -5,9 +5,8 @@
 // that no lane walks back over an insertion) lie beside it.  The rule: include/pbsim3_amd.h, tests/lift_model.py.
 //
 //   kept, check : one lane per variant base: the scan's input; rule 2 against the scan's output.
-//   span        : one wave per record.  The ops 64 a round, the wave's prefix sums of their column, reference and query advances in
-//                 the wave's part of LDS (k_err_columns' shape); the round's columns 64 at a time, each lane finding its op by a
-//                 binary search among the 64 prefix values and reading origin[] at its variant base.  It leaves the first and the
+//   span        : one wave per record, its columns walked by bam_cigar.h's walk_columns (the walk of k_err_columns and of the
+//                 pileup, here over the whole record); each lane reads origin[] at its column's variant base.  It leaves the first and the
 //                 last column that stays M, their query indices, the lifted pos, the clips and the verdict.
 //   runs        : the same walk over the columns of the core alone, twice.  A lane's column gives up to two pieces of the lifted
 //                 CIGAR: the D columns of the original bases the variant genome deleted in front of it, and its own M, I or D.
@@ -25,8 +24,7 @@
 
 #include <rocprim/device/device_scan.hpp>
 
-#include "bam_aux.h"
-#include "bam_fields.h"
+#include "bam_cigar.h"
 #include "bam_lift.h"
 #include "bam_tags.h"
 
@@ -38,32 +36,6 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kRecBlocksMax = 4096;  // workgroups of the per-record wave passes: their waves stride over the records
 constexpr int kSizeBits = kBamSamplePacking.size_bits;
-
-typedef unsigned long long u64;
-
-enum : uint32_t { kOpM = 0, kOpI = 1, kOpD = 2, kOpN = 3, kOpS = 4, kOpH = 5, kOpP = 6, kOpNone = 15 };
-
-__device__ __forceinline__ u64 wave_sum(u64 x) {
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
-}
-__device__ __forceinline__ u64 wave_scan(u64 x, int lane) {  // inclusive
-  for (int d = 1; d < 64; d <<= 1) {
-    const u64 y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  return x;
-}
-__device__ __forceinline__ void advances(uint32_t v, u64 *col, u64 *ref, u64 *query) {
-  const uint32_t op = v & 15u;
-  const u64 n = v >> 4;
-  const bool m = op == 0 || op == 7 || op == 8;
-  *col = m || op == 1 || op == 2 ? n : 0;
-  *ref = m || op == 2 || op == 3 ? n : 0;
-  *query = m || op == 1 || op == 4 ? n : 0;
-}
-__device__ __forceinline__ uint32_t ref_class(uint32_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
-__device__ __forceinline__ uint32_t code_class(uint32_t nib) { return nib == 1 ? 0u : nib == 2 ? 1u : nib == 4 ? 2u : nib == 8 ? 3u : 4u; }
 
 __global__ __launch_bounds__(kThreads) void k_lift_kept(const int32_t *origin, int64_t n, int32_t *kept) {
   const int64_t v = (int64_t)blockIdx.x * kThreads + threadIdx.x;
@@ -78,63 +50,6 @@ __global__ __launch_bounds__(kThreads) void k_lift_check(const int32_t *origin, 
   if (o >= 0) kind = o >= l_orig ? kLiftBadRange : o <= before ? kLiftBadOrder : 0;
   else if (o != (before < 0 ? kLiftFront : -1 - before)) kind = kLiftBadAnchor;
   if (kind) atomicMin(&cells[kLiftCellOrigin], (u64)v << 2 | (u64)kind);
-}
-
-// the wave's part of LDS: where each op of the round begins, and the op
-struct WaveLds {
-  u64 col[64], ref[64], query[64];
-  uint32_t op[64];
-};
-
-// The columns [x_lo, x_hi) of the n ops at `ops`, by the whole wave: f(valid, x, op, rp, qp) is called by all 64 lanes together
-// for 64 columns at a time; op is 0 (M = X), 1 or 2, rp the variant base of an M or D column, qp the query index of an M or I.
-template <class F>
-__device__ __forceinline__ void walk_columns(const uint8_t *ops, int64_t n, int64_t pos, u64 x_lo, u64 x_hi, int lane, WaveLds *w, F f) {
-  u64 run_col = 0, run_ref = (u64)pos, run_query = 0;
-  for (int64_t k0 = 0; k0 < n && run_col < x_hi; k0 += 64) {
-    const uint32_t v = k0 + lane < n ? ld32(ops + 4 * (k0 + lane)) : 0u;
-    u64 col, ref, query;
-    advances(v, &col, &ref, &query);
-    const u64 in_col = wave_scan(col, lane), in_ref = wave_scan(ref, lane), in_query = wave_scan(query, lane);
-    __builtin_amdgcn_wave_barrier();  // (the lanes' searches of the round before are over)
-    w->col[lane] = run_col + in_col - col, w->ref[lane] = run_ref + in_ref - ref, w->query[lane] = run_query + in_query - query;
-    w->op[lane] = v;
-    __builtin_amdgcn_wave_barrier();
-    const u64 round_cols = __shfl(in_col, 63, 64);
-    const u64 lo = max(x_lo, run_col), hi = min(x_hi, run_col + round_cols);
-    for (u64 x0 = lo; x0 < hi; x0 += 64) {
-      const u64 x = x0 + lane;
-      const bool valid = x < hi;
-      const u64 xs = valid ? x : hi - 1;
-      int i = 0;  // the last op of the round that begins at or before x: the one that holds it
-      for (int d = 32; d >= 1; d >>= 1)
-        if (w->col[i + d] <= xs) i += d;
-      uint32_t op = w->op[i] & 15u;
-      op = op == 7 || op == 8 ? 0u : op;
-      const u64 off = xs - w->col[i];
-      f(valid, x, op, w->ref[i] + off, w->query[i] + off);
-    }
-    run_col += round_cols, run_ref += __shfl(in_ref, 63, 64), run_query += __shfl(in_query, 63, 64);
-  }
-}
-
-// the record's fields the column passes need
-struct RecView {
-  const uint8_t *p, *ops, *bases;
-  int64_t n_ops, pos;
-  u64 l_seq;
-  int32_t ref_id;
-};
-__device__ __forceinline__ RecView view_of(const ErrRecs &a, int64_t r) {
-  RecView v;
-  v.p = a.stream + (int64_t)(a.rec[r] >> kSizeBits);
-  v.ops = a.stream + a.cig_at[r];
-  v.n_ops = a.n_ops[r];
-  v.pos = (int32_t)ld32(v.p + kBamPos);
-  v.l_seq = ld32(v.p + kBamLSeq);
-  v.ref_id = (int32_t)ld32(v.p + kBamRefId);
-  v.bases = v.p + kBamFixed + v.p[kBamLReadName] + 4 * (int64_t)ld16(v.p + kBamNCigarOp);
-  return v;
 }
 
 __global__ __launch_bounds__(kThreads) void k_lift_span(ErrRecs a, const LiftRef *refs, LiftRec *lr, u64 *cells) {
@@ -184,19 +99,21 @@ __global__ __launch_bounds__(kThreads) void k_lift_span(ErrRecs a, const LiftRef
     bool found = false;
     u64 x_first = 0, x_last = 0, q_first = 0, q_last = 0, to_ins = 0, vanished = 0;
     int32_t pos_out = 0;
-    walk_columns(rv.ops, rv.n_ops, rv.pos, 0, col_sum, lane, w, [&](bool valid, u64 x, uint32_t op, u64 rp, u64 qp) {
-      const bool on_ref = valid && op != kOpI && rp < (u64)ref.l_var;
-      const int32_t o = on_ref ? ref.origin[rp] : 0;
-      const u64 kept = __ballot(on_ref && op == kOpM && o >= 0);
-      to_ins += on_ref && op == kOpM && o < 0;
-      vanished += on_ref && op == kOpD && o < 0;
+    ColumnRange range = range_of(rv);
+    range.x_hi = col_sum;
+    walk_columns(range, lane, w, NoOpHook(), [&](const Column &c) {
+      const bool on_ref = c.valid && c.op != kOpI && c.rp < (u64)ref.l_var;
+      const int32_t o = on_ref ? ref.origin[c.rp] : 0;
+      const u64 kept = __ballot(on_ref && c.op == kOpM && o >= 0);
+      to_ins += on_ref && c.op == kOpM && o < 0;
+      vanished += on_ref && c.op == kOpD && o < 0;
       if (!kept) return;
       const int lo = __ffsll((long long)kept) - 1, hi = 63 - __clzll((long long)kept);
       if (!found) {
         found = true;
-        x_first = __shfl(x, lo, 64), q_first = __shfl(qp, lo, 64), pos_out = __shfl(o, lo, 64);
+        x_first = __shfl(c.x, lo, 64), q_first = __shfl(c.qp, lo, 64), pos_out = __shfl(o, lo, 64);
       }
-      x_last = __shfl(x, hi, 64), q_last = __shfl(qp, hi, 64);
+      x_last = __shfl(c.x, hi, 64), q_last = __shfl(c.qp, hi, 64);
     });
     to_ins = wave_sum(to_ins), vanished = wave_sum(vanished);
     out.verdict = found ? kLvLift : kLvUnplaced;
@@ -240,7 +157,12 @@ __global__ __launch_bounds__(kThreads) void k_lift_runs(ErrRecs a, const LiftRef
     u64 starts = 0;             // the runs begun so far (wave-uniform)
     uint32_t last_op = kOpNone;  // the op of the last piece so far (wave-uniform)
     u64 n_m = 0, n_i = 0, n_d = 0, n_gap = 0, n_sub = 0;
-    walk_columns(rv.ops, rv.n_ops, rv.pos, (u64)me.x_first, (u64)me.x_last + 1, lane, w, [&](bool valid, u64 x, uint32_t op, u64 rp, u64 qp) {
+    ColumnRange range = range_of(rv);
+    range.x_lo = (u64)me.x_first, range.x_hi = (u64)me.x_last + 1;
+    walk_columns(range, lane, w, NoOpHook(), [&](const Column &c) {
+      const bool valid = c.valid;
+      const uint32_t op = c.op;
+      const u64 x = c.x, rp = c.rp, qp = c.qp;
       const bool on_ref = valid && op != kOpI && rp < (u64)ref.l_var;
       const int32_t o = on_ref ? ref.origin[rp] : -1;
       // this column's own piece and the gap in front of it
@@ -277,7 +199,7 @@ __global__ __launch_bounds__(kThreads) void k_lift_runs(ErrRecs a, const LiftRef
       } else {
         n_m += t == kOpM, n_i += t == kOpI, n_d += (t == kOpD) + gap, n_gap += gap;
         if (t == kOpM && rv.l_seq != 0 && qp < rv.l_seq && (u64)o < (u64)ref.l_orig) {
-          const uint32_t nib = (rv.bases[qp >> 1] >> (qp & 1 ? 0 : 4)) & 15u;
+          const uint32_t nib = base_code(rv.bases, qp);
           const uint32_t rc = ref_class(g_seq[o]), bc = nib == 0 ? rc : code_class(nib);
           n_sub += rc != 4 && bc != 4 && rc != bc;
         }
@@ -472,7 +394,6 @@ __global__ __launch_bounds__(kThreads) void k_lift_write(ErrRecs a, const LiftRe
   }
 }
 
-inline unsigned blocks_of(int64_t n, int per = kThreads) { return (unsigned)((n + per - 1) / per); }
 inline unsigned wave_blocks(int64_t n_rec) { return (unsigned)std::min<int64_t>((n_rec + kWaves - 1) / kWaves, kRecBlocksMax); }
 
 }  // namespace

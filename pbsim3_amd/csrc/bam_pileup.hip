@@ -3,10 +3,8 @@
 // include/pbsim3_amd.h.
 //
 //   columns : (k_pile_columns<false> of bam_pileup_walk.h, which pbsim_bam_consensus runs with its log switched on)
-//             one wave per segment, the waves striding over the segments, walking a segment as k_err_columns does: a round loads 64
-//             ops of the block, forms the wave's prefix sums of their column, reference and query advances and leaves them in the
-//             wave's part of LDS; then the round's columns inside the segment are taken 64 at a time, each lane finding its op by
-//             a binary search among the 64 prefix values.  Every M = X or D column issues one atomic add on a 32-bit cell of the
+//             one wave per segment, the waves striding over the segments, walking a segment with bam_cigar.h's walk_columns as
+//             k_err_columns does.  Every M = X or D column issues one atomic add on a 32-bit cell of the
 //             table in global memory, laid out [position][8]: a wave's 64 consecutive columns fall into one span of 2 KB.  An I op
 //             adds to the ins cell of the position before it, by the lane that holds the op, in the segment that holds its first
 //             column; where nothing of the reference is consumed yet it counts in the wave's LDS cell, flushed once per workgroup.
@@ -27,7 +25,7 @@ namespace pbsim {
 
 namespace {
 
-using namespace pilewalk;  // the column pass, the wave's sums and a site's cells (bam_pileup_walk.h)
+using namespace pilewalk;  // the column pass and a site's cells (bam_pileup_walk.h)
 
 constexpr int kSiteBlocksMax = 2048;  // workgroups of the site pass
 static_assert(kPileTile == kThreads, "a tile of the text is one workgroup's positions");
@@ -108,21 +106,6 @@ __global__ __launch_bounds__(kThreads) void k_pile_sites(PileGenome g, const uin
   }
 }
 
-__device__ __forceinline__ int digits(u64 x) {
-  int n = 1;
-  while (x >= 10) x /= 10, n++;
-  return n;
-}
-__device__ __forceinline__ char *put(char *o, u64 x) {
-  const int n = digits(x);
-  for (int k = n - 1; k >= 0; k--, x /= 10) o[k] = (char)('0' + x % 10);
-  return o + n;
-}
-__device__ __forceinline__ char *put(char *o, const char *s) {
-  while (*s) *o++ = *s++;
-  return o;
-}
-
 __device__ __forceinline__ bool listed(uint32_t c, int format) {
   if (c == (uint32_t)kPileNoSite) return false;
   const uint32_t kind = c & 7u;
@@ -194,8 +177,8 @@ inline int64_t tiles_of(const PileGenome &g) { return (g.total + kPileTile - 1) 
 void launch_pileup_columns(ErrRecs r, ErrRefs refs, ErrGenome g, const ErrSegment *seg, int64_t n_seg, uint32_t min_baseq, uint32_t *table,
                            unsigned long long *cells, hipStream_t s) {
   if (n_seg <= 0) return;
-  hipLaunchKernelGGL(k_pile_columns<false>, dim3((unsigned)column_blocks(n_seg)), dim3(kThreads), 0, s, r, refs, g.seq, kBamSamplePacking.size_bits, seg,
-                     n_seg, min_baseq, table, cells, NoLog());
+  hipLaunchKernelGGL(k_pile_columns<false>, dim3((unsigned)column_blocks(n_seg, kWaves, kSegBlocksMax)), dim3(kThreads), 0, s, r, refs, g.seq, seg, n_seg,
+                     min_baseq, table, cells, NoLog());
 }
 
 void launch_pileup_sites(PileGenome g, const uint32_t *table, int64_t min_depth, uint8_t *cls, unsigned long long *cells, hipStream_t s) {

@@ -19,6 +19,7 @@
 #include "bam_chain.h"
 #include "bam_fields.h"
 #include "bam_sort.h"
+#include "device_util.h"
 
 namespace pbsim {
 
@@ -128,8 +129,6 @@ __global__ __launch_bounds__(kThreads) void k_bs_gather(const uint8_t *stream, u
     *reinterpret_cast<uint4 *>(out + d) = o;
   }
 }
-
-inline unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
 

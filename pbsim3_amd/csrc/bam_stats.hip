@@ -2,10 +2,11 @@
 // records located (bam_scan.hip, bam_chain.cpp).  The rule: include/pbsim3_amd.h.
 //
 //   records : one lane per record: its class, its quality field's place, its length, and for an aligned record the CIGAR sums
-//             (the CG tag's array where the field is the <l_seq>S<span>N placeholder) and NM (bam_aux.h).  A record of more
-//             than 64 ops is taken by its whole wave, op k by lane k mod 64, the sums reduced across the wave (k_depth_events'
-//             shape).  The counts, the length cells and the totals over scored records are added up per workgroup in LDS and
-//             flushed with one vector atomic per cell that is not 0; the identity histogram takes one atomic per scored record.
+//             (the CG tag's array where the field is the <l_seq>S<span>N placeholder) and NM (bam_cigar.h's resolve_cigar).  A
+//             record of more than 64 ops is taken by its whole wave, op k by lane k mod 64, the sums reduced across the wave
+//             (bam_cigar.h's each_long_cigar and wave_cigar_sums).  The counts, the length cells and the totals over scored
+//             records are added up per workgroup in LDS and flushed with one vector atomic per cell that is not 0; the identity
+//             histogram takes one atomic per scored record.
 //   quals   : the quality fields of the records that have qualities, laid end to end, in tiles of kStatsTile bytes: 64
 //             consecutive bytes of that axis per lane.  A lane finds its first record by a binary search in the scanned lengths
 //             and steps to the later ones, so a long read spreads over many workgroups and short reads share one.  Each piece
@@ -29,8 +30,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
-#include "bam_aux.h"
-#include "bam_fields.h"
+#include "bam_cigar.h"
 #include "bam_stats.h"
 
 namespace pbsim {
@@ -41,47 +41,11 @@ constexpr int kThreads = 256;
 constexpr int kChunk = kStatsTile / kThreads;
 static_assert(kChunk == 64, "a lane takes 64 bytes of the quality axis");
 
-typedef unsigned long long u64;
-
-// floor(x * 1000000 / c) for x <= c < 2^62, inside 64 bits: Horner over the bits of 1000000, quotient and remainder kept apart
-__device__ __forceinline__ u64 ppm_of(u64 x, u64 c) {
-  u64 q = 0, r = 0;
-  for (int b = 19; b >= 0; b--) {
-    q <<= 1;
-    r <<= 1;
-    if ((1000000u >> b) & 1u) r += x;  // r < 3 c
-    if (r >= c) r -= c, q++;
-    if (r >= c) r -= c, q++;
-  }
-  return q;
-}
-
 // 1000000 - floor(esum * 1000000 / (l_seq << 32)) for esum <= l_seq << 32 < 2^63: the division by 2^32 first, which the
 // nested floors allow
 __device__ __forceinline__ u64 acc_ppm_of(u64 esum, u64 l_seq) {
   const u64 t = (esum >> 32) * 1000000ull + (((esum & 0xffffffffull) * 1000000ull) >> 32);
   return 1000000ull - t / l_seq;
-}
-
-struct CigarSums {
-  u64 m = 0, ins = 0, del = 0, soft = 0, hard = 0, ins_events = 0, del_events = 0;
-  bool bad = false;
-};
-
-__device__ __forceinline__ void add_op(uint32_t v, CigarSums &c) {
-  const uint32_t op = v & 15u;
-  const u64 n = v >> 4;
-  if (op > 8) c.bad = true;
-  else if (op == 0 || op == 7 || op == 8) c.m += n;
-  else if (op == 1) c.ins += n, c.ins_events += n != 0;
-  else if (op == 2) c.del += n, c.del_events += n != 0;
-  else if (op == 4) c.soft += n;
-  else if (op == 5) c.hard += n;
-}
-
-__device__ __forceinline__ u64 wave_sum(u64 x) {
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
 }
 
 // the workgroup's cells of the record pass, and where each goes in the call's cells
@@ -149,22 +113,8 @@ __global__ __launch_bounds__(kThreads) void k_stats_records(StatsRecs a, int siz
         }
       }
       if (aligned) {
-        cig = field;
-        n_ops = n_cigar;
-        int want = kAuxNm;
-        if (n_ops == 2) {
-          const uint32_t op0 = ld32(cig), op1 = ld32(cig + 4);
-          if ((op0 & 15u) == 4 && (op0 >> 4) == l_seq && (op1 & 15u) == 3) want |= kAuxCg;
-        }
-        const uint8_t *aux = q + (int64_t)l_seq;
-        BamAux ax;
-        const int got = aux > end ? -1 : bam_aux_walk(aux, end, want, &ax);
-        if (got < 0) {
-          bad = true;
-        } else {
-          if (got & kAuxCg) cig = ax.cg, n_ops = ax.n_cg;
-          if (got & kAuxNm) has_nm = true, nm = ax.nm;
-        }
+        const ResolvedCigar rc = resolve_cigar(p, end, l_seq, kAuxCg | kAuxNm);
+        cig = rc.ops, n_ops = rc.n_ops, bad = rc.bad, has_nm = rc.has_nm, nm = rc.nm;
       }
     }
     a.qoff[r] = qoff;
@@ -175,18 +125,10 @@ __global__ __launch_bounds__(kThreads) void k_stats_records(StatsRecs a, int siz
   CigarSums c;
   if (mine && n_ops <= 64)
     for (uint32_t k = 0; k < n_ops; k++) add_op(ld32(cig + 4 * k), c);
-  // the records of more than 64 ops, one after the other, each by the whole wave
-  for (uint64_t big = __ballot(mine && n_ops > 64); big; big &= big - 1) {
-    const int src = __ffsll((long long)big) - 1;
-    const uint8_t *c_ops = (const uint8_t *)__shfl((int64_t)cig, src, 64);
-    const int64_t n = (int64_t)__shfl(n_ops, src, 64);
-    CigarSums part;
-    for (int64_t k = lane; k < n; k += 64) add_op(ld32(c_ops + 4 * k), part);
-    part.m = wave_sum(part.m), part.ins = wave_sum(part.ins), part.del = wave_sum(part.del), part.soft = wave_sum(part.soft);
-    part.hard = wave_sum(part.hard), part.ins_events = wave_sum(part.ins_events), part.del_events = wave_sum(part.del_events);
-    part.bad = __ballot(part.bad) != 0;
-    if (lane == src) c = part;
-  }
+  each_long_cigar(mine, cig, n_ops, [&](int src, const uint8_t *c_ops, int64_t n) {
+    const CigarSums whole = wave_cigar_sums(c_ops, n, lane);
+    if (lane == src) c = whole;
+  });
   if (mine && c.bad) bad = true;
   if (mine && !bad) {
     const u64 indel = c.ins + c.del, cols = c.m + indel;
@@ -225,17 +167,6 @@ __global__ __launch_bounds__(kThreads) void k_stats_records(StatsRecs a, int siz
     atomicMin(&cells[kStatsCellLenMin], (u64)sh_min);
     atomicMax(&cells[kStatsCellLenMax], (u64)sh_max);
   }
-}
-
-// the last r in [0, n) with table[r] <= x (table ascending, table[0] <= x)
-__device__ __forceinline__ int64_t last_at_most(const int64_t *table, int64_t n, int64_t x) {
-  int64_t lo = 0, hi = n;  // table[lo] <= x, table[hi] > x (or hi == n)
-  while (hi - lo > 1) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (table[mid] <= x) lo = mid;
-    else hi = mid;
-  }
-  return lo;
 }
 
 __global__ __launch_bounds__(kThreads) void k_stats_quals(StatsRecs a, int64_t n_bytes, const u64 *e_table, u64 *cells) {
@@ -361,17 +292,6 @@ __global__ void k_stats_nx(const uint32_t *sorted, const u64 *sums, int64_t n_al
   out[k] = sorted[lo];
 }
 
-__device__ __forceinline__ int digits(u64 x) {
-  int n = 1;
-  while (x >= 10) x /= 10, n++;
-  return n;
-}
-__device__ __forceinline__ char *put(char *o, u64 x) {
-  const int n = digits(x);
-  for (int k = n - 1; k >= 0; k--, x /= 10) o[k] = (char)('0' + x % 10);
-  return o + n;
-}
-
 // the nine numbers behind a counted record's name and class, and which of them the record defines (bit j: f[j])
 __device__ __forceinline__ uint32_t line_fields(const StatsRecs &a, int64_t r, uint32_t st, u64 f[9]) {
   uint32_t has = 1;
@@ -400,8 +320,7 @@ __global__ __launch_bounds__(kThreads) void k_stats_line_sizes(StatsRecs a, int6
     const uint32_t has = line_fields(a, r, st, f);
     const uint8_t *name = a.stream + (int64_t)(a.rec[r] >> kBamSamplePacking.size_bits) + kBamFixed;
     while (name[l]) l++;  // (the locator: the name ends with a NUL inside the record)
-    l += 3;               // the tab and the class, the line feed
-    for (int j = 0; j < 9; j++) l += 1 + ((has >> j) & 1u ? digits(f[j]) : 1);
+    l += 3 + fields_len(has, f, 9);  // the tab and the class, the line feed
   }
   len[r] = l;
 }
@@ -417,15 +336,8 @@ __global__ __launch_bounds__(kThreads) void k_stats_line_fill(StatsRecs a, const
   for (const uint8_t *name = a.stream + (int64_t)(a.rec[r] >> kBamSamplePacking.size_bits) + kBamFixed; *name; name++) *o++ = (char)*name;
   *o++ = '\t';
   *o++ = st & kStAligned ? 'A' : 'U';
-  for (int j = 0; j < 9; j++) {
-    *o++ = '\t';
-    if ((has >> j) & 1u) o = put(o, f[j]);
-    else *o++ = '*';
-  }
-  *o = '\n';
+  *put_fields(o, has, f, 9) = '\n';
 }
-
-inline unsigned blocks_of(int64_t n, int per = kThreads) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
 

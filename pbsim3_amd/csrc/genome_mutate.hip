@@ -57,23 +57,9 @@ __device__ __forceinline__ u64 wave_scan_max(u64 x, int lane) {  // inclusive
   return x;
 }
 
-// the exclusive prefix sum of v over the workgroup and *all, the workgroup's sum; every lane of the workgroup calls it
-__device__ __forceinline__ u64 block_scan(u64 v, u64 *sh_wave, int wave, int lane, u64 *all) {
-  const u64 incl = wave_scan(v, lane);
-  __syncthreads();  // (the values of the call before have been read)
-  if (lane == 63) sh_wave[wave] = incl;
-  __syncthreads();
-  u64 before = 0, sum = 0;
-  for (int w = 0; w < kWaves; w++) {
-    if (w < wave) before += sh_wave[w];
-    sum += sh_wave[w];
-  }
-  *all = sum;
-  return before + incl - v;
-}
-
-// the same with the maximum: the largest v of the lanes in front (0: none), *all the workgroup's largest
-__device__ __forceinline__ u64 block_scan_max(u64 v, u64 *sh_wave, int wave, int lane, u64 *all) {
+// block_scan (device_util.h) with the maximum: the largest v of the lanes in front (0: none), *all the workgroup's largest
+template <int kWaves>
+__device__ __forceinline__ u64 block_scan_max(u64 v, u64 (&sh_wave)[kWaves], int wave, int lane, u64 *all) {
   const u64 incl = wave_scan_max(v, lane);
   u64 prev = __shfl_up(incl, 1, 64);
   if (lane == 0) prev = 0;
@@ -270,21 +256,6 @@ __global__ __launch_bounds__(kThreads) void k_mut_bases(PileGenome g, pbsim_muta
     }
   }
   if (!kFill) add_cells(n_cell, sh, cells, tid, wave, lane);
-}
-
-__device__ __forceinline__ int digits(u64 x) {
-  int n = 1;
-  while (x >= 10) x /= 10, n++;
-  return n;
-}
-__device__ __forceinline__ char *put(char *o, u64 x) {
-  const int n = digits(x);
-  for (int k = n - 1; k >= 0; k--, x /= 10) o[k] = (char)('0' + x % 10);
-  return o + n;
-}
-__device__ __forceinline__ char *put(char *o, const char *s) {
-  while (*s) *o++ = *s++;
-  return o;
 }
 
 template <bool kFill>

@@ -45,14 +45,9 @@ namespace {
 using pilewalk::kThreads;
 using pilewalk::kWaves;
 using pilewalk::record_of;
-using pilewalk::u64;
-using pilewalk::wave_max;
 using vcftext::base_or_n;
-using vcftext::block_scan;
-using vcftext::digits;
 using vcftext::length_of;
 using vcftext::line_begins;
-using vcftext::put;
 using vcftext::put_span;
 using vcftext::upper;
 

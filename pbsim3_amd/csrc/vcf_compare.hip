@@ -30,7 +30,6 @@
 
 #include <algorithm>
 
-#include "bam_pileup_walk.h"
 #include "vcf_compare.h"
 #include "vcf_text.h"
 
@@ -38,15 +37,11 @@ namespace pbsim {
 
 namespace {
 
-using pilewalk::kThreads;
-using pilewalk::kWaves;
-using pilewalk::u64;
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
 using vcftext::base_or_n;
-using vcftext::block_scan;
-using vcftext::digits;
 using vcftext::length_of;
 using vcftext::line_begins;
-using vcftext::put;
 using vcftext::put_span;
 using vcftext::upper;
 

@@ -1,33 +1,14 @@
 // vcf_text.h -- what the kernels that read VCF text in HBM and write text back share (vcf_compare.hip, vcf_apply.hip): where a data
-// line begins, the workgroup's prefix sum, the bytes' classes and the small writers of numbers and spans.  Device code only;
-// internal: nothing here is part of include/pbsim3_amd.h.
+// line begins, the bytes' classes and the writer of a column's span.  The sums and the writers of numbers are device_util.h's.
+// Device code only; internal: nothing here is part of include/pbsim3_amd.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "bam_pileup_walk.h"
+#include "device_util.h"
 
 namespace pbsim {
 namespace vcftext {
-
-using pilewalk::kWaves;
-using pilewalk::u64;
-using pilewalk::wave_scan;
-
-// the exclusive prefix sum of v over the workgroup and *all, the workgroup's sum; every lane of the workgroup calls it
-__device__ __forceinline__ u64 block_scan(u64 v, u64 *sh_wave, int wave, int lane, u64 *all) {
-  const u64 incl = wave_scan(v, lane);
-  __syncthreads();  // (the values of the call before have been read)
-  if (lane == 63) sh_wave[wave] = incl;
-  __syncthreads();
-  u64 before = 0, sum = 0;
-  for (int w = 0; w < kWaves; w++) {
-    if (w < wave) before += sh_wave[w];
-    sum += sh_wave[w];
-  }
-  *all = sum;
-  return before + incl - v;
-}
 
 __device__ __forceinline__ uint32_t upper(uint32_t c) { return c >= 'a' && c <= 'z' ? c - 32u : c; }
 __device__ __forceinline__ bool base_or_n(uint32_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T' || c == 'N'; }
@@ -50,20 +31,6 @@ __device__ __forceinline__ u64 line_begins(const uint8_t *bytes, int64_t i0, int
   return n;
 }
 
-__device__ __forceinline__ int digits(u64 x) {
-  int n = 1;
-  while (x >= 10) x /= 10, n++;
-  return n;
-}
-__device__ __forceinline__ char *put(char *o, u64 x) {
-  const int n = digits(x);
-  for (int k = n - 1; k >= 0; k--, x /= 10) o[k] = (char)('0' + x % 10);
-  return o + n;
-}
-__device__ __forceinline__ char *put(char *o, const char *s) {
-  while (*s) *o++ = *s++;
-  return o;
-}
 // a column as the file has it, `.` for one the line lacks or that is empty
 __device__ __forceinline__ char *put_span(char *o, const uint8_t *p, uint32_t n) {
   if (n == 0) *o++ = '.';
